@@ -8,7 +8,11 @@ fusionnet/run-testing.py:151-204 (features -> cost volume -> encoder -> re-proje
 already resident in HBM.  N > 1: one independent sequence per rank (weak scaling), no collective on the data path; the
 barrier + max-over-ranks timing is the only communication.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  ``--dump-outputs DIR`` writes the depth
+map the last timed step returned to DIR/depth.npy (seeded inputs: the same arguments give the same inputs, so builds compare output
+for output).  ``--full`` adds, after the headline, every other figure of the line (section "Extra objects" and ``full_legs``).
+
+Extra objects on the line (--full):
 * ``roofline``     -- the fused warp + cost-volume kernel: algorithmic bytes per launch / its average duration, measured
                       here with HIP events around a back-to-back hipGraph of launches on the launch stream;
 * ``cpu_baseline`` -- the CPU oracle pipeline (oracle/fusionnet_cpu.py, "port" of the reference loop) timed on this
@@ -70,6 +74,11 @@ def parse():
                          "The headline value is always one sequence per GPU (BASELINE.json configs[2]).")
     ap.add_argument("--batched-steps", type=int, default=40)
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary legs (collector on, causal pipeline, pairnet)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the line can report: roofline and per-kernel timings, launches per frame, "
+                         "golden rel-L1, batched / secondary / drop-in / pairnet legs, CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (inference: the depth map, float32)")
     return ap.parse_args()
 
 
@@ -466,6 +475,15 @@ def finite_or_null(value):
     return value
 
 
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as ``directory/<name>.npy`` (float64 where it is held in float64, float32 otherwise), so that two builds
+    can be compared output for output on the same arguments (the inputs are seeded)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, value in arrays.items():
+        a = value.detach().cpu().numpy() if isinstance(value, torch.Tensor) else np.asarray(value)
+        np.save(os.path.join(directory, f"{name}.npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
 def issue_roofline(per_geometry, variants):
     """Issue-time accounting of the engine's sweep kernels from the newest committed PMC profile (profiles/r*_sweep_issue_pmc.json, counted on
     index line 0): per kernel the instruction-issue time per SIMD against its mean duration on the timed steps that ran it; top level = the
@@ -777,6 +795,8 @@ def train_mode(args, world, rank, device):
     mark = region_marker(device) if args.mark_region else None
     elapsed = timed_region(step, max(args.warmup, 1), args.steps, world, device, before=mark, after=mark)
     loss = last["loss"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss})
     db_after = {f: os.path.getsize(os.path.join(db_dir, f)) for f in os.listdir(db_dir)} if os.path.isdir(db_dir) else {}
     new_files = sorted(f for f in db_after if f not in db_before)
     grown = sorted(f for f in db_after if f in db_before and db_after[f] != db_before[f])
@@ -806,10 +826,11 @@ def train_mode(args, world, rank, device):
 
 
 def relaunch_under_torchrun(gpus):
-    """`python bench.py --gpus N` without a launcher (WORLD_SIZE unset): replace this process by the contract's own launch line --
-    one rank per GPU on this node, rendezvous on 127.0.0.1 -- so that the command works in either shape and still prints one JSON line
-    (rank 0's).  Driven on CPU by tests/test_bench_harness.py."""
+    """`python bench.py --gpus N` without a launcher (WORLD_SIZE unset): run the contract's own launch line as a child process -- one rank
+    per GPU on this node, rendezvous on 127.0.0.1 -- and exit with its status, so that the command works in either shape and still prints
+    one JSON line (rank 0's).  Driven on CPU by tests/test_bench_harness.py."""
     import socket
+    import subprocess
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
@@ -819,7 +840,8 @@ def relaunch_under_torchrun(gpus):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.run(cmd).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)
 
 
 def stub_mode(args, world, rank):
@@ -840,10 +862,216 @@ def stub_mode(args, world, rank):
         dist.destroy_process_group()
 
 
+def full_legs(args, engine, modules, device, seq, M, rank, world):
+    """--full (rank 0, after the headline): every figure of the line beyond the headline -- the sweep kernel's rooflines on the timed
+    steps' geometries, the whole keyframe index and all its pairs (+ comparison kernels), the other hot-path kernels, launches per frame,
+    the golden rel-L1, the batched, secondary, drop-in and pairnet legs and the CPU baseline, each on its own engine or harness.
+    Returns the extra keys of the line."""
+    picks, whole_index, all_pairs, mfma_variant = [], None, None, None
+    if args.no_roofline_leg:
+        kernel_s, alg_bytes, per_geometry, variants = float("nan"), (1 + M) * 32 * 128 * 160 * 4 + 64 * 128 * 160 * 4, [], []
+    else:
+        # the geometries of the TIMED steps (what a rocprofv3 kernel trace of this command's timed region averages over) ...
+        timed = [seq[M + args.warmup + i] for i in range(args.steps)]
+        kernel_s, alg_bytes, per_geometry, variants = measure_cost_volume_kernel(engine, M, args.kernel_reps, timed)
+        # ... and, secondary, 25 lines spread over the WHOLE keyframe index (the timed steps of a short run are its first lines)
+        picks, pose_sets = index_pose_sets(M, ROOFLINE_GEOMETRIES)
+        w_s, _, w_per, w_var = measure_cost_volume_kernel(engine, M, args.kernel_reps, pose_sets)
+        whole_index = {"kernel_us": w_s * 1e6, "frac": alg_bytes / w_s / 1e9 / HBM_PEAK_GBPS, "index_lines": picks,
+                       "kernel_us_per_geometry": [round(t * 1e6, 2) for t in w_per], "sweep_variant_per_geometry": w_var,
+                       "worst_us": max(w_per) * 1e6}
+        # ... and EVERY keyframe pair of the index (285 lines; fewer repetitions per pair): the figure that does not flatter
+        all_lines, all_sets = index_pose_sets(M, 10 ** 6)
+        reps_all = args.kernel_reps      # (round 6: as many back-to-back ops per graph as on the timed lines -- with 3 per graph the gap between two graph
+                                         # replays, ~5 - 10 us on the device, was 1.5 - 2 us of every op's figure)
+        a_s, _, a_per, a_var = measure_cost_volume_kernel(engine, M, reps_all, all_sets, rounds=2)
+        all_pairs = {"pairs": len(a_per), "kernel_us": a_s * 1e6, "frac": alg_bytes / a_s / 1e9 / HBM_PEAK_GBPS, "worst_us": max(a_per) * 1e6,
+                     "worst_index_line": all_lines[int(np.argmax(a_per))], "p90_us": float(np.percentile(a_per, 90)) * 1e6,
+                     "sweep_variants": {str(v): a_var.count(v) for v in sorted(set(a_var))}}
+        # Comparison legs, same harness, same geometries: (i) the LDS-tiled sweep as dvmvs_sweep_plan plans it (what the engine ran before round 6
+        # on the pairs it did not give to variant 6), (ii) variant 7 = the MFMA sweep as one work item per workgroup (round 5's launch shape; the
+        # same arithmetic, bit-identical volumes): what the persistent form buys (DESIGN.md section 4.1b)
+        t_s, _, t_per, t_var = measure_cost_volume_kernel(engine, M, args.kernel_reps, timed, tiled_plan=True)
+        ta_s, _, ta_per, _ = measure_cost_volume_kernel(engine, M, reps_all, all_sets, rounds=2, tiled_plan=True)
+        g_s, _, g_per, _ = measure_cost_volume_kernel(engine, M, args.kernel_reps, timed, force_variant=7)
+        ga_s, _, ga_per, _ = measure_cost_volume_kernel(engine, M, reps_all, all_sets, force_variant=7, rounds=2)
+        mfma_variant = {"tiled_plan": {"kernel": "sweep_tiled_kernel [+ sweep_spill_kernel] as dvmvs_sweep_plan plans it", "kernel_us_timed_steps": t_s * 1e6,
+                                       "kernel_us_all_pairs": ta_s * 1e6, "worst_us_all_pairs": max(ta_per) * 1e6, "p90_us_all_pairs": float(np.percentile(ta_per, 90)) * 1e6,
+                                       "pairs_where_faster_than_engine_choice": int(sum(1 for x, y in zip(ta_per, a_per) if x < y)),
+                                       "variants_timed_steps": {str(v): t_var.count(v) for v in sorted(set(t_var))}},
+                        "one_item_per_workgroup": {"kernel": "sweep_mfma_kernel (variant 7)", "kernel_us_timed_steps": g_s * 1e6, "kernel_us_all_pairs": ga_s * 1e6,
+                                                   "worst_us_all_pairs": max(ga_per) * 1e6, "p90_us_all_pairs": float(np.percentile(ga_per, 90)) * 1e6,
+                                                   "pairs_where_faster_than_engine_choice": int(sum(1 for x, y in zip(ga_per, a_per) if x < y))}}
+    achieved = alg_bytes / kernel_s / 1e9
+    # HBM bytes per op from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes: only when the committed measurement was taken on
+    # exactly the kernel sources that are being benchmarked, otherwise null (profiles/README.md says how to re-collect)
+    traffic, traffic_source = None, None
+    try:
+        import glob
+        import hashlib
+        digest = hashlib.sha256(b"".join(open(os.path.join(ROOT, "deep-video-mvs_amd", "csrc", f), "rb").read()
+                                         for f in ("sweep_tiled.hip", "sweep_mfma.hip", "cost_volume.hip", "plane_sweep.h", "sweep_sample.h"))).hexdigest()
+        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_cost_volume_pmc.json")), reverse=True):
+            pmc = json.load(open(path))
+            if pmc.get("shape") == [1, M, 32, 128, 160, 64] and pmc.get("kernel_sources_sha256") == digest:
+                traffic, traffic_source = pmc["hbm_bytes_per_launch"], os.path.relpath(path, ROOT)
+                break
+    except (OSError, ValueError, KeyError):
+        pass
+    # useful arithmetic of the op: per (pixel, plane, frame) 4 taps x C channels of FMA + 4 weight FMAs, 2 flop each
+    useful_flop = 128 * 160 * 64 * M * (4 * 32 + 4) * 2
+    valu_tflops = useful_flop / kernel_s / 1e12
+    lds_bytes = 128 * 160 * 64 * M * 4 * 32 * 4
+    # (the LDS accounting below is the TILED formulation's -- the MFMA sweep reads 4 dot products per sample, not 4 x 32 channels: the steps that ran it are left out)
+    tiled_times = [t for t, v in zip(per_geometry, variants) if v not in (6, 7)]
+    tiled_s = sum(tiled_times) / len(tiled_times) if tiled_times else float("nan")
+    other_kernels = None if args.no_roofline_leg else measure_small_kernels(engine)
+    launches_per_frame = {}
+    try:     # kernel nodes of the captured frame graph (what one replay launches), where the runtime can dump a graph
+        counts = {f"n_meas={k[0]},has_previous={k[1]},sweep_variant={k[2]}": count_graph_kernels(g) for k, g in engine._graphs.items()}
+        launches_per_frame.update({k: v for k, v in counts.items() if v is not None})
+    except Exception:
+        pass
+    try:     # ... and the count a rocprofv3 kernel trace of THIS command's timed region recorded at the benchmarked look-ahead level
+        import glob      # (profiles/, per round: the newest round that has one)
+        level = 0 if args.no_feature_cache else args.lookahead
+        region = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]_bench_timed_region_lookahead{level}.csv")))[-1]
+        last = open(region).read().strip().splitlines()[-1].split(",")
+        launches_per_frame.update(profiled=float(last[5]) / float(last[7]), profiled_source=os.path.relpath(region, ROOT), profiled_lookahead=level)
+    except Exception:
+        pass
+    launches_per_frame = launches_per_frame or None
+    rel = golden_rel_l1(modules, device, args) if not args.no_rel_l1 else None
+    extra = {
+        "roofline": {"kernel": "sweep_mfma_persistent_kernel (variant 6: every pair since round 6, dvmvs_sweep_plan6); 1 launch = all planes x M frames",
+                     "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                     "sample": "frac/achieved/kernel_us: mean over the timed steps' keyframe pairs; all_pairs: all 285 index lines; whole_index: 25 spread",
+                     "all_pairs": all_pairs,
+                     "traffic": traffic, "traffic_source": traffic_source, "kernel_us": kernel_s * 1e6, "algorithmic_bytes": alg_bytes,
+                     # the channels-last copy of a keyframe's features that variant 6 reads: round 5 a launch per frame outside this accounting
+                     # (5 - 16 us in the frame), since round 6 written by the FPN smoothing layer's own epilogue (dvmvs_direct_conv_dual_fwd)
+                     "kernel_us_incl_layout": kernel_s * 1e6 + 0.0, "layout_launches_per_frame": 0 if getattr(engine, "sweep_mfma", False) and engine.direct_convs else 1,
+                     "geometries": f"{len(per_geometry)} timed steps = index lines {(M + args.warmup + 37 * rank) % 286}.. (nmeas+2 index), each as the engine launches it",
+                     "kernel_us_per_geometry": [round(t * 1e6, 2) for t in per_geometry],
+                     "sweep_variant_per_geometry": variants,
+                     "sweep_variants": {"2 (default: 3 x 48 KB boxes, 256 threads; two passes)": variants.count(2),
+                                        "3 (wide-baseline: 2 x 72 KB boxes, 512 threads; two passes)": variants.count(3),
+                                        "4 (default, single pass: the host's plan queues nothing)": variants.count(4),
+                                        "5 (wide-baseline, single pass)": variants.count(5),
+                                        "6 (correlate-then-interpolate on the fp32 matrix cores, persistent form; channels-last maps)": variants.count(6)},
+                     "engine_frames_per_sweep_variant": {str(k): v for k, v in sorted(engine.sweep_variant_counts.items())},
+                     "whole_index": whole_index},
+        # HBM is not what binds this op (13 MB of algorithmic traffic against 0.69 GFLOP of tap arithmetic and 1.3 GB of LDS
+        # reads): the same duration against the fp32 vector peak, counting only the useful tap FMAs
+        "roofline_valu": {"bound": "valu_fp32", "achieved": valu_tflops, "peak": FP32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                          "frac": valu_tflops / FP32_VALU_PEAK_TFLOPS, "useful_flop": useful_flop},
+        # the pipe this formulation is actually bound by: 4 taps x 32 channels x 4 B from LDS per (pixel, plane, frame).  "peak" is
+        # the ds_read_b128 rate of the chip; "pattern_floor_us" the measured floor of the kernel's own inner pattern (bank conflicts
+        # of the tap addresses and the packed FMAs between the reads included)
+        "roofline_lds": None if not tiled_times else {
+            "bound": "lds", "kernel": f"sweep_tiled_kernel ({len(tiled_times)} of the {len(per_geometry)} timed steps ran it)", "achieved": lds_bytes / tiled_s / 1e12,
+            "peak": LDS_PEAK_TBPS, "unit": "TB/s", "frac": lds_bytes / tiled_s / 1e12 / LDS_PEAK_TBPS, "lds_bytes": lds_bytes, "kernel_us": tiled_s * 1e6,
+            "pattern_floor_us": SWEEP_LDS_PATTERN_FLOOR_US, "frac_of_pattern_floor": SWEEP_LDS_PATTERN_FLOOR_US / (tiled_s * 1e6)},
+        # what the launch's duration is made of (round 5): instruction ISSUE.  Summed over a SIMD's waves, the cycles with an instruction
+        # issuing / executing (SQ_ACTIVE_INST_ANY of the committed PMC profile, index line 0) add up to the waves' lifetime in both sweep
+        # kernels: neither HBM nor LDS bandwidth nor the matrix pipe but the instruction count bounds them (DESIGN.md section 4.1b)
+        "roofline_issue": issue_roofline(per_geometry, variants) if per_geometry else None,
+        "roofline_comparison_kernels": mfma_variant,
+        "roofline_other": other_kernels,
+        "launches_per_frame": launches_per_frame,
+        "rel_l1": None if rel is None else {
+            "what": "depth rel-L1 mean(|d - d_ref| / d_ref) of this engine configuration (graph replay included) vs the REFERENCE forward "
+                    "(fixtures captured from the reference itself); target 1e-4.  teacher_forced: the reference's own (h, c, previous depth, "
+                    "previous pose) installed before every step -- 3 golden frames + the 14-keyframe long run, full resolution; free_running: "
+                    "the engine's own state over the 3 golden frames, with the number of pixels of the discrete 8x10 depth estimate that "
+                    "differ from the reference's (after a flipped pixel the runs see different inputs).  The fixture host's fp32 pose "
+                    "matrices are replayed (tests/golden/host_pose_algebra.npz); the kernels alone are pinned by tests/test_hybrid_parity.py",
+            "target": 1e-4,
+            "teacher_forced": [round(r["rel_l1"], 9) for r in rel["teacher_forced"]],
+            "teacher_forced_max": max(r["rel_l1"] for r in rel["teacher_forced"]),
+            "teacher_forced_frames": len(rel["teacher_forced"]),
+            "teacher_forced_flipped_estimate_pixels": [r["flipped_estimate_pixels"] for r in rel["teacher_forced"]],
+            "teacher_forced_steps": [f"{r['run']} step {r['step']}" for r in rel["teacher_forced"]],
+            "free_running": [r["engine_vs_reference"] for r in rel["free_running"]],
+            "free_running_flipped_estimate_pixels": [r["flipped_estimate_pixels"] for r in rel["free_running"]],
+            "engine_vs_float64": [r["engine_vs_float64"] for r in rel["free_running"]],
+            "reference_vs_float64": [r["reference_vs_float64"] for r in rel["free_running"]],
+            "host_algebra_misses": rel["host_algebra_misses"]},
+    }
+    if world == 1 and args.sequences_per_gpu > 1:
+        try:
+            S = args.sequences_per_gpu
+            fps_b, ms_b, kernel_b, bytes_b = batched_throughput(modules, device, args, S, M)
+            extra["value_batched"] = fps_b
+            extra["batched"] = {"sequences_per_gpu": S, "frames_per_s": fps_b, "ms_per_lockstep_step": ms_b, "steps": args.batched_steps,
+                                "note": "secondary: S independent sequences in lockstep on one engine (batch S); not the headline"}
+            extra["roofline"]["frac_batched"] = bytes_b / kernel_b / 1e9 / HBM_PEAK_GBPS
+            extra["roofline"]["kernel_us_batched"] = kernel_b * 1e6
+            extra["roofline_valu"]["frac_batched"] = (S * useful_flop / kernel_b / 1e12) / FP32_VALU_PEAK_TFLOPS
+        except Exception as e:   # the secondary figure must never cost the headline line
+            extra["value_batched"] = None
+            extra["batched"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and not args.no_secondary:
+        # secondary figures, each on its own engine, never at the cost of the headline line: (i) the collector left on, (ii) the causal
+        # pipeline (no look-ahead: what an online caller without the next frame gets), (iii) BASELINE.json configs[1]: pairnet inference
+        # (M = 1, no ConvLSTM; the reference's dvmvs/pairnet/run-testing.py:136-166)
+        steps2, warm2 = min(args.steps, 60), max(args.warmup, 5)
+        level = 0 if args.no_feature_cache else args.lookahead
+        for key, fn in (("value_gc_on", lambda: secondary_leg(modules, device, args, M, level, steps2, warm2, gc_on=True)[0]),
+                        ("value_causal", lambda: secondary_leg(modules, device, args, M, 0, steps2, warm2)[0])):
+            try:
+                extra[key] = fn()
+            except Exception as e:
+                extra[key] = None
+                extra[key + "_error"] = f"{type(e).__name__}: {e}"
+        # The headline depends on a property of the runtime that is observed, not documented (DESIGN.md section 5: the hardware queue
+        # hipGraphInstantiate hands a frame graph's second branch; the engine steers it with never-launched filler graphs).  The same
+        # measurement with and without them, back to back on this box: a runtime that behaves differently shows up here.
+        try:
+            import dvmvs.engine as engine_module
+            fps_on = secondary_leg(modules, device, args, M, level, steps2, warm2, queue_fillers=engine_module._GRAPH_QUEUE_FILLERS)[0]
+            fps_off = secondary_leg(modules, device, args, M, level, steps2, warm2, queue_fillers=0)[0]
+            extra["graph_queue_fillers"] = {"configured": engine_module._GRAPH_QUEUE_FILLERS, "ms_per_step_on": 1e3 / fps_on, "ms_per_step_off": 1e3 / fps_off,
+                                            "steps": steps2, "note": "secondary engines, same box, back to back; on = as the headline"}
+        except Exception as e:
+            extra["graph_queue_fillers"] = {"error": f"{type(e).__name__}: {e}"}
+        try:      # the drop-in route north_star names (INTEGRATION.md section A), timed: no engine, no graphs, poses on the device
+            surface = module_surface_leg(build_modules(), device, args, M, steps2, warm2)
+            extra["module_surface"] = surface
+            extra["value_module_surface"] = surface["value"]
+            fast = module_surface_leg(build_modules(), device, args, M, steps2, warm2, accelerated=True)
+            extra["module_surface_accelerated"] = fast
+            extra["value_module_surface_accelerated"] = fast["value"]
+            graphed = module_surface_leg(build_modules(), device, args, M, steps2, max(warm2, 6), accelerated=True, graphs=True)
+            extra["module_surface_accelerated_graphs"] = graphed
+            extra["value_module_surface_accelerated_graphs"] = graphed["value"]
+        except Exception as e:
+            extra["module_surface"] = {"error": f"{type(e).__name__}: {e}"}
+            extra["value_module_surface"] = None
+        try:
+            import synthetic as syn
+            from dvmvs.pairnet.model import CostVolumeDecoder, CostVolumeEncoder, FeatureExtractor, FeatureShrinker
+            pair_modules = syn.build_e2e_modules((FeatureExtractor, FeatureShrinker, CostVolumeEncoder, CostVolumeDecoder))
+            pair_modules.insert(3, None)
+            fps_p, pair_engine = secondary_leg(pair_modules, device, args, 1, level, steps2, warm2)
+            extra["pairnet"] = {"value": fps_p, "unit": "frames/s", "ms_per_step": 1e3 / fps_p, "steps": steps2, "warmup": warm2,
+                                "config": {"workload": "pairnet inference, one synthetic-image sequence on the sample scene's keyframe poses, 320x256, "
+                                                       "64 planes, M=1 measurement frame, batch 1 (BASELINE.json configs[1])",
+                                           "lookahead": level, "hip_graphs": not args.no_graphs, "feature_cache": not args.no_feature_cache}}
+        except Exception as e:
+            extra["pairnet"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and not args.no_cpu_baseline:
+        cpu_mods = build_modules()
+        extra["cpu_baseline"] = cpu_baseline(args, cpu_mods, M)
+    else:
+        extra["cpu_baseline"] = None
+    return extra
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        relaunch_under_torchrun(args.gpus)      # (does not return)
+        relaunch_under_torchrun(args.gpus)      # (does not return: exits with the launcher's status)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -874,7 +1102,7 @@ def main():
     engine = DepthEngine(*modules, device=device, fold_bn=not args.no_fold_bn, cache_features=not args.no_feature_cache,
                          use_graphs=not args.no_graphs, channels_last=args.channels_last,
                          lstm_channels_last=not args.no_lstm_channels_last, max_lookahead=args.lookahead)
-    engine.graph_debug = True
+    engine.graph_debug = True      # (every run: frame graphs are captured alike with and without --full, whose launch count reads their dumps)
     M = args.measurement_frames
     n_images = 32
     total = args.warmup + args.steps
@@ -884,6 +1112,7 @@ def main():
     # matrices (dvmvs.pose_algebra, "reference" mode) before its single per-frame upload
 
     host_seconds = [0.0, 0]      # time the host spends inside engine.step (pose algebra, sweep plan, upload, graph launch), and calls
+    last_depth = [None]          # what the latest step returned (a static buffer of the engine: --dump-outputs copies it after the timed steps)
 
     step_events = []             # one device event after every timed step: per-step device times (diagnostic, short runs)
 
@@ -898,7 +1127,8 @@ def main():
             engine.step_clock = []
         t_host = time.perf_counter()
         try:
-            return run_frame_inner(k)
+            last_depth[0] = run_frame_inner(k)
+            return last_depth[0]
         finally:
             t_end = time.perf_counter()
             host_seconds[0] += t_end - t_host
@@ -936,7 +1166,9 @@ def main():
             # 5 % slower than the last)
             gc_quiet()
         elapsed = timed_region(lambda i: run_frame(M + i), args.warmup, args.steps, world, device, before=region_start, after=region_end)
-        host_ms = 1e3 * host_seconds[0] / max(host_seconds[1], 1)
+        if args.dump_outputs and rank == 0:      # the last timed keyframe's full-resolution depth [1, 256, 320], as engine.step returned it
+            dump_outputs(args.dump_outputs, {"depth": last_depth[0]})
+        host_ms =1e3 * host_seconds[0] / max(host_seconds[1], 1)
         host_wait_ms = 1e3 * engine.ring_wait_seconds / max(host_seconds[1], 1)
         if step_trace_path:
             timed = step_trace[-args.steps:]
@@ -952,81 +1184,6 @@ def main():
 
     result = None
     if rank == 0:
-        picks, whole_index, all_pairs, mfma_variant = [], None, None, None
-        if args.no_roofline_leg:
-            kernel_s, alg_bytes, per_geometry, variants = float("nan"), (1 + M) * 32 * 128 * 160 * 4 + 64 * 128 * 160 * 4, [], []
-        else:
-            # the geometries of the TIMED steps (what a rocprofv3 kernel trace of this command's timed region averages over) ...
-            timed = [seq[M + args.warmup + i] for i in range(args.steps)]
-            kernel_s, alg_bytes, per_geometry, variants = measure_cost_volume_kernel(engine, M, args.kernel_reps, timed)
-            # ... and, secondary, 25 lines spread over the WHOLE keyframe index (the timed steps of a short run are its first lines)
-            picks, pose_sets = index_pose_sets(M, ROOFLINE_GEOMETRIES)
-            w_s, _, w_per, w_var = measure_cost_volume_kernel(engine, M, args.kernel_reps, pose_sets)
-            whole_index = {"kernel_us": w_s * 1e6, "frac": alg_bytes / w_s / 1e9 / HBM_PEAK_GBPS, "index_lines": picks,
-                           "kernel_us_per_geometry": [round(t * 1e6, 2) for t in w_per], "sweep_variant_per_geometry": w_var,
-                           "worst_us": max(w_per) * 1e6}
-            # ... and EVERY keyframe pair of the index (285 lines; fewer repetitions per pair): the figure that does not flatter
-            all_lines, all_sets = index_pose_sets(M, 10 ** 6)
-            reps_all = args.kernel_reps      # (round 6: as many back-to-back ops per graph as on the timed lines -- with 3 per graph the gap between two graph
-                                             # replays, ~5 - 10 us on the device, was 1.5 - 2 us of every op's figure)
-            a_s, _, a_per, a_var = measure_cost_volume_kernel(engine, M, reps_all, all_sets, rounds=2)
-            all_pairs = {"pairs": len(a_per), "kernel_us": a_s * 1e6, "frac": alg_bytes / a_s / 1e9 / HBM_PEAK_GBPS, "worst_us": max(a_per) * 1e6,
-                         "worst_index_line": all_lines[int(np.argmax(a_per))], "p90_us": float(np.percentile(a_per, 90)) * 1e6,
-                         "sweep_variants": {str(v): a_var.count(v) for v in sorted(set(a_var))}}
-            # Comparison legs, same harness, same geometries: (i) the LDS-tiled sweep as dvmvs_sweep_plan plans it (what the engine ran before round 6
-            # on the pairs it did not give to variant 6), (ii) variant 7 = the MFMA sweep as one work item per workgroup (round 5's launch shape; the
-            # same arithmetic, bit-identical volumes): what the persistent form buys
-            t_s, _, t_per, t_var = measure_cost_volume_kernel(engine, M, args.kernel_reps, timed, tiled_plan=True)
-            ta_s, _, ta_per, _ = measure_cost_volume_kernel(engine, M, reps_all, all_sets, rounds=2, tiled_plan=True)
-            g_s, _, g_per, _ = measure_cost_volume_kernel(engine, M, args.kernel_reps, timed, force_variant=7)
-            ga_s, _, ga_per, _ = measure_cost_volume_kernel(engine, M, reps_all, all_sets, force_variant=7, rounds=2)
-            mfma_variant = {"tiled_plan": {"kernel": "sweep_tiled_kernel [+ sweep_spill_kernel] as dvmvs_sweep_plan plans it", "kernel_us_timed_steps": t_s * 1e6,
-                                           "kernel_us_all_pairs": ta_s * 1e6, "worst_us_all_pairs": max(ta_per) * 1e6, "p90_us_all_pairs": float(np.percentile(ta_per, 90)) * 1e6,
-                                           "pairs_where_faster_than_engine_choice": int(sum(1 for x, y in zip(ta_per, a_per) if x < y)),
-                                           "variants_timed_steps": {str(v): t_var.count(v) for v in sorted(set(t_var))}},
-                            "one_item_per_workgroup": {"kernel": "sweep_mfma_kernel (variant 7)", "kernel_us_timed_steps": g_s * 1e6, "kernel_us_all_pairs": ga_s * 1e6,
-                                                       "worst_us_all_pairs": max(ga_per) * 1e6, "p90_us_all_pairs": float(np.percentile(ga_per, 90)) * 1e6,
-                                                       "pairs_where_faster_than_engine_choice": int(sum(1 for x, y in zip(ga_per, a_per) if x < y))}}
-        achieved = alg_bytes / kernel_s / 1e9
-        # HBM bytes per op from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes: only when the committed measurement was taken on
-        # exactly the kernel sources that are being benchmarked, otherwise null (profiles/README.md says how to re-collect)
-        traffic, traffic_source = None, None
-        try:
-            import glob
-            import hashlib
-            digest = hashlib.sha256(b"".join(open(os.path.join(ROOT, "deep-video-mvs_amd", "csrc", f), "rb").read()
-                                             for f in ("sweep_tiled.hip", "sweep_mfma.hip", "cost_volume.hip", "plane_sweep.h", "sweep_sample.h"))).hexdigest()
-            for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_cost_volume_pmc.json")), reverse=True):
-                pmc = json.load(open(path))
-                if pmc.get("shape") == [1, M, 32, 128, 160, 64] and pmc.get("kernel_sources_sha256") == digest:
-                    traffic, traffic_source = pmc["hbm_bytes_per_launch"], os.path.relpath(path, ROOT)
-                    break
-        except (OSError, ValueError, KeyError):
-            pass
-        # useful arithmetic of the op: per (pixel, plane, frame) 4 taps x C channels of FMA + 4 weight FMAs, 2 flop each
-        useful_flop = 128 * 160 * 64 * M * (4 * 32 + 4) * 2
-        valu_tflops = useful_flop / kernel_s / 1e12
-        lds_bytes = 128 * 160 * 64 * M * 4 * 32 * 4
-        # (the LDS accounting below is the TILED formulation's -- the MFMA sweep reads 4 dot products per sample, not 4 x 32 channels: the steps that ran it are left out)
-        tiled_times = [t for t, v in zip(per_geometry, variants) if v not in (6, 7)]
-        tiled_s = sum(tiled_times) / len(tiled_times) if tiled_times else float("nan")
-        other_kernels = None if args.no_roofline_leg else measure_small_kernels(engine)
-        launches_per_frame = {}
-        try:     # kernel nodes of the captured frame graph (what one replay launches), where the runtime can dump a graph
-            counts = {f"n_meas={k[0]},has_previous={k[1]},sweep_variant={k[2]}": count_graph_kernels(g) for k, g in engine._graphs.items()}
-            launches_per_frame.update({k: v for k, v in counts.items() if v is not None})
-        except Exception:
-            pass
-        try:     # ... and the count a rocprofv3 kernel trace of THIS command's timed region recorded at the benchmarked look-ahead level
-            import glob      # (profiles/, per round: the newest round that has one)
-            level = 0 if args.no_feature_cache else args.lookahead
-            region = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]_bench_timed_region_lookahead{level}.csv")))[-1]
-            last = open(region).read().strip().splitlines()[-1].split(",")
-            launches_per_frame.update(profiled=float(last[5]) / float(last[7]), profiled_source=os.path.relpath(region, ROOT), profiled_lookahead=level)
-        except Exception:
-            pass
-        launches_per_frame = launches_per_frame or None
-        rel = golden_rel_l1(modules, device, args) if not args.no_rel_l1 else None
         result = {
             "metric": "depth frames/sec/GPU @ 320x256x64 planes (fusionnet); rel-L1 vs ref",
             "value": world * args.steps / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1050,131 +1207,12 @@ def main():
                        "weights": "seeded (tests/synthetic.py) + published FPN checkpoint",
                        "cyclic_gc": "left on" if args.keep_gc else "off for warm-up + timed steps as in timeit (collect + freeze before); value_gc_on = collector left on",
                        "parallelism": f"sequence-sharded x{world}, no data-path collective"},
-            "roofline": {"kernel": "sweep_mfma_persistent_kernel (variant 6: every pair since round 6, dvmvs_sweep_plan6); 1 launch = all planes x M frames",
-                         "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "sample": "frac/achieved/kernel_us: mean over the timed steps' keyframe pairs; all_pairs: all 285 index lines; whole_index: 25 spread",
-                         "all_pairs": all_pairs,
-                         "traffic": traffic, "traffic_source": traffic_source, "kernel_us": kernel_s * 1e6, "algorithmic_bytes": alg_bytes,
-                         # the channels-last copy of a keyframe's features that variant 6 reads: round 5 a launch per frame outside this accounting
-                         # (5 - 16 us in the frame), since round 6 written by the FPN smoothing layer's own epilogue (dvmvs_direct_conv_dual_fwd)
-                         "kernel_us_incl_layout": kernel_s * 1e6 + 0.0, "layout_launches_per_frame": 0 if getattr(engine, "sweep_mfma", False) and engine.direct_convs else 1,
-                         "geometries": f"{len(per_geometry)} timed steps = index lines {(M + args.warmup + 37 * rank) % 286}.. (nmeas+2 index), each as the engine launches it",
-                         "kernel_us_per_geometry": [round(t * 1e6, 2) for t in per_geometry],
-                         "sweep_variant_per_geometry": variants,
-                         "sweep_variants": {"2 (default: 3 x 48 KB boxes, 256 threads; two passes)": variants.count(2),
-                                            "3 (wide-baseline: 2 x 72 KB boxes, 512 threads; two passes)": variants.count(3),
-                                            "4 (default, single pass: the host's plan queues nothing)": variants.count(4),
-                                            "5 (wide-baseline, single pass)": variants.count(5),
-                                            "6 (correlate-then-interpolate on the fp32 matrix cores, persistent form; channels-last maps)": variants.count(6)},
-                         "engine_frames_per_sweep_variant": {str(k): v for k, v in sorted(engine.sweep_variant_counts.items())},
-                         "whole_index": whole_index},
-            # HBM is not what binds this op (13 MB of algorithmic traffic against 0.69 GFLOP of tap arithmetic and 1.3 GB of LDS
-            # reads): the same duration against the fp32 vector peak, counting only the useful tap FMAs
-            "roofline_valu": {"bound": "valu_fp32", "achieved": valu_tflops, "peak": FP32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                              "frac": valu_tflops / FP32_VALU_PEAK_TFLOPS, "useful_flop": useful_flop},
-            # the pipe this formulation is actually bound by: 4 taps x 32 channels x 4 B from LDS per (pixel, plane, frame).  "peak" is
-            # the ds_read_b128 rate of the chip; "pattern_floor_us" the measured floor of the kernel's own inner pattern (bank conflicts
-            # of the tap addresses and the packed FMAs between the reads included)
-            "roofline_lds": None if not tiled_times else {
-                "bound": "lds", "kernel": f"sweep_tiled_kernel ({len(tiled_times)} of the {len(per_geometry)} timed steps ran it)", "achieved": lds_bytes / tiled_s / 1e12,
-                "peak": LDS_PEAK_TBPS, "unit": "TB/s", "frac": lds_bytes / tiled_s / 1e12 / LDS_PEAK_TBPS, "lds_bytes": lds_bytes, "kernel_us": tiled_s * 1e6,
-                "pattern_floor_us": SWEEP_LDS_PATTERN_FLOOR_US, "frac_of_pattern_floor": SWEEP_LDS_PATTERN_FLOOR_US / (tiled_s * 1e6)},
-            # what the launch's duration is made of (round 5): instruction ISSUE.  Summed over a SIMD's waves, the cycles with an instruction
-            # issuing / executing (SQ_ACTIVE_INST_ANY of the committed PMC profile, index line 0) add up to the waves' lifetime in both sweep
-            # kernels: neither HBM nor LDS bandwidth nor the matrix pipe but the instruction count bounds them
-            "roofline_issue": issue_roofline(per_geometry, variants) if per_geometry else None,
-            "roofline_comparison_kernels": mfma_variant,
-            "roofline_other": other_kernels,
             # what the engine's warm-up costs (outside the timed steps): eager first frames, graph capture, first launches of the graphs
             # captured ahead; device memory reserved beyond live tensors (the captured graphs' private pools are part of it)
             "warmup_report": engine.graph_memory_report(),      # ("warmup" is the contract's integer above)
-            "launches_per_frame": launches_per_frame,
-            "rel_l1": None if rel is None else {
-                "what": "depth rel-L1 mean(|d - d_ref| / d_ref) of this engine configuration (graph replay included) vs the REFERENCE forward "
-                        "(fixtures captured from the reference itself); target 1e-4.  teacher_forced: the reference's own (h, c, previous depth, "
-                        "previous pose) installed before every step -- 3 golden frames + the 14-keyframe long run, full resolution; free_running: "
-                        "the engine's own state over the 3 golden frames, with the number of pixels of the discrete 8x10 depth estimate that "
-                        "differ from the reference's (after a flipped pixel the runs see different inputs).  The fixture host's fp32 pose "
-                        "matrices are replayed (tests/golden/host_pose_algebra.npz); the kernels alone are pinned by tests/test_hybrid_parity.py",
-                "target": 1e-4,
-                "teacher_forced": [round(r["rel_l1"], 9) for r in rel["teacher_forced"]],
-                "teacher_forced_max": max(r["rel_l1"] for r in rel["teacher_forced"]),
-                "teacher_forced_frames": len(rel["teacher_forced"]),
-                "teacher_forced_flipped_estimate_pixels": [r["flipped_estimate_pixels"] for r in rel["teacher_forced"]],
-                "teacher_forced_steps": [f"{r['run']} step {r['step']}" for r in rel["teacher_forced"]],
-                "free_running": [r["engine_vs_reference"] for r in rel["free_running"]],
-                "free_running_flipped_estimate_pixels": [r["flipped_estimate_pixels"] for r in rel["free_running"]],
-                "engine_vs_float64": [r["engine_vs_float64"] for r in rel["free_running"]],
-                "reference_vs_float64": [r["reference_vs_float64"] for r in rel["free_running"]],
-                "host_algebra_misses": rel["host_algebra_misses"]},
         }
-        if world == 1 and args.sequences_per_gpu > 1:
-            try:
-                S = args.sequences_per_gpu
-                fps_b, ms_b, kernel_b, bytes_b = batched_throughput(modules, device, args, S, M)
-                result["value_batched"] = fps_b
-                result["batched"] = {"sequences_per_gpu": S, "frames_per_s": fps_b, "ms_per_lockstep_step": ms_b, "steps": args.batched_steps,
-                                     "note": "secondary: S independent sequences in lockstep on one engine (batch S); not the headline"}
-                result["roofline"]["frac_batched"] = bytes_b / kernel_b / 1e9 / HBM_PEAK_GBPS
-                result["roofline"]["kernel_us_batched"] = kernel_b * 1e6
-                result["roofline_valu"]["frac_batched"] = (S * useful_flop / kernel_b / 1e12) / FP32_VALU_PEAK_TFLOPS
-            except Exception as e:   # the secondary figure must never cost the headline line
-                result["value_batched"] = None
-                result["batched"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_secondary:
-            # secondary figures, each on its own engine, never at the cost of the headline line: (i) the collector left on, (ii) the causal
-            # pipeline (no look-ahead: what an online caller without the next frame gets), (iii) BASELINE.json configs[1]: pairnet inference
-            # (M = 1, no ConvLSTM; /root/reference/dvmvs/pairnet/run-testing.py:136-166)
-            steps2, warm2 = min(args.steps, 60), max(args.warmup, 5)
-            level = 0 if args.no_feature_cache else args.lookahead
-            for key, fn in (("value_gc_on", lambda: secondary_leg(modules, device, args, M, level, steps2, warm2, gc_on=True)[0]),
-                            ("value_causal", lambda: secondary_leg(modules, device, args, M, 0, steps2, warm2)[0])):
-                try:
-                    result[key] = fn()
-                except Exception as e:
-                    result[key] = None
-                    result[key + "_error"] = f"{type(e).__name__}: {e}"
-            # The headline depends on a property of the runtime that is observed, not documented (the hardware queue
-            # hipGraphInstantiate hands a frame graph's second branch; the engine steers it with never-launched filler graphs).  The same
-            # measurement with and without them, back to back on this box: a runtime that behaves differently shows up here.
-            try:
-                import dvmvs.engine as engine_module
-                fps_on = secondary_leg(modules, device, args, M, level, steps2, warm2, queue_fillers=engine_module._GRAPH_QUEUE_FILLERS)[0]
-                fps_off = secondary_leg(modules, device, args, M, level, steps2, warm2, queue_fillers=0)[0]
-                result["graph_queue_fillers"] = {"configured": engine_module._GRAPH_QUEUE_FILLERS, "ms_per_step_on": 1e3 / fps_on, "ms_per_step_off": 1e3 / fps_off,
-                                                 "steps": steps2, "note": "secondary engines, same box, back to back; on = as the headline"}
-            except Exception as e:
-                result["graph_queue_fillers"] = {"error": f"{type(e).__name__}: {e}"}
-            try:      # the drop-in route north_star names, timed: no engine, no graphs, poses on the device
-                surface = module_surface_leg(build_modules(), device, args, M, steps2, warm2)
-                result["module_surface"] = surface
-                result["value_module_surface"] = surface["value"]
-                fast = module_surface_leg(build_modules(), device, args, M, steps2, warm2, accelerated=True)
-                result["module_surface_accelerated"] = fast
-                result["value_module_surface_accelerated"] = fast["value"]
-                graphed = module_surface_leg(build_modules(), device, args, M, steps2, max(warm2, 6), accelerated=True, graphs=True)
-                result["module_surface_accelerated_graphs"] = graphed
-                result["value_module_surface_accelerated_graphs"] = graphed["value"]
-            except Exception as e:
-                result["module_surface"] = {"error": f"{type(e).__name__}: {e}"}
-                result["value_module_surface"] = None
-            try:
-                import synthetic as syn
-                from dvmvs.pairnet.model import CostVolumeDecoder, CostVolumeEncoder, FeatureExtractor, FeatureShrinker
-                pair_modules = syn.build_e2e_modules((FeatureExtractor, FeatureShrinker, CostVolumeEncoder, CostVolumeDecoder))
-                pair_modules.insert(3, None)
-                fps_p, pair_engine = secondary_leg(pair_modules, device, args, 1, level, steps2, warm2)
-                result["pairnet"] = {"value": fps_p, "unit": "frames/s", "ms_per_step": 1e3 / fps_p, "steps": steps2, "warmup": warm2,
-                                     "config": {"workload": "pairnet inference, one synthetic-image sequence on the sample scene's keyframe poses, 320x256, "
-                                                            "64 planes, M=1 measurement frame, batch 1 (BASELINE.json configs[1])",
-                                                "lookahead": level, "hip_graphs": not args.no_graphs, "feature_cache": not args.no_feature_cache}}
-            except Exception as e:
-                result["pairnet"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
-            cpu_mods = build_modules()
-            result["cpu_baseline"] = cpu_baseline(args, cpu_mods, M)
-        else:
-            result["cpu_baseline"] = None
+        if args.full:
+            result.update(full_legs(args, engine, modules, device, seq, M, rank, world))
         if args.stage_times:
             print(f"[bench] final depth mean {depth_mean:.4f}", file=sys.stderr)
         print(json.dumps(finite_or_null(result)))

@@ -16,10 +16,12 @@ import time
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-STEPS, LAUNCH_STUB_SECONDS = 150, 0.0004
+STEPS, LAUNCH_STUB_SECONDS, REPEATS = 600, 0.0004, 3
 
 
-def _host_loop(rank, queue, barrier):
+def _host_loop(rank, queue, barrier, core):
+    if core is not None:
+        os.sched_setaffinity(0, {core})      # a core of its own, as "a machine with at least eight usable cores" gives every rank
     sys.path[:0] = [os.path.join(HERE, "..", "deep-video-mvs_amd"), HERE]
     import torch
     torch.set_num_threads(1)
@@ -56,7 +58,11 @@ def _host_loop(rank, queue, barrier):
 def _run(n):
     ctx = mp.get_context("spawn")
     queue, barrier = ctx.Queue(), ctx.Barrier(n)
-    procs = [ctx.Process(target=_host_loop, args=(rank, queue, barrier)) for rank in range(n)]
+    # one rank per usable core where there are enough of them (the scheduler otherwise stacks two ranks on one core now and then, and the
+    # test measures where they were put, not the host path)
+    cores = sorted(os.sched_getaffinity(0)) if hasattr(os, "sched_setaffinity") else []
+    pin = [cores[rank] for rank in range(n)] if len(cores) >= n else [None] * n
+    procs = [ctx.Process(target=_host_loop, args=(rank, queue, barrier, pin[rank])) for rank in range(n)]
     for p in procs:
         p.start()
     results = [queue.get(timeout=300) for _ in range(n)]
@@ -66,12 +72,18 @@ def _run(n):
 
 
 def test_eight_host_loops_cost_per_rank_what_one_costs():
-    one = _run(1)
-    eight = _run(8)
+    # REPEATS interleaved rounds of one rank alone and eight at once, so that a slow or a quiet spell of a shared machine falls on both sides;
+    # of each, the median round counts (one round of either alone varies by a third from run to run on a virtual machine)
+    rounds_1, rounds_8 = [], []
+    for _ in range(REPEATS):
+        rounds_1.append(_run(1))
+        rounds_8.append(_run(8))
+    one = sorted(rounds_1, key=lambda r: r[0][2])[REPEATS // 2]
+    eight = sorted(rounds_8, key=lambda r: max(x[2] for x in r))[REPEATS // 2]
     step_1, busy_1 = one[0][1], one[0][2]
     step_8, busy_8 = max(r[1] for r in eight), max(r[2] for r in eight)
     cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
-    report = {"host_cores_visible": cores, "steps": STEPS, "launch_stub_ms": LAUNCH_STUB_SECONDS * 1e3,
+    report = {"host_cores_visible": cores, "steps": STEPS, "rounds": REPEATS, "launch_stub_ms": LAUNCH_STUB_SECONDS * 1e3,
               "one_rank": {"ms_per_step": round(step_1, 4), "host_work_ms_per_step": round(busy_1, 4)},
               "eight_ranks_worst": {"ms_per_step": round(step_8, 4), "host_work_ms_per_step": round(busy_8, 4)},
               "eight_ranks_all": [round(r[2], 4) for r in eight]}

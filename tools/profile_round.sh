@@ -18,7 +18,7 @@ root="$(pwd)"
 for la in 1 0; do
   tag="lookahead$la"
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d "$root/$out/bench_trace_$tag" --output-format csv -- \
-     python "$root/bench.py" --steps $steps --warmup $warmup --lookahead $la --mark-region --no-cpu-baseline --no-rel-l1 --sequences-per-gpu 0 \
+     python "$root/bench.py" --steps $steps --warmup $warmup --lookahead $la --mark-region --full --no-cpu-baseline --no-rel-l1 --sequences-per-gpu 0 \
      > "$root/$out/bench_under_rocprof_$tag.json" 2> "$root/$out/bench_under_rocprof_$tag.err")
   trace=$(ls "$out"/bench_trace_$tag/*/*kernel_trace.csv 2>/dev/null | head -1)
   stats=$(ls "$out"/bench_trace_$tag/*/*kernel_stats.csv 2>/dev/null | head -1)
