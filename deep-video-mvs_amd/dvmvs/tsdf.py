@@ -4,9 +4,20 @@ reference's reconstruction script, /root/reference/sample-data/run-tsdf-reconstr
 ``TSDFVolume.integrate`` is the hot function: one HIP launch (``dvmvs_tsdf_integrate``) updates the whole voxel volume in
 place in HBM; the volumes never leave the device until ``get_volume()``.  The reference compiles an equivalent CUDA kernel
 with pycuda and launches it once per "gpu loop"; its numba CPU fall-back has no counterpart here (GPU only, like the rest of
-the package).  Marching cubes (``get_mesh`` / ``get_point_cloud``) come from scikit-image in the reference and are out of
-scope: use ``get_volume()`` with any iso-surface extractor.
+the package).
+
+``get_mesh`` / ``get_point_cloud`` extract the zero iso-surface on the device with ``marching_cubes`` (csrc/marching_cubes.hip,
+four launches), where the reference calls scikit-image's ``marching_cubes_lewiner`` on the host.  Vertices are the same (one on
+every grid edge whose sign changes, linearly interpolated); in cubes with an ambiguous face or interior the Lewiner (MC33) cases
+of scikit-image may triangulate differently, so face counts can differ slightly from the reference's; normals are the
+interpolated ``np.gradient`` of the volume.  ``TSDFFusion`` carries the script's helpers (``meshwrite`` / ``pcwrite`` write the
+same bytes, ``integrate``, ``calculate_volume_bounds``) and ``run`` is its main program: ``python -m dvmvs.tsdf --help``.
 """
+import glob
+import os
+import time
+from argparse import ArgumentParser
+
 import numpy as np
 import torch
 
@@ -17,6 +28,59 @@ def fold_color(color_im):
     """[H,W,3] RGB (0..255) -> float32 [H,W] holding b * 65536 + g * 256 + r (run-tsdf-reconstruction.py:236-238)."""
     c = np.asarray(color_im, dtype=np.float32)
     return np.floor(c[..., 2] * np.float32(65536.0) + c[..., 1] * np.float32(256.0) + c[..., 0]).astype(np.float32)
+
+
+def marching_cubes(volume, level=0.0, color=None, origin=(0.0, 0.0, 0.0), voxel_size=1.0):
+    """Iso-surface ``value == level`` of a device float32 volume [X,Y,Z] (z fastest) as device tensors
+    ``(verts [V,3] float32, faces [F,3] int32, normals [V,3] float32, colors [V,3] uint8 or None)``.
+
+    A corner is inside when ``value < level``; each grid edge with exactly one inside endpoint carries one vertex, shared by the
+    faces around it.  Vertices are ordered by (linear index of the voxel that owns the edge, axis x < y < z), faces by cube, so
+    two calls give the same bytes.  ``verts = index-space position * voxel_size + origin``; ``normals`` are the interpolated
+    ``np.gradient`` of the volume, unit length (zero where it vanishes), pointing toward increasing values; faces are
+    counter-clockwise seen from that side.  ``color`` (the folded ``b * 65536 + g * 256 + r`` volume) is read at the rounded
+    vertex position and decoded to RGB.  A volume thinner than 2 voxels on an axis, or without a crossing, gives V = F = 0.
+
+    Makes ONE host read (a synchronisation): the vertex and face counts, to size the outputs.  The case table is not the
+    Lewiner (MC33) one of scikit-image: in cubes with ambiguous faces its triangles can differ from the reference's."""
+    if not torch.is_tensor(volume) or volume.device.type != "cuda":
+        raise TypeError("marching_cubes takes a device tensor (the HIP kernel has no CPU path)")
+    if volume.dim() != 3 or volume.dtype != torch.float32:
+        raise ValueError(f"volume must be float32 [X,Y,Z], got {volume.dtype} {tuple(volume.shape)}")
+    dev = volume.device
+    vol = volume.contiguous()
+    col = None
+    if color is not None:
+        if not torch.is_tensor(color) or color.shape != volume.shape or color.dtype != torch.float32 or color.device != dev:
+            raise ValueError("color must be a float32 device tensor of the volume's shape")
+        col = color.contiguous()
+    X, Y, Z = (int(d) for d in vol.shape)
+
+    def empty(v, f):
+        return (torch.empty((v, 3), dtype=torch.float32, device=dev), torch.empty((f, 3), dtype=torch.int32, device=dev),
+                torch.empty((v, 3), dtype=torch.float32, device=dev), None if col is None else torch.empty((v, 3), dtype=torch.uint8, device=dev))
+
+    if vol.numel() == 0:
+        return empty(0, 0)
+    lib = _capi.lib()
+    nbytes = lib.dvmvs_marching_cubes_workspace_bytes(X, Y, Z)
+    if nbytes == 0:
+        raise RuntimeError(f"marching_cubes: volume {X}x{Y}x{Z} is too large for the kernel (2^31 voxels at most)")
+    origin = [float(o) for o in np.asarray(origin, dtype=np.float32).reshape(3)]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _capi.check(lib.dvmvs_marching_cubes_count(vol.data_ptr(), X, Y, Z, float(level), workspace.data_ptr(), nbytes,
+                                                   counts.data_ptr(), stream), "dvmvs_marching_cubes_count")
+        V, F = (int(c) for c in counts.cpu())                      # the one host read
+        verts, faces, normals, colors = empty(V, F)
+        if V or F:
+            _capi.check(lib.dvmvs_marching_cubes_emit(
+                vol.data_ptr(), None if col is None else col.data_ptr(), X, Y, Z, float(level), origin[0], origin[1], origin[2],
+                float(np.float32(voxel_size)), workspace.data_ptr(), verts.data_ptr(), normals.data_ptr(),
+                None if colors is None else colors.data_ptr(), faces.data_ptr(), V, F, stream), "dvmvs_marching_cubes_emit")
+    return verts, faces, normals, colors
 
 
 class TSDFVolume:
@@ -81,9 +145,15 @@ class TSDFVolume:
         return self._weight.cpu().numpy()
 
     def get_mesh(self):
-        raise NotImplementedError("marching cubes (scikit-image in the reference) is out of scope: extract the iso-surface from get_volume()")
+        """(verts [V,3] float32 in world units, faces [F,3] int32, normals [V,3] float32, colours [V,3] uint8 RGB) of the zero
+        iso-surface, as numpy arrays (run-tsdf-reconstruction.py:334-351); extracted on the device by ``marching_cubes``."""
+        verts, faces, norms, colors = marching_cubes(self._tsdf, 0.0, self._color, self._vol_origin, self._voxel_size)
+        return verts.cpu().numpy(), faces.cpu().numpy(), norms.cpu().numpy(), colors.cpu().numpy()
 
-    get_point_cloud = get_mesh
+    def get_point_cloud(self):
+        """[N,6] float32: the mesh's vertices (xyz, world units) followed by their colour (rgb) (run-tsdf-reconstruction.py:313-332)."""
+        verts, _, _, colors = self.get_mesh()
+        return np.hstack([verts, colors])
 
 
 class TSDFFusion:
@@ -115,3 +185,171 @@ class TSDFFusion:
             bounds[:, 0] = np.minimum(bounds[:, 0], np.amin(frustum, axis=1))
             bounds[:, 1] = np.maximum(bounds[:, 1], np.amax(frustum, axis=1))
         return bounds
+
+    @staticmethod
+    def calculate_volume_bounds(depth_maps, poses, K):
+        """Bounds of the view frusta of ``depth_maps`` seen from ``poses`` with intrinsics ``K``, the reconstruction script's way:
+        the running min / max start at ZERO, so the world origin is always inside (``volume_bounds`` starts at +-inf)."""
+        assert len(depth_maps) == len(poses)
+        bounds = np.zeros((3, 2))
+        for depth_map, pose in zip(depth_maps, poses):
+            frustum = TSDFFusion.get_view_frustum(depth_map, K, pose)
+            bounds[:, 0] = np.minimum(bounds[:, 0], np.amin(frustum, axis=1))
+            bounds[:, 1] = np.maximum(bounds[:, 1], np.amax(frustum, axis=1))
+        return bounds
+
+    @staticmethod
+    def _columns(formats, columns):
+        """Rows of space-separated, %-formatted columns, each ending in a newline: one string, built without a Python loop
+        over the rows (np.char formats each column element with the same % operator a per-row write uses)."""
+        if len(columns[0]) == 0:
+            return ""
+        line = np.char.mod(formats[0], columns[0])
+        for fmt, col in zip(formats[1:], columns[1:]):
+            line = np.char.add(np.char.add(line, " "), np.char.mod(fmt, col))
+        return "\n".join(line.tolist()) + "\n"
+
+    @staticmethod
+    def meshwrite(filename, verts, faces, norms, colors):
+        """ASCII .ply of a coloured mesh with normals, byte for byte the reconstruction script's format (:379-415)."""
+        verts, faces, norms, colors = (np.asarray(a) for a in (verts, faces, norms, colors))
+        header = ("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\n"
+                  "property uchar blue\nelement face %d\nproperty list uchar int vertex_index\nend_header\n") % (len(verts), len(faces))
+        body = TSDFFusion._columns(["%f"] * 6 + ["%d"] * 3, [verts[:, 0], verts[:, 1], verts[:, 2], norms[:, 0], norms[:, 1], norms[:, 2],
+                                                            colors[:, 0], colors[:, 1], colors[:, 2]])
+        tris = TSDFFusion._columns(["3 %d", "%d", "%d"], [faces[:, 0], faces[:, 1], faces[:, 2]])
+        with open(filename, "w") as f:
+            f.write(header + body + tris)
+
+    @staticmethod
+    def pcwrite(filename, xyzrgb):
+        """ASCII .ply of a coloured point cloud [N,6] (xyz, rgb), byte for byte the reconstruction script's format (:417-439)."""
+        xyzrgb = np.asarray(xyzrgb)
+        xyz, rgb = xyzrgb[:, :3], xyzrgb[:, 3:].astype(np.uint8)
+        header = ("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n") % len(xyz)
+        body = TSDFFusion._columns(["%f"] * 3 + ["%d"] * 3, [xyz[:, 0], xyz[:, 1], xyz[:, 2], rgb[:, 0], rgb[:, 1], rgb[:, 2]])
+        with open(filename, "w") as f:
+            f.write(header + body)
+
+    @staticmethod
+    def integrate(tsdf_volume, images, depths, poses, K, mesh_name, save_progressive):
+        """Fuses every (image, depth, pose) with weight 1 and writes ``<mesh_name>_complete.ply`` (with ``save_progressive``,
+        also ``<mesh_name>_frame_<i>.ply`` after each frame), like the reconstruction script (:442-462)."""
+        n = len(images)
+        start = time.time()
+        for i in range(n):
+            print(f"Fusing frame {i + 1}/{n} for {mesh_name}")
+            tsdf_volume.integrate(images[i], depths[i], K, poses[i], obs_weight=1.0)
+            if save_progressive:
+                print("Saving for progressive visuals...")
+                TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *tsdf_volume.get_mesh())
+        torch.cuda.synchronize(tsdf_volume.device)
+        print("Average FPS: {:.2f}".format(n / max(time.time() - start, 1e-9)))
+        print("Saving mesh to", mesh_name)
+        TSDFFusion.meshwrite(mesh_name + "_complete.ply", *tsdf_volume.get_mesh())
+
+
+def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dataset_name, scene_name):
+    return (f"{reconstruction_folder}/reconstruction_voxelsize-{voxel_size}_maxdepth-{max_depth}_anchor-{anchor}_"
+            f"{system}_{dataset_name}_{scene_name}")
+
+
+def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, scene_name, system_name, voxel_size, max_depth,
+        use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda"):
+    """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
+    predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
+    the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
+    loaders (no OpenCV)."""
+    from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, resize_nearest
+    scene_folder = os.path.join(data_folder, dataset_name, scene_name)
+    original_K = np.loadtxt(os.path.join(scene_folder, "K.txt")).astype(np.float32)
+    all_poses = np.fromfile(os.path.join(scene_folder, "poses.txt"), dtype=float, sep="\n ").reshape((-1, 4, 4))
+    all_image_filenames = sorted(glob.glob(os.path.join(scene_folder, "images", "*.png")))
+
+    pattern = f"keyframe_{dataset_name}_{system_name}_predictions_{scene_name}*"
+    prediction_files = glob.glob(os.path.join(prediction_folder, pattern))
+    if not prediction_files:
+        raise FileNotFoundError(f"no prediction file {pattern} in {prediction_folder}")
+    predictions = np.load(prediction_files[0])["arr_0"]
+    prediction_height, prediction_width = np.shape(predictions[0])
+
+    nmeas = system_name.split("_")[2]
+    with open(os.path.join(data_folder, "indices", f"keyframe+{dataset_name}+{scene_name}+nmeas+{nmeas}")) as f:
+        keyframe_lines = [line.rstrip("\n") for line in f if line.strip()]
+    keyframe_poses, keyframe_image_filenames = [], []
+    for line in keyframe_lines:
+        if line == "TRACKING LOST":
+            continue
+        image_filename = os.path.join(scene_folder, "images", line.split(" ")[0])
+        keyframe_poses.append(all_poses[all_image_filenames.index(image_filename)])
+        keyframe_image_filenames.append(image_filename)
+
+    first = load_image(all_image_filenames[0])
+    preprocessor = PreprocessImage(K=original_K, old_width=first.shape[1], old_height=first.shape[0], new_width=prediction_width,
+                                   new_height=prediction_height, distortion_crop=0, perform_crop=False)
+    scaled_K = preprocessor.get_updated_intrinsics()
+
+    # ScanNet frames have black, undistorted-away borders: predictions there are masked
+    edge = 10
+    edge_mask = np.zeros((prediction_height, prediction_width), dtype=bool)
+    edge_mask[:edge, :] = edge_mask[-edge:, :] = True
+    edge_mask[:, :edge] = edge_mask[:, -edge:] = True
+    keyframe_images, keyframe_predictions = [], []
+    for index, image_filename in enumerate(keyframe_image_filenames):
+        image = resize_nearest(load_image(image_filename), prediction_width, prediction_height)
+        prediction = predictions[index]
+        if "scannet" in dataset_name:
+            prediction[np.logical_and(np.mean(image.astype(float), axis=-1) < 10.0, edge_mask)] = 0.0
+        prediction[prediction > max_depth] = 0.0
+        keyframe_predictions.append(prediction)
+        keyframe_images.append(image.astype(np.uint8))
+
+    groundtruths = None
+    if use_groundtruth_to_anchor or save_groundtruth:
+        groundtruths = []
+        for filename in sorted(glob.glob(os.path.join(scene_folder, "depth", "*.png"))):
+            depth = load_depth_png(filename)
+            depth[depth > max_depth] = 0.0
+            groundtruths.append(depth)
+    if use_groundtruth_to_anchor:
+        volume_bounds = TSDFFusion.calculate_volume_bounds(groundtruths, all_poses, original_K)
+    else:
+        volume_bounds = TSDFFusion.calculate_volume_bounds(keyframe_predictions, keyframe_poses, scaled_K)
+    volume_bounds *= 1.05      # margin for errors in the bounds
+
+    os.makedirs(reconstruction_folder, exist_ok=True)
+    if save_groundtruth:
+        volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
+        images = [load_image(f).astype(np.uint8) for f in all_image_filenames]
+        TSDFFusion.integrate(volume, images, groundtruths, all_poses, original_K,
+                             _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, "GROUNDTRUTH",
+                                        dataset_name, scene_name), save_progressive=False)
+        del volume
+    volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
+    TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K,
+                         _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name,
+                                    dataset_name, scene_name), save_progressive)
+
+
+def main(argv=None):
+    parser = ArgumentParser(description="TSDF reconstruction of a scene from saved keyframe depth predictions (writes .ply meshes)")
+    parser.add_argument("--reconstruction_folder", default="./reconstructions", type=str)
+    parser.add_argument("--prediction_folder", default="./predictions", type=str)
+    parser.add_argument("--data_folder", default=".", type=str)
+    parser.add_argument("--dataset_name", default="hololens-dataset", type=str)
+    parser.add_argument("--scene_name", default="000", type=str)
+    parser.add_argument("--system_name", default="320_256_3_dvmvs_fusionnet_online", type=str)
+    parser.add_argument("--voxel_size", default=0.025, type=float)
+    parser.add_argument("--max_depth", default=5.0, type=float)
+    parser.add_argument("--use_groundtruth_to_anchor", action="store_true",
+                        help="compute the volume bounds from the ground-truth depth maps (recommended when they are available)")
+    parser.add_argument("--save_progressive", action="store_true", help="also write the mesh after every fused keyframe")
+    parser.add_argument("--save_groundtruth", action="store_true", help="also write the reconstruction from the ground-truth depth maps")
+    args = parser.parse_args(argv)
+    run(**vars(args))
+
+
+if __name__ == "__main__":
+    main()

@@ -38,8 +38,9 @@ extern "C" {
  * Variant 6 of dvmvs_cost_volume_fwd runs as one persistent 16-wave workgroup per CU where the problem allows (csrc/sweep_mfma.hip): same
  * arguments, bit-identical volumes.
  * ABI 8 (round 6) = ABI 7 + the 1x1 convolution with bias, ReLU and the residual add in its store path (dvmvs_pointwise_conv_*); no earlier
- * signature changed; dvmvs_bottleneck_conv_up2x_fwd and the 32x40 stride-2 shape of dvmvs_bottleneck_conv_fwd; dvmvs_host_pointer_device_visible, dvmvs_upsample2x_pair_fwd. */
-#define DVMVS_ABI_VERSION 8
+ * signature changed; dvmvs_bottleneck_conv_up2x_fwd and the 32x40 stride-2 shape of dvmvs_bottleneck_conv_fwd; dvmvs_host_pointer_device_visible, dvmvs_upsample2x_pair_fwd.
+ * ABI 9 = ABI 8 + marching cubes on a voxel volume (dvmvs_marching_cubes_*); no earlier signature changed. */
+#define DVMVS_ABI_VERSION 9
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
 
@@ -449,6 +450,28 @@ int dvmvs_tsdf_integrate(float* tsdf_vol, float* weight_vol, float* color_vol, i
                          float origin_x, float origin_y, float origin_z, float voxel_size, const float* cam_intr,
                          const float* cam_pose, const float* color_im, const float* depth_im, int im_h, int im_w,
                          float trunc_margin, float obs_weight, dvmvs_stream_t stream);
+
+/*
+ * Marching cubes on a voxel volume: the mesh of the iso-surface value == level, with shared vertices in a fixed order.  Replaces
+ * scikit-image's marching_cubes_lewiner in the reference's get_mesh / get_point_cloud (run-tsdf-reconstruction.py:313-351).
+ *   vol [X,Y,Z] (z fastest), color_vol the same shape, folded as b * 65536 + g * 256 + r (may be NULL: no colours)
+ *   A corner is inside when value < level.  Each voxel owns its +x, +y, +z edges; vertices are numbered by (linear index of the
+ *   owner, axis x < y < z); triangles by (linear index of the cube's lowest corner, table order of csrc/marching_cubes_tables.h),
+ *   counter-clockwise seen from the side of increasing values, where the normals point.  A volume with a dimension below 2 has
+ *   V = F = 0.  Exact formulas: csrc/marching_cubes.hip.
+ * Two calls, with one host read of V and F between them to size the outputs:
+ *   dvmvs_marching_cubes_workspace_bytes   host only, no HIP call: 4 bytes per voxel + 24 per 256 voxels (0 for a bad shape)
+ *   dvmvs_marching_cubes_count             counts_dev (device int64 [2]) <- V, F; keeps per-block offsets in the workspace
+ *   dvmvs_marching_cubes_emit              with the SAME workspace, after _count: verts, normals [V,3] float32 (verts in world
+ *                                          units: index * voxel_size + origin), colors [V,3] uint8 RGB (only when color_vol is
+ *                                          given), faces [F,3] int32.  V and F as read from counts_dev; each below 2^31.
+ */
+size_t dvmvs_marching_cubes_workspace_bytes(int X, int Y, int Z);
+int dvmvs_marching_cubes_count(const float* vol, int X, int Y, int Z, float level, void* workspace, size_t workspace_bytes,
+                               long long* counts_dev, dvmvs_stream_t stream);
+int dvmvs_marching_cubes_emit(const float* vol, const float* color_vol, int X, int Y, int Z, float level, float ox, float oy, float oz,
+                              float voxel_size, void* workspace, float* verts, float* normals, unsigned char* colors, int* faces,
+                              long long V, long long F, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
