@@ -1,0 +1,264 @@
+"""Scene runners of the MVDepthNet and GP-MVS baselines: the loops of the reference's dvmvs/baselines/mvdepthnet/run-testing.py and
+dvmvs/baselines/gpmvs/run-testing.py on the MI355X, without cv2 / path / tqdm / scipy.
+
+Per frame, one dvmvs::rgb_sweep launch writes the encoder's 67-channel input (the normalised reference image and its 64-plane SAD cost
+volume, 0.5 - 50 m) into a buffer the runner keeps; the encoder and decoder run on MIOpen; the prediction is 1 / clamp(disp1, 0.02, 2).
+GP-MVS filters the encoder's conv5 between frames with dvmvs::gp_filter_step: the 2x2 algebra of the filter depends on the poses only
+and is evaluated on the host (GPFilter), the float64 state stays on the device, and a frame has no host synchronisation between the
+sweep and the prediction.
+
+Reference behaviour that is kept: preprocessing with scale 1, mean 81, std 35 at the full 320x256 (no crop, K from
+get_updated_intrinsics()); "TRACKING LOST" lines are skipped and do not reset the GP state; on a scene's first frame GP-MVS measures the
+pose distance to the LAST measurement frame of that line; the timed region runs from the cost volume to the inverted prediction.
+"""
+import glob
+import os
+
+import numpy as np
+import torch
+
+from dvmvs.baselines.networks import Decoder, Encoder
+from dvmvs.baselines.gpmvs.gplayer import GPlayer
+from dvmvs.dataset_loader import PreprocessImage
+from dvmvs.hip import ops
+from dvmvs.pose_algebra import sweep_matrices_host
+from dvmvs.runner import Scene
+from dvmvs.utils import InferenceTimer, pose_distance
+
+WIDTH, HEIGHT = 320, 256
+MIN_DEPTH, MAX_DEPTH, N_DEPTH_LEVELS = 0.5, 50.0, 64
+SCALE_RGB = 1.0
+MEAN_RGB = [81.0, 81.0, 81.0]
+STD_RGB = [35.0, 35.0, 35.0]
+LATENT = (512, 8, 10)        # conv5 of a 256x320 frame
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# checkpoints
+# ----------------------------------------------------------------------------------------------------------------------
+def load_checkpoint(module, checkpoint):
+    """Loads a published checkpoint into ``module``: a plain state dict, a ``module.``-prefixed one (saved through DataParallel), or a
+    combined file ``{'state_dict': ...}`` holding several modules' parameters, of which the keys of ``module`` are taken
+    (mvdepthnet/run-testing.py:35-42)."""
+    if isinstance(checkpoint, (str, os.PathLike)):
+        checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=True)
+    combined = "state_dict" in checkpoint and isinstance(checkpoint["state_dict"], dict)
+    state = checkpoint["state_dict"] if combined else checkpoint
+    state = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state.items()}
+    if combined:
+        own = module.state_dict()
+        own.update({k: v for k, v in state.items() if k in own})
+        state = own
+    module.load_state_dict(state)
+    return module
+
+
+def _only(folder, pattern):
+    files = sorted(glob.glob(os.path.join(str(folder), pattern)))
+    if not files:
+        raise FileNotFoundError(f"no checkpoint matching {pattern!r} in {folder}")
+    return files[0]
+
+
+def build_mvdepthnet(weights_folder=None, device="cuda", seed=0):
+    """(encoder, decoder) in eval mode on ``device``.  ``weights_folder``: files ``*encoder*`` and ``*decoder*`` (the fine-tuned
+    weights), or ``pretrained_mvdepthnet_combined`` (the original combined file); None = seeded weights (tests, benchmarks)."""
+    torch.manual_seed(seed)
+    encoder, decoder = Encoder(), Decoder()
+    if weights_folder is not None:
+        combined = os.path.join(str(weights_folder), "pretrained_mvdepthnet_combined")
+        if os.path.exists(combined):
+            checkpoint = torch.load(combined, map_location="cpu", weights_only=True)
+            load_checkpoint(encoder, checkpoint)
+            load_checkpoint(decoder, checkpoint)
+        else:
+            load_checkpoint(encoder, _only(weights_folder, "*encoder*"))
+            load_checkpoint(decoder, _only(weights_folder, "*decoder*"))
+    return encoder.to(device).eval(), decoder.to(device).eval()
+
+
+def build_gpmvs(weights_folder=None, device="cuda", seed=0):
+    """(encoder, decoder, gplayer) in eval mode on ``device`` from files ``*encoder*``, ``*decoder*``, ``*gplayer*`` (plain,
+    ``module.``-prefixed or ``{'state_dict': ...}``); None = seeded weights."""
+    torch.manual_seed(seed)
+    encoder, decoder, gplayer = Encoder(), Decoder(), GPlayer(device="cpu")
+    if weights_folder is not None:
+        load_checkpoint(encoder, _only(weights_folder, "*encoder*"))
+        load_checkpoint(decoder, _only(weights_folder, "*decoder*"))
+        load_checkpoint(gplayer, _only(weights_folder, "*gplayer*"))
+    gplayer.device = torch.device(device)
+    return encoder.to(device).eval(), decoder.to(device).eval(), gplayer.to(device).eval()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# GP-MVS filter: host algebra of the poses, device state
+# ----------------------------------------------------------------------------------------------------------------------
+def gp_transition(lam, dt):
+    """expm(F dt) for F = [[0, 1], [-lam^2, -2 lam]] (double eigenvalue -lam), in closed form: e^{-lam dt} [[1 + lam dt, dt],
+    [-lam^2 dt, 1 - lam dt]]."""
+    e = np.exp(-lam * dt)
+    return e * np.array([[1.0 + lam * dt, dt], [-lam * lam * dt, 1.0 - lam * dt]])
+
+
+class GPFilter:
+    """The 2x2 part of GP-MVS's Kalman filter (gpmvs/run-testing.py:97-106, 179-190) in float64 on the host: per frame, the transition
+    A and gain k that dvmvs::gp_filter_step applies to the [2, N] state mean on the device."""
+
+    def __init__(self, gamma2_log, ell_log, sigma2_log):
+        self.gamma2, ell, self.sigma2 = np.exp(gamma2_log), np.exp(ell_log), np.exp(sigma2_log)
+        self.lam = np.sqrt(3) / ell
+        self.Pinf = np.array([[self.gamma2, 0.0], [0.0, self.gamma2 * self.lam ** 2]])
+        self.reset()
+
+    @classmethod
+    def from_gplayer(cls, gplayer):
+        return cls(*(p.detach().double().cpu().reshape(-1)[0].item() for p in (gplayer.gamma2, gplayer.ell, gplayer.sigma2)))
+
+    def reset(self):
+        """A new scene: P = Pinf; the next step starts the state mean from zero."""
+        self.P = self.Pinf.copy()
+        self.fresh = True
+
+    def step(self, dt):
+        """Advances the covariance by one frame ``dt`` apart; returns (A row-major [4], k [2], reset) for gp_filter_step."""
+        A = gp_transition(self.lam, dt)
+        Q = self.Pinf - A.dot(self.Pinf).dot(A.T)
+        P = A.dot(self.P).dot(A.T) + Q
+        s = P[0, 0] + self.sigma2
+        k = P[:, 0] / s
+        self.P = P - np.outer(k, P[0, :])
+        reset, self.fresh = self.fresh, False
+        return [float(v) for v in A.reshape(-1)], [float(k[0]), float(k[1])], reset
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# one frame
+# ----------------------------------------------------------------------------------------------------------------------
+class BaselineFrame:
+    """One frame of either baseline on preprocessed device images and host poses.  Keeps the 67-channel encoder input buffer and,
+    for GP-MVS, the float64 filter state on the device."""
+
+    def __init__(self, encoder, decoder, device, gp=None):
+        self.encoder, self.decoder, self.gp = encoder, decoder, gp
+        self.device = torch.device(device)
+        self.fused = None
+        self.state = torch.zeros((2, int(np.prod(LATENT))), dtype=torch.float64, device=self.device) if gp is not None else None
+
+    def sweep(self, reference_image, measurement_images, reference_pose, measurement_poses, K):
+        """[B, 67, H, W]: image in channels 0..2, the SAD cost volume of ``measurement_images`` in 3..66 (one launch).  Poses [B,4,4]
+        and K [B,3,3] are float32 host tensors; their sweep matrices are evaluated with the reference's fp32 expressions."""
+        B, C, H, W = reference_image.shape
+        if self.fused is None or self.fused.shape != (B, 3 + N_DEPTH_LEVELS, H, W):
+            self.fused = torch.empty((B, 3 + N_DEPTH_LEVELS, H, W), dtype=torch.float32, device=self.device)
+        Hm, kt = sweep_matrices_host(reference_pose, list(measurement_poses), K)
+        Hm = Hm.pin_memory().to(self.device, non_blocking=True)
+        kt = kt.pin_memory().to(self.device, non_blocking=True)
+        ops.rgb_sweep(self.fused, reference_image, list(measurement_images), Hm, kt, MIN_DEPTH, MAX_DEPTH, N_DEPTH_LEVELS, 3, True)
+        return self.fused
+
+    def __call__(self, reference_image, measurement_images, reference_pose, measurement_poses, K, dt=None, outputs=None):
+        """Depth [B,1,H,W].  GP-MVS needs ``dt``, the pose distance to the previous frame.  ``outputs`` (a dict) receives conv5 and,
+        for GP-MVS, Z."""
+        fused = self.sweep(reference_image, measurement_images, reference_pose, measurement_poses, K)
+        conv5, conv4, conv3, conv2, conv1 = self.encoder.forward_fused(fused)
+        if self.gp is not None:
+            A, k, reset = self.gp.step(dt)
+            latent = ops.gp_filter_step(self.state, conv5.reshape(-1), A, k, reset).view_as(conv5)
+        else:
+            latent = conv5
+        if outputs is not None:
+            outputs["conv5"] = conv5
+            outputs["Z"] = latent
+        disp = self.decoder(latent, conv4, conv3, conv2, conv1)[0]
+        return 1.0 / torch.clamp(disp, min=0.02, max=2.0)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# scene loops
+# ----------------------------------------------------------------------------------------------------------------------
+def _index_file_fields(keyframe_index_file):
+    """(keyframing type, dataset name, scene name, number of measurement frames) from "keyframe+dataset+scene+nmeas+N"."""
+    keyframing_type, dataset_name, scene_name, _, n_measurement_frames = os.path.basename(str(keyframe_index_file)).split("+")
+    return keyframing_type, dataset_name, scene_name, n_measurement_frames
+
+
+def system_name(method, keyframe_index_file, finetuned=True):
+    keyframing_type, dataset_name, _, n_measurement_frames = _index_file_fields(keyframe_index_file)
+    return "{}_{}_{}_{}_{}_{}_{}".format(keyframing_type, dataset_name, WIDTH, HEIGHT, n_measurement_frames, method,
+                                         "finetuned" if finetuned else "without_ft")
+
+
+def _to_device(image_hwc, device):
+    return torch.from_numpy(np.ascontiguousarray(np.transpose(image_hwc, (2, 0, 1)))).float().unsqueeze(0).to(device)
+
+
+def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames):
+    scene = Scene(scene_folder)
+    device = frame.device
+    position = {name: i for i, name in enumerate(scene.image_names)}
+    lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
+    timer = InferenceTimer()
+    predictions, reference_depths = [], []
+    previous_index = None
+    if frame.gp is not None:
+        frame.gp.reset()
+    with torch.no_grad():
+        for line in lines:
+            if line == "TRACKING LOST":
+                continue
+            indices = [position[name] for name in line.split(" ")]
+            reference_index, measurement_indices = indices[0], indices[1:]
+            raw = scene.image(reference_index)
+            pre = PreprocessImage(K=scene.K, old_width=raw.shape[1], old_height=raw.shape[0], new_width=WIDTH, new_height=HEIGHT,
+                                  distortion_crop=0, perform_crop=False)
+            reference_image = _to_device(pre.apply_rgb(raw, SCALE_RGB, MEAN_RGB, STD_RGB), device)
+            measurement_images = [_to_device(pre.apply_rgb(scene.image(m), SCALE_RGB, MEAN_RGB, STD_RGB), device) for m in measurement_indices]
+            reference_pose = torch.from_numpy(scene.poses[reference_index]).float().unsqueeze(0)
+            measurement_poses = [torch.from_numpy(scene.poses[m]).float().unsqueeze(0) for m in measurement_indices]
+            K = torch.from_numpy(pre.get_updated_intrinsics()).float().unsqueeze(0)
+            dt = None
+            if frame.gp is not None:
+                if previous_index is None:
+                    previous_index = measurement_indices[-1]     # the reference's leaked loop variable
+                dt = pose_distance(scene.poses[reference_index], scene.poses[previous_index])[0]
+            timer.record_start_time()
+            depth = frame(reference_image, measurement_images, reference_pose, measurement_poses, K, dt=dt)
+            timer.record_end_time_and_elapsed_time()
+            predictions.append(depth.cpu().numpy().squeeze())
+            previous_index = reference_index
+            if evaluate and scene.depth_names:
+                reference_depths.append(pre.apply_depth(scene.depth(reference_index)))
+    return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
+
+
+def predict_mvdepthnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda"):
+    """MVDepthNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer)."""
+    encoder, decoder = build_mvdepthnet(weights_folder, device)
+    return _predict(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames)
+
+
+def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda"):
+    """GP-MVS over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer)."""
+    encoder, decoder, gplayer = build_gpmvs(weights_folder, device)
+    frame = BaselineFrame(encoder, decoder, device, gp=GPFilter.from_gplayer(gplayer))
+    return _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames)
+
+
+def main(method, argv=None):
+    """``python -m dvmvs.baselines.{mvdepthnet,gpmvs} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]``."""
+    import argparse
+    from dvmvs.utils import save_results
+    parser = argparse.ArgumentParser(prog=f"python -m dvmvs.baselines.{method}")
+    parser.add_argument("scene_folder")
+    parser.add_argument("keyframe_index_file")
+    parser.add_argument("--weights", default=None, help="checkpoint folder (default: seeded weights)")
+    parser.add_argument("--without-ft", action="store_true", help="name the results '..._without_ft' (original weights)")
+    parser.add_argument("--out", default=".", help="folder for the .npz results")
+    parser.add_argument("--max-frames", type=int, default=None)
+    args = parser.parse_args(argv)
+    predict = predict_mvdepthnet if method == "mvdepthnet" else predict_gpmvs
+    predictions, reference_depths, timer = predict(args.scene_folder, args.keyframe_index_file, args.weights, max_frames=args.max_frames)
+    timer.print_statistics()
+    save_results(predictions=predictions, groundtruths=reference_depths,
+                 system_name=system_name(method, args.keyframe_index_file, finetuned=not args.without_ft),
+                 scene_name=_index_file_fields(args.keyframe_index_file)[2], save_folder=args.out)

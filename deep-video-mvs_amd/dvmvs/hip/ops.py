@@ -15,7 +15,7 @@ from torch import Tensor
 from dvmvs.hip import _capi
 
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
-           "bias_act_", "upsample2x", "depthwise_conv"]
+           "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1034,3 +1034,72 @@ def cost_volume_into(image1: Tensor, image2s, Hm: Tensor, kt: Tensor, min_depth:
         drop_sweep_workspace(image1.device, B, M, H, W, D)
     _capi.check(rc, "dvmvs_cost_volume_planned_fwd")
     return dst
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# baselines (MVDepthNet, GP-MVS): the RGB SAD sweep into the encoder input and GP-MVS's filter step (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("dvmvs::rgb_sweep", mutates_args=("out",), device_types="cuda")
+def rgb_sweep(out: Tensor, image1: Tensor, image2s: Sequence[Tensor], Hm: Tensor, kt: Tensor, min_depth: float, max_depth: float,
+              n_depth_levels: int, channel_offset: int, copy_image: bool) -> None:
+    """In place: ``out[:, channel_offset:channel_offset + n_depth_levels]`` = the SAD cost volume of the 3-channel ``image1`` against
+    ``image2s`` (cost_volume_fusion(..., dot_product=False)); with ``copy_image`` also ``out[:, 0:3] = image1``.  ``out`` is a
+    contiguous [B,Cout,H,W] tensor; no other channel is written.  Bit-identical to ``cost_volume(..., dot_product=False, variant=1)``."""
+    _dev_f32("rgb_sweep", out, image1, Hm, kt, *image2s)
+    M = len(image2s)
+    if M == 0:
+        raise ValueError("dvmvs::rgb_sweep: need at least one measurement image")
+    B, C, H, W = image1.shape
+    _check_sweep_matrices("rgb_sweep", Hm, kt, B, M)
+    if out.dim() != 4 or not out.is_contiguous() or tuple(out.shape[::2]) != (B, H) or out.shape[3] != W:
+        raise ValueError(f"dvmvs::rgb_sweep: expected a contiguous [{B},Cout,{H},{W}] output, got {tuple(out.shape)}")
+    for t in image2s:
+        if t.shape != image1.shape:
+            raise ValueError(f"dvmvs::rgb_sweep: measurement image {tuple(t.shape)} != reference {tuple(image1.shape)}")
+    image1 = image1.contiguous()
+    image2s = [t.contiguous() for t in image2s]
+    with torch.cuda.device(out.device):
+        rc = _capi.lib().dvmvs_rgb_sweep_fwd(_ptr(image1), _capi.pointer_array([_ptr(t) for t in image2s]), _ptr(Hm.contiguous()),
+                                             _ptr(kt.contiguous()), _ptr(out), B, M, C, H, W, int(n_depth_levels), float(min_depth),
+                                             float(max_depth), out.shape[1], int(channel_offset), int(bool(copy_image)), _stream(out))
+    _capi.check(rc, "dvmvs_rgb_sweep_fwd")
+
+
+@rgb_sweep.register_fake
+def _(out, image1, image2s, Hm, kt, min_depth, max_depth, n_depth_levels, channel_offset, copy_image):
+    return None
+
+
+@rgb_sweep.register_kernel("cpu")
+def _(out, image1, image2s, Hm, kt, min_depth, max_depth, n_depth_levels, channel_offset, copy_image):
+    _no_cpu("rgb_sweep")
+
+
+@torch.library.custom_op("dvmvs::gp_filter_step", mutates_args=("state",), device_types="cuda")
+def gp_filter_step(state: Tensor, y: Tensor, A: Sequence[float], k: Sequence[float], reset: bool) -> Tensor:
+    """One step of GP-MVS's Kalman filter: ``state`` [2,N] float64 in place (M <- A M; M <- M + k (y - M[0])), returns
+    relu(float32(M[0])) shaped like ``y`` (fp32, N elements).  ``A`` = the 2x2 transition row-major, ``k`` the gain (host
+    algebra: dvmvs.baselines.runner.GPFilter); ``reset`` starts from M = 0."""
+    _dev_f32("gp_filter_step", y)
+    if state.device != y.device or state.dtype != torch.float64 or not state.is_contiguous() or tuple(state.shape) != (2, y.numel()):
+        raise ValueError(f"dvmvs::gp_filter_step: expected a contiguous float64 state [2,{y.numel()}] on {y.device}, got "
+                         f"{state.dtype} {tuple(state.shape)} on {state.device}")
+    if len(A) != 4 or len(k) != 2:
+        raise ValueError("dvmvs::gp_filter_step: A has 4 entries (row-major 2x2), k has 2")
+    y = y.contiguous()
+    z = torch.empty_like(y)
+    with torch.cuda.device(y.device):
+        rc = _capi.lib().dvmvs_gp_filter_step(_ptr(state), _ptr(y), _ptr(z), y.numel(), float(A[0]), float(A[1]), float(A[2]), float(A[3]),
+                                              float(k[0]), float(k[1]), int(bool(reset)), _stream(y))
+    _capi.check(rc, "dvmvs_gp_filter_step")
+    return z
+
+
+@gp_filter_step.register_fake
+def _(state, y, A, k, reset):
+    return torch.empty_like(y)
+
+
+@gp_filter_step.register_kernel("cpu")
+def _(state, y, A, k, reset):
+    _no_cpu("gp_filter_step")

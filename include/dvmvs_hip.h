@@ -39,8 +39,10 @@ extern "C" {
  * arguments, bit-identical volumes.
  * ABI 8 (round 6) = ABI 7 + the 1x1 convolution with bias, ReLU and the residual add in its store path (dvmvs_pointwise_conv_*); no earlier
  * signature changed; dvmvs_bottleneck_conv_up2x_fwd and the 32x40 stride-2 shape of dvmvs_bottleneck_conv_fwd; dvmvs_host_pointer_device_visible, dvmvs_upsample2x_pair_fwd.
- * ABI 9 = ABI 8 + marching cubes on a voxel volume (dvmvs_marching_cubes_*); no earlier signature changed. */
-#define DVMVS_ABI_VERSION 9
+ * ABI 9 = ABI 8 + marching cubes on a voxel volume (dvmvs_marching_cubes_*); no earlier signature changed.
+ * ABI 10 = ABI 9 + the RGB SAD sweep of the MVDepthNet / GP-MVS baselines (dvmvs_rgb_sweep_fwd) and GP-MVS's filter step
+ * (dvmvs_gp_filter_step); no earlier signature changed. */
+#define DVMVS_ABI_VERSION 10
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
 
@@ -472,6 +474,34 @@ int dvmvs_marching_cubes_count(const float* vol, int X, int Y, int Z, float leve
 int dvmvs_marching_cubes_emit(const float* vol, const float* color_vol, int X, int Y, int Z, float level, float ox, float oy, float oz,
                               float voxel_size, void* workspace, float* verts, float* normals, unsigned char* colors, int* faces,
                               long long V, long long F, dvmvs_stream_t stream);
+
+/*
+ * Baselines (ABI 10): MVDepthNet and GP-MVS, the reference's dvmvs/baselines/{mvdepthnet,gpmvs}/run-testing.py.
+ *
+ * dvmvs_rgb_sweep_fwd: cost_volume_fusion(..., dot_product=False) of a 3-channel image (utils.py:45-107), written into a channel
+ * slice of a caller-owned tensor; with copy_image = 1 the reference image goes into channels 0..2 of the same tensor, so one launch
+ * yields the encoders' torch.cat((image, cost_volume), 1) input.  Bit-identical to dvmvs_cost_volume_fwd(dot_product = 0,
+ * variant = 1) on the same arguments.  No gradient.
+ *   image1      [B,3,H,W]   reference image            image2s  host array of M device pointers, each [B,3,H,W]
+ *   Hm, kt      [B,M,9], [B,M,3] as for dvmvs_cost_volume_fwd; min_depth, max_depth, D as there (plane 0 = max_depth)
+ *   out         [B,Cout,H,W]  the volume goes to channels [channel_offset, channel_offset + D); nothing else is written except,
+ *               with copy_image = 1, channels 0..2 (= image1); every other channel keeps its contents
+ *   Returns DVMVS_EUNSUPPORTED for C != 3, M > DVMVS_MAX_MEASUREMENTS, D > DVMVS_MAX_DEPTH_LEVELS or Cout * H * W >= 2^31;
+ *   DVMVS_EINVAL for a null pointer, a non-positive dimension or depth, copy_image not 0 / 1, or a slice that overruns Cout or
+ *   (copy_image = 1) overlaps channels 0..2.
+ *
+ * dvmvs_gp_filter_step: one step of GP-MVS's Kalman filter over the N = 512 * 8 * 10 bottleneck columns (run-testing.py:179-193), in
+ * float64 like the reference's numpy:  M <- A M;  v = y - M[0];  M <- M + k v;  z = relu(float32(M[0])).
+ *   state  [2,N] float64, in place (the reference's M)   y [N] fp32 (the encoder's conv5, read in place)   z [N] fp32 out
+ *   a00..a11  A = expm(F dt) row-major;  k0, k1  the Kalman gain (host algebra of the poses: dvmvs.baselines.runner)
+ *   reset  1 = start from M = 0 (a scene's first frame; the old state is not read), 0 = continue
+ *   Returns DVMVS_EINVAL for a null pointer, N <= 0 or reset not 0 / 1; DVMVS_EUNSUPPORTED for N > 2^30.
+ */
+int dvmvs_rgb_sweep_fwd(const float* image1, const float* const* image2s, const float* Hm, const float* kt, float* out,
+                        int B, int M, int C, int H, int W, int D, double min_depth, double max_depth, int Cout,
+                        int channel_offset, int copy_image, dvmvs_stream_t stream);
+int dvmvs_gp_filter_step(double* state, const float* y, float* z, int N, double a00, double a01, double a10, double a11,
+                         double k0, double k1, int reset, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
