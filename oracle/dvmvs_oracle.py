@@ -86,10 +86,11 @@ def unnormalize_align_corners(g: Tensor, size: int) -> Tensor:
 def plane_depths(min_depth: float, max_depth: float, n_depth_levels: int) -> List[float]:
     """Depth of every sweep plane, far -> near, uniform in inverse depth (python doubles).
 
-    /root/reference/dvmvs/utils.py:59-66.
+    /root/reference/dvmvs/utils.py:59-66.  One plane (where the reference would divide by zero) is the far plane, as in
+    the kernels' plane spacing (csrc/plane_sweep.h, fill_sweep_args).
     """
     base = 1.0 / max_depth
-    step = (1.0 / min_depth - 1.0 / max_depth) / (n_depth_levels - 1)
+    step = (1.0 / min_depth - 1.0 / max_depth) / (n_depth_levels - 1) if n_depth_levels > 1 else 0.0
     return [1 / (base + i * step) for i in range(n_depth_levels)]
 
 

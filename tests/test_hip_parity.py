@@ -18,6 +18,7 @@ import torch
 import dvmvs_oracle as orc
 import hipcall
 import synthetic as syn
+from accuracy import as_accurate_as_reference, f64  # noqa: F401  (also imported from here by test_sweep_mfma_gpu)
 
 pytestmark = pytest.mark.gpu
 
@@ -65,21 +66,6 @@ def check_pins(t, z, prefix, atol):
 VARIANTS = [0, 1, 2, 3, 4, 5, 6, 7]   # 0 automatic, 1 generic, 2 / 3 the two configurations of the LDS-tiled sweep, 4 / 5 the same without a second pass,
                                       # 6 the correlate-then-interpolate sweep on the fp32 matrix cores (csrc/sweep_mfma.hip; persistent form where
                                       # eligible), 7 its one-item-per-workgroup form
-
-
-def as_accurate_as_reference(got, ref32, ref64, slack=3.0, floor=2e-6):
-    """Principled fp32 criterion: measured against the SAME algebra evaluated in float64, the kernel may be at most
-    ``slack`` times as far away as the float32 reference/oracle itself is (plus a small floor).  This separates
-    "different rounding" (allowed: the fp32 result is only defined up to its own round-off, which for the sweep is
-    dominated by ~1e-5 px of sample-position error times the feature gradient) from "different algorithm"."""
-    got, ref32, ref64 = got.detach().cpu().double(), ref32.detach().cpu().double(), ref64.detach().cpu().double()
-    err_kernel, err_ref = (got - ref64).abs(), (ref32 - ref64).abs()
-    assert err_kernel.max().item() <= slack * err_ref.max().item() + floor, (err_kernel.max().item(), err_ref.max().item())
-    assert err_kernel.mean().item() <= slack * err_ref.mean().item() + floor / 10, (err_kernel.mean().item(), err_ref.mean().item())
-
-
-def f64(*ts):
-    return [t.double() if isinstance(t, torch.Tensor) else [x.double() for x in t] for t in ts]
 
 
 def run_cv(ops, dev, f1, f2s, p1, p2s, K, lo, hi, D, dot, variant):
