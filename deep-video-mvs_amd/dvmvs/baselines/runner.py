@@ -1,5 +1,5 @@
-"""Scene runners of the MVDepthNet and GP-MVS baselines: the loops of the reference's dvmvs/baselines/mvdepthnet/run-testing.py and
-dvmvs/baselines/gpmvs/run-testing.py on the MI355X, without cv2 / path / tqdm / scipy.
+"""Scene runners of the MVDepthNet, GP-MVS and DPSNet baselines: the loops of the reference's dvmvs/baselines/mvdepthnet/run-testing.py,
+dvmvs/baselines/gpmvs/run-testing.py and dvmvs/baselines/dpsnet/run-testing.py on the MI355X, without cv2 / path / tqdm / scipy.
 
 Per frame, one dvmvs::rgb_sweep launch writes the encoder's 67-channel input (the normalised reference image and its 64-plane SAD cost
 volume, 0.5 - 50 m) into a buffer the runner keeps; the encoder and decoder run on MIOpen; the prediction is 1 / clamp(disp1, 0.02, 2).
@@ -10,6 +10,10 @@ sweep and the prediction.
 Reference behaviour that is kept: preprocessing with scale 1, mean 81, std 35 at the full 320x256 (no crop, K from
 get_updated_intrinsics()); "TRACKING LOST" lines are skipped and do not reset the GP state; on a scene's first frame GP-MVS measures the
 pose distance to the LAST measurement frame of that line; the timed region runs from the cost volume to the inverted prediction.
+
+DPSNet (predict_dpsnet) differs: 320x240, scale 255 with mean and std 0.5, PSNet(64, 0.5); the network gets the relative poses
+(inv(measurement) @ reference)[0:3], taken in float64 on the host, K and np.linalg.inv(K); the timed region is the network call and its
+second output is the prediction.
 """
 import glob
 import os
@@ -18,6 +22,7 @@ import numpy as np
 import torch
 
 from dvmvs.baselines.networks import Decoder, Encoder
+from dvmvs.baselines.dpsnet.dpsnet import PSNet
 from dvmvs.baselines.gpmvs.gplayer import GPlayer
 from dvmvs.dataset_loader import PreprocessImage
 from dvmvs.hip import ops
@@ -31,6 +36,11 @@ SCALE_RGB = 1.0
 MEAN_RGB = [81.0, 81.0, 81.0]
 STD_RGB = [35.0, 35.0, 35.0]
 LATENT = (512, 8, 10)        # conv5 of a 256x320 frame
+DPS_WIDTH, DPS_HEIGHT = 320, 240
+DPS_NLABEL, DPS_MIN_DEPTH = 64, 0.5
+DPS_SCALE_RGB = 255.0
+DPS_MEAN_RGB = [0.5, 0.5, 0.5]
+DPS_STD_RGB = [0.5, 0.5, 0.5]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -88,6 +98,16 @@ def build_gpmvs(weights_folder=None, device="cuda", seed=0):
         load_checkpoint(gplayer, _only(weights_folder, "*gplayer*"))
     gplayer.device = torch.device(device)
     return encoder.to(device).eval(), decoder.to(device).eval(), gplayer.to(device).eval()
+
+
+def build_dpsnet(weights_folder=None, device="cuda", seed=0):
+    """PSNet(64, 0.5) in eval mode on ``device`` from a file ``*dpsnet*`` (a plain state dict: the fine-tuned weights, or
+    ``{'state_dict': ...}``: the original ones); None = seeded weights."""
+    torch.manual_seed(seed)
+    dpsnet = PSNet(DPS_NLABEL, DPS_MIN_DEPTH)
+    if weights_folder is not None:
+        load_checkpoint(dpsnet, _only(weights_folder, "*dpsnet*"))
+    return dpsnet.to(device).eval()
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -182,9 +202,10 @@ def _index_file_fields(keyframe_index_file):
     return keyframing_type, dataset_name, scene_name, n_measurement_frames
 
 
-def system_name(method, keyframe_index_file, finetuned=True):
+def system_name(method, keyframe_index_file, finetuned=True, size=(WIDTH, HEIGHT)):
+    """Result name of the run-testing scripts; ``size`` = (width, height) of the network input (DPSNet: 320 x 240)."""
     keyframing_type, dataset_name, _, n_measurement_frames = _index_file_fields(keyframe_index_file)
-    return "{}_{}_{}_{}_{}_{}_{}".format(keyframing_type, dataset_name, WIDTH, HEIGHT, n_measurement_frames, method,
+    return "{}_{}_{}_{}_{}_{}_{}".format(keyframing_type, dataset_name, size[0], size[1], n_measurement_frames, method,
                                          "finetuned" if finetuned else "without_ft")
 
 
@@ -244,8 +265,46 @@ def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evalua
     return _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames)
 
 
+def dpsnet_relative_pose(reference_pose, measurement_pose):
+    """[1,3,4] float32: (inv(measurement) @ reference)[0:3] in float64 on the host, then cast (dpsnet/run-testing.py:110-112)."""
+    return torch.from_numpy((np.linalg.inv(measurement_pose) @ reference_pose)[0:3, :]).float().unsqueeze(0)
+
+
+def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda"):
+    """DPSNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer)."""
+    dpsnet = build_dpsnet(weights_folder, device)
+    scene = Scene(scene_folder)
+    position = {name: i for i, name in enumerate(scene.image_names)}
+    lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
+    timer = InferenceTimer()
+    predictions, reference_depths = [], []
+    with torch.no_grad():
+        for line in lines:
+            if line == "TRACKING LOST":
+                continue
+            indices = [position[name] for name in line.split(" ")]
+            reference_index, measurement_indices = indices[0], indices[1:]
+            raw = scene.image(reference_index)
+            pre = PreprocessImage(K=scene.K, old_width=raw.shape[1], old_height=raw.shape[0], new_width=DPS_WIDTH, new_height=DPS_HEIGHT,
+                                  distortion_crop=0, perform_crop=False)
+            rgb = (DPS_SCALE_RGB, DPS_MEAN_RGB, DPS_STD_RGB)
+            reference_image = _to_device(pre.apply_rgb(raw, *rgb), device)
+            measurement_images = [_to_device(pre.apply_rgb(scene.image(m), *rgb), device) for m in measurement_indices]
+            poses = [dpsnet_relative_pose(scene.poses[reference_index], scene.poses[m]).to(device) for m in measurement_indices]
+            camera_k = pre.get_updated_intrinsics()
+            K = torch.from_numpy(camera_k).float().unsqueeze(0).to(device)
+            K_inv = torch.from_numpy(np.linalg.inv(camera_k)).float().unsqueeze(0).to(device)
+            timer.record_start_time()
+            _, prediction = dpsnet(reference_image, measurement_images, poses, K, K_inv)
+            timer.record_end_time_and_elapsed_time()
+            predictions.append(prediction.cpu().numpy().squeeze())
+            if evaluate and scene.depth_names:
+                reference_depths.append(pre.apply_depth(scene.depth(reference_index)))
+    return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
+
+
 def main(method, argv=None):
-    """``python -m dvmvs.baselines.{mvdepthnet,gpmvs} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]``."""
+    """``python -m dvmvs.baselines.{mvdepthnet,gpmvs,dpsnet} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]``."""
     import argparse
     from dvmvs.utils import save_results
     parser = argparse.ArgumentParser(prog=f"python -m dvmvs.baselines.{method}")
@@ -256,9 +315,10 @@ def main(method, argv=None):
     parser.add_argument("--out", default=".", help="folder for the .npz results")
     parser.add_argument("--max-frames", type=int, default=None)
     args = parser.parse_args(argv)
-    predict = predict_mvdepthnet if method == "mvdepthnet" else predict_gpmvs
+    predict = {"mvdepthnet": predict_mvdepthnet, "gpmvs": predict_gpmvs, "dpsnet": predict_dpsnet}[method]
+    size = (DPS_WIDTH, DPS_HEIGHT) if method == "dpsnet" else (WIDTH, HEIGHT)
     predictions, reference_depths, timer = predict(args.scene_folder, args.keyframe_index_file, args.weights, max_frames=args.max_frames)
     timer.print_statistics()
     save_results(predictions=predictions, groundtruths=reference_depths,
-                 system_name=system_name(method, args.keyframe_index_file, finetuned=not args.without_ft),
+                 system_name=system_name(method, args.keyframe_index_file, finetuned=not args.without_ft, size=size),
                  scene_name=_index_file_fields(args.keyframe_index_file)[2], save_folder=args.out)

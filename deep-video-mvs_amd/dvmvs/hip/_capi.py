@@ -17,7 +17,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DVMVS_HIP_LIB", os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libdvmvs_hip.so")))
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MAX_MEASUREMENTS = 8
 MAX_DEPTH_LEVELS = 256
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
@@ -103,6 +103,8 @@ SIGNATURES = {
     "dvmvs_rgb_sweep_fwd": (_c_int, [_c_fp, _c_fpp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                      _c_dbl, _c_dbl, _c_int, _c_int, _c_int, _c_stream]),
     "dvmvs_gp_filter_step": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_int, _c_stream]),
+    "dvmvs_dps_volume_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_stream]),
+    "dvmvs_dps_regress_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_stream]),
 }
 
 _lib = None

@@ -15,7 +15,7 @@ from torch import Tensor
 from dvmvs.hip import _capi
 
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
-           "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step"]
+           "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1103,3 +1103,72 @@ def _(state, y, A, k, reset):
 @gp_filter_step.register_kernel("cpu")
 def _(state, y, A, k, reset):
     _no_cpu("gp_filter_step")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# DPSNet baseline: the plane volume of one measurement frame and the up-sampling soft-argmin (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op("dvmvs::dps_volume", mutates_args=(), device_types="cuda")
+def dps_volume(ref: Tensor, meas: Tensor, pose: Tensor, K: Tensor, Kinv: Tensor, nlabel: int, mindepth: float) -> Tensor:
+    """[B,2C,nlabel,h,w]: channels 0..C-1 = ``ref`` at every plane, channels C..2C-1 = ``meas`` warped to plane i at depth
+    mindepth * nlabel / (i + 1e-16) with DPSNet's ``inverse_warp`` (K^-1 un-projection, Z >= 1e-3, (w - 1) normalisation, coordinates
+    outside [-1, 1] fully masked).  ``pose`` [B,3,4] maps the reference camera to the measurement camera; ``K`` / ``Kinv`` [B,3,3] are
+    the intrinsics at the resolution of the features."""
+    _dev_f32("dps_volume", ref, meas, pose, K, Kinv)
+    if ref.dim() != 4 or meas.shape != ref.shape:
+        raise ValueError(f"dvmvs::dps_volume: expected two [B,C,h,w] feature maps, got {tuple(ref.shape)} and {tuple(meas.shape)}")
+    B, C, h, w = ref.shape
+    if tuple(pose.shape) != (B, 3, 4) or tuple(K.shape) != (B, 3, 3) or tuple(Kinv.shape) != (B, 3, 3):
+        raise ValueError(f"dvmvs::dps_volume: expected pose [{B},3,4] and K, Kinv [{B},3,3], got {tuple(pose.shape)}, {tuple(K.shape)}, "
+                         f"{tuple(Kinv.shape)}")
+    ref, meas, pose, K, Kinv = (t.contiguous() for t in (ref, meas, pose, K, Kinv))
+    out = torch.empty((B, 2 * C, int(nlabel), h, w), dtype=torch.float32, device=ref.device)
+    with torch.cuda.device(ref.device):
+        rc = _capi.lib().dvmvs_dps_volume_fwd(_ptr(ref), _ptr(meas), _ptr(pose), _ptr(K), _ptr(Kinv), _ptr(out), B, C, h, w, int(nlabel),
+                                              float(mindepth), _stream(ref))
+    _capi.check(rc, "dvmvs_dps_volume_fwd")
+    return out
+
+
+@dps_volume.register_fake
+def _(ref, meas, pose, K, Kinv, nlabel, mindepth):
+    B, C, h, w = ref.shape
+    return ref.new_empty((B, 2 * C, nlabel, h, w))
+
+
+@dps_volume.register_kernel("cpu")
+def _(ref, meas, pose, K, Kinv, nlabel, mindepth):
+    _no_cpu("dps_volume")
+
+
+@torch.library.custom_op("dvmvs::dps_regress", mutates_args=(), device_types="cuda")
+def dps_regress(costs: Tensor, height: int, width: int, mindepth: float, with_pred: bool = True) -> Tuple[Tensor, Tensor]:
+    """(depth [B,1,H,W], pred [B,H,W]) of DPSNet's regression: the plane costs [B,nlabel,h,w] or [B,1,nlabel,h,w] are up-sampled to
+    (``height``, ``width``) per plane (bilinear, half-pixel centres), then pred = sum_i softmax_i * i and
+    depth = mindepth * nlabel / (pred + 1e-16).  With ``with_pred`` False the expectation is not written (an empty tensor is returned)."""
+    _dev_f32("dps_regress", costs)
+    if costs.dim() == 5 and costs.shape[1] == 1:
+        costs = costs[:, 0]
+    if costs.dim() != 4:
+        raise ValueError(f"dvmvs::dps_regress: expected costs [B,nlabel,h,w] or [B,1,nlabel,h,w], got {tuple(costs.shape)}")
+    costs = costs.contiguous()
+    B, nlabel, h, w = costs.shape
+    H, W = int(height), int(width)
+    depth = torch.empty((B, 1, H, W), dtype=torch.float32, device=costs.device)
+    pred = torch.empty((B, H, W) if with_pred else (0,), dtype=torch.float32, device=costs.device)
+    with torch.cuda.device(costs.device):
+        rc = _capi.lib().dvmvs_dps_regress_fwd(_ptr(costs), _ptr(depth), _ptr(pred) if with_pred else None, B, nlabel, h, w, H, W,
+                                               float(mindepth), _stream(costs))
+    _capi.check(rc, "dvmvs_dps_regress_fwd")
+    return depth, pred
+
+
+@dps_regress.register_fake
+def _(costs, height, width, mindepth, with_pred=True):
+    B = costs.shape[0]
+    return costs.new_empty((B, 1, height, width)), costs.new_empty((B, height, width) if with_pred else (0,))
+
+
+@dps_regress.register_kernel("cpu")
+def _(costs, height, width, mindepth, with_pred=True):
+    _no_cpu("dps_regress")

@@ -41,8 +41,10 @@ extern "C" {
  * signature changed; dvmvs_bottleneck_conv_up2x_fwd and the 32x40 stride-2 shape of dvmvs_bottleneck_conv_fwd; dvmvs_host_pointer_device_visible, dvmvs_upsample2x_pair_fwd.
  * ABI 9 = ABI 8 + marching cubes on a voxel volume (dvmvs_marching_cubes_*); no earlier signature changed.
  * ABI 10 = ABI 9 + the RGB SAD sweep of the MVDepthNet / GP-MVS baselines (dvmvs_rgb_sweep_fwd) and GP-MVS's filter step
- * (dvmvs_gp_filter_step); no earlier signature changed. */
-#define DVMVS_ABI_VERSION 10
+ * (dvmvs_gp_filter_step); no earlier signature changed.
+ * ABI 11 = ABI 10 + the DPSNet baseline's plane volume (dvmvs_dps_volume_fwd) and its up-sampling soft-argmin (dvmvs_dps_regress_fwd);
+ * no earlier signature changed. */
+#define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
 
@@ -502,6 +504,33 @@ int dvmvs_rgb_sweep_fwd(const float* image1, const float* const* image2s, const 
                         int channel_offset, int copy_image, dvmvs_stream_t stream);
 int dvmvs_gp_filter_step(double* state, const float* y, float* z, int N, double a00, double a01, double a10, double a11,
                          double k0, double k1, int reset, dvmvs_stream_t stream);
+
+/*
+ * DPSNet baseline (ABI 11): the reference's dvmvs/baselines/dpsnet/dpsnet.py.  Forward only.
+ *
+ * dvmvs_dps_volume_fwd: the plane volume of one measurement frame (dpsnet.py:343-351, the loop of inverse_warp calls), in the layout
+ * Conv3d reads.  Channels 0..C-1 hold the reference features at every plane; channels C..2C-1 the measurement features warped to
+ * plane i, whose depth is fp32(mindepth) * nlabel / (i + 1e-16) (plane 0 lies at ~3.2e17, as in the reference).  Warp convention
+ * (dpsnet.py:36-120, not the one of dvmvs_cost_volume_fwd): cam = (Kinv [x,y,1]) depth; p = (K pose)[:, :3] cam + (K pose)[:, 3];
+ * Z = max(p_z, 1e-3); gx = 2 (p_x / Z) / (w - 1) - 1, gy likewise with h; gx or gy outside [-1, 1] becomes 2 (the sample reads
+ * zeros); bilinear, zeros padding, align_corners = True.  K pose is taken in fp32 by the kernel.
+ *   ref, meas  [B,C,h,w]      pose [B,3,4] (reference camera -> measurement camera)      K, Kinv [B,3,3] at the feature resolution
+ *   out        [B,2C,nlabel,h,w], every element written
+ *   Returns DVMVS_EINVAL for a null pointer, a non-positive dimension or mindepth; DVMVS_EUNSUPPORTED for C > 64,
+ *   nlabel > DVMVS_MAX_DEPTH_LEVELS, B > 65535 or h * w >= 2^24.
+ *
+ * dvmvs_dps_regress_fwd: up-sampling, softmax and expectation (dpsnet.py:373-383):
+ *   c = interpolate(costs, [nlabel,H,W], trilinear, align_corners = False)   (per plane: bilinear, half-pixel centres, clamped borders)
+ *   pred = sum_i softmax(c)_i * i;      depth = mindepth * nlabel / (pred + 1e-16)
+ * The costs are interpolated, then the softmax is taken (not the other way round).
+ *   costs [B,nlabel,h,w] (= [B,1,nlabel,h,w])      depth [B,1,H,W] out      pred [B,H,W] out, or null: not written
+ *   Returns DVMVS_EINVAL for a null costs / depth pointer, a non-positive dimension or mindepth; DVMVS_EUNSUPPORTED for
+ *   nlabel > DVMVS_MAX_DEPTH_LEVELS, B > 65535, or h * w or H * W >= 2^30.
+ */
+int dvmvs_dps_volume_fwd(const float* ref, const float* meas, const float* pose, const float* K, const float* Kinv, float* out,
+                         int B, int C, int h, int w, int nlabel, double mindepth, dvmvs_stream_t stream);
+int dvmvs_dps_regress_fwd(const float* costs, float* depth, float* pred, int B, int nlabel, int h, int w, int H, int W,
+                          double mindepth, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
