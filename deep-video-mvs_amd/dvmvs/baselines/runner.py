@@ -24,7 +24,7 @@ import torch
 from dvmvs.baselines.networks import Decoder, Encoder
 from dvmvs.baselines.dpsnet.dpsnet import PSNet
 from dvmvs.baselines.gpmvs.gplayer import GPlayer
-from dvmvs.dataset_loader import PreprocessImage
+from dvmvs.dataset_loader import FrameUploader, PreprocessImage
 from dvmvs.hip import ops
 from dvmvs.pose_algebra import sweep_matrices_host
 from dvmvs.runner import Scene
@@ -213,9 +213,24 @@ def _to_device(image_hwc, device):
     return torch.from_numpy(np.ascontiguousarray(np.transpose(image_hwc, (2, 0, 1)))).float().unsqueeze(0).to(device)
 
 
-def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames):
-    scene = Scene(scene_folder)
+def _prepare(pre, raw, rgb, device, uploader):
+    """Network input [1,3,h,w] on the device: numpy on the host and a blocking copy, or (``uploader``) one kernel launch on the raw frame."""
+    if uploader is None:
+        return _to_device(pre.apply_rgb(raw, *rgb), device)
+    return pre.apply_rgb_device(raw, *rgb, device=device, uploader=uploader)
+
+
+def _reference_depth(pre, scene, reference_index, device, uploader):
+    if uploader is None:
+        return pre.apply_depth(scene.depth(reference_index))
+    return pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader)[0].cpu().numpy()
+
+
+def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess=False):
+    scene = Scene(scene_folder, raw=device_preprocess)
     device = frame.device
+    uploader = FrameUploader(device) if device_preprocess else None
+    rgb = (SCALE_RGB, MEAN_RGB, STD_RGB)
     position = {name: i for i, name in enumerate(scene.image_names)}
     lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
     timer = InferenceTimer()
@@ -232,8 +247,8 @@ def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames):
             raw = scene.image(reference_index)
             pre = PreprocessImage(K=scene.K, old_width=raw.shape[1], old_height=raw.shape[0], new_width=WIDTH, new_height=HEIGHT,
                                   distortion_crop=0, perform_crop=False)
-            reference_image = _to_device(pre.apply_rgb(raw, SCALE_RGB, MEAN_RGB, STD_RGB), device)
-            measurement_images = [_to_device(pre.apply_rgb(scene.image(m), SCALE_RGB, MEAN_RGB, STD_RGB), device) for m in measurement_indices]
+            reference_image = _prepare(pre, raw, rgb, device, uploader)
+            measurement_images = [_prepare(pre, scene.image(m), rgb, device, uploader) for m in measurement_indices]
             reference_pose = torch.from_numpy(scene.poses[reference_index]).float().unsqueeze(0)
             measurement_poses = [torch.from_numpy(scene.poses[m]).float().unsqueeze(0) for m in measurement_indices]
             K = torch.from_numpy(pre.get_updated_intrinsics()).float().unsqueeze(0)
@@ -248,21 +263,26 @@ def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames):
             predictions.append(depth.cpu().numpy().squeeze())
             previous_index = reference_index
             if evaluate and scene.depth_names:
-                reference_depths.append(pre.apply_depth(scene.depth(reference_index)))
+                reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
 
 
-def predict_mvdepthnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda"):
-    """MVDepthNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer)."""
+def predict_mvdepthnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
+                       device_preprocess=False):
+    """MVDepthNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
+    ``device_preprocess``: raw 8-bit frames are uploaded through a pinned ring and pre-processed by dvmvs.hip.ops.preprocess_rgb (the
+    ground-truth depth by preprocess_depth, float32) instead of by numpy on the host."""
     encoder, decoder = build_mvdepthnet(weights_folder, device)
-    return _predict(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames)
+    return _predict(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess)
 
 
-def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda"):
-    """GP-MVS over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer)."""
+def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
+                  device_preprocess=False):
+    """GP-MVS over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
+    ``device_preprocess`` as in ``predict_mvdepthnet``."""
     encoder, decoder, gplayer = build_gpmvs(weights_folder, device)
     frame = BaselineFrame(encoder, decoder, device, gp=GPFilter.from_gplayer(gplayer))
-    return _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames)
+    return _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess)
 
 
 def dpsnet_relative_pose(reference_pose, measurement_pose):
@@ -270,10 +290,13 @@ def dpsnet_relative_pose(reference_pose, measurement_pose):
     return torch.from_numpy((np.linalg.inv(measurement_pose) @ reference_pose)[0:3, :]).float().unsqueeze(0)
 
 
-def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda"):
-    """DPSNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer)."""
+def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
+                   device_preprocess=False):
+    """DPSNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
+    ``device_preprocess`` as in ``predict_mvdepthnet``."""
     dpsnet = build_dpsnet(weights_folder, device)
-    scene = Scene(scene_folder)
+    scene = Scene(scene_folder, raw=device_preprocess)
+    uploader = FrameUploader(device) if device_preprocess else None
     position = {name: i for i, name in enumerate(scene.image_names)}
     lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
     timer = InferenceTimer()
@@ -288,8 +311,8 @@ def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evalu
             pre = PreprocessImage(K=scene.K, old_width=raw.shape[1], old_height=raw.shape[0], new_width=DPS_WIDTH, new_height=DPS_HEIGHT,
                                   distortion_crop=0, perform_crop=False)
             rgb = (DPS_SCALE_RGB, DPS_MEAN_RGB, DPS_STD_RGB)
-            reference_image = _to_device(pre.apply_rgb(raw, *rgb), device)
-            measurement_images = [_to_device(pre.apply_rgb(scene.image(m), *rgb), device) for m in measurement_indices]
+            reference_image = _prepare(pre, raw, rgb, device, uploader)
+            measurement_images = [_prepare(pre, scene.image(m), rgb, device, uploader) for m in measurement_indices]
             poses = [dpsnet_relative_pose(scene.poses[reference_index], scene.poses[m]).to(device) for m in measurement_indices]
             camera_k = pre.get_updated_intrinsics()
             K = torch.from_numpy(camera_k).float().unsqueeze(0).to(device)
@@ -299,12 +322,13 @@ def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evalu
             timer.record_end_time_and_elapsed_time()
             predictions.append(prediction.cpu().numpy().squeeze())
             if evaluate and scene.depth_names:
-                reference_depths.append(pre.apply_depth(scene.depth(reference_index)))
+                reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
 
 
 def main(method, argv=None):
-    """``python -m dvmvs.baselines.{mvdepthnet,gpmvs,dpsnet} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]``."""
+    """``python -m dvmvs.baselines.{mvdepthnet,gpmvs,dpsnet} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]
+    [--device-preprocess]``."""
     import argparse
     from dvmvs.utils import save_results
     parser = argparse.ArgumentParser(prog=f"python -m dvmvs.baselines.{method}")
@@ -314,10 +338,13 @@ def main(method, argv=None):
     parser.add_argument("--without-ft", action="store_true", help="name the results '..._without_ft' (original weights)")
     parser.add_argument("--out", default=".", help="folder for the .npz results")
     parser.add_argument("--max-frames", type=int, default=None)
+    parser.add_argument("--device-preprocess", action="store_true",
+                        help="crop / resize / normalise the raw 8-bit frames on the GPU (one launch per image) instead of with numpy")
     args = parser.parse_args(argv)
     predict = {"mvdepthnet": predict_mvdepthnet, "gpmvs": predict_gpmvs, "dpsnet": predict_dpsnet}[method]
     size = (DPS_WIDTH, DPS_HEIGHT) if method == "dpsnet" else (WIDTH, HEIGHT)
-    predictions, reference_depths, timer = predict(args.scene_folder, args.keyframe_index_file, args.weights, max_frames=args.max_frames)
+    predictions, reference_depths, timer = predict(args.scene_folder, args.keyframe_index_file, args.weights, max_frames=args.max_frames,
+                                                  device_preprocess=args.device_preprocess)
     timer.print_statistics()
     save_results(predictions=predictions, groundtruths=reference_depths,
                  system_name=system_name(method, args.keyframe_index_file, finetuned=not args.without_ft, size=size),

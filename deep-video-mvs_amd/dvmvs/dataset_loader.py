@@ -27,6 +27,83 @@ def load_depth_png(path, scaling=1000.0):
     return np.asarray(Image.open(path)).astype(np.float64) / scaling
 
 
+def load_image_u8(path):
+    """RGB image as uint8 [H,W,3], as decoded (no float conversion): the input of ``PreprocessImage.apply_rgb_device``."""
+    return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+
+
+def load_depth_png_u16(path):
+    """16-bit depth PNG as uint16 [H,W] in millimetres, as decoded: the input of ``PreprocessImage.apply_depth_device``."""
+    return np.asarray(Image.open(path)).astype(np.uint16, copy=False)
+
+
+class FrameUploader:
+    """Host -> device copies of raw frames through a fixed ring of pinned staging buffers, owned by whoever runs the frames (a scene
+    runner keeps one per call): a frame is copied into the next slot's pinned buffer, sent with a ``non_blocking`` copy on the current
+    stream, and an event recorded behind the copy says when the slot may be overwritten -- ``upload`` waits on that event, and on
+    nothing else, before it reuses a slot.  The buffers grow to the largest frame seen and are freed with the object; there is no
+    module-level state.  On a CPU ``device`` (tests) the same ring logic runs on ordinary memory without events."""
+
+    def __init__(self, device, slots=4):
+        if slots < 1:
+            raise ValueError("FrameUploader needs at least one slot")
+        self.device = torch.device(device)
+        self.slots = int(slots)
+        self._buffers = [None] * self.slots
+        self._events = [None] * self.slots
+        self._next = 0
+
+    def _allocate(self, nbytes):
+        buffer = torch.empty(nbytes, dtype=torch.uint8)
+        return buffer.pin_memory() if self.device.type == "cuda" else buffer
+
+    def _record(self):
+        if self.device.type != "cuda":
+            return None
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(self.device))
+        return event
+
+    def upload(self, array):
+        """``array``: a numpy array or host tensor of any 8- or 16-bit layout; returns its bytes as a flat uint8 device tensor."""
+        if isinstance(array, torch.Tensor):
+            array = array.detach().cpu().numpy()
+        flat = np.ascontiguousarray(array).reshape(-1).view(np.uint8)       # may be read-only (a decoder's buffer): only read here
+        slot = self._next
+        self._next = (slot + 1) % self.slots
+        if self._events[slot] is not None:
+            self._events[slot].synchronize()        # the copy that last read this slot has finished
+            self._events[slot] = None
+        if self._buffers[slot] is None or self._buffers[slot].numel() < flat.size:
+            self._buffers[slot] = self._allocate(flat.size)
+        staged = self._buffers[slot][:flat.size]
+        np.copyto(staged.numpy(), flat)
+        if self.device.type == "cuda":
+            on_device = staged.to(self.device, non_blocking=True)
+        else:
+            on_device = staged.clone()               # `.to` would alias the slot
+        self._events[slot] = self._record()
+        return on_device
+
+    def upload_rgb(self, image_u8):
+        """uint8 [H,W,3] or [N,H,W,3] -> the same shape on the device."""
+        is_u8 = image_u8.dtype == torch.uint8 if isinstance(image_u8, torch.Tensor) else np.asarray(image_u8).dtype == np.uint8
+        if not is_u8:
+            raise TypeError(f"expected a uint8 image, got {image_u8.dtype}")
+        return self.upload(image_u8).view(tuple(image_u8.shape))
+
+    def upload_depth(self, depth_u16):
+        """uint16 [H,W] or [N,H,W] -> an int16 device tensor of the same shape holding the same bits (dvmvs.hip.ops.preprocess_depth
+        reads them as unsigned)."""
+        if isinstance(depth_u16, torch.Tensor):
+            is_16 = depth_u16.dtype == torch.int16 or (hasattr(torch, "uint16") and depth_u16.dtype == torch.uint16)
+        else:
+            is_16 = np.asarray(depth_u16).dtype in (np.dtype(np.uint16), np.dtype(np.int16))
+        if not is_16:
+            raise TypeError(f"expected a uint16 depth map (or int16 holding the same bits), got {depth_u16.dtype}")
+        return self.upload(depth_u16).view(torch.int16).view(tuple(depth_u16.shape))
+
+
 def resize_bilinear(image, new_width, new_height):
     """cv2.resize(..., interpolation=cv2.INTER_LINEAR) for float arrays [H,W] or [H,W,C]."""
     h, w = image.shape[:2]
@@ -91,6 +168,40 @@ class PreprocessImage:
         if normalize_colors:
             out = (out / scale_rgb - np.asarray(mean_rgb, dtype=out.dtype)) / np.asarray(std_rgb, dtype=out.dtype)
         return out
+
+    def apply_rgb_device(self, image_u8, scale_rgb, mean_rgb, std_rgb, normalize_colors=True, device=None, out=None, uploader=None):
+        """``apply_rgb`` of a raw 8-bit frame as one kernel launch (dvmvs.hip.ops.preprocess_rgb): returns the network's input layout,
+        float32 [1,3,new_height,new_width] on the device (``[N,H,W,3]`` gives ``[N,3,...]``).  ``image_u8``: a numpy uint8 [H,W,3], or
+        a host or device uint8 tensor.  A host image is copied to ``device`` (default: "cuda") first -- through ``uploader`` (a
+        ``FrameUploader``) when one is given, with a plain blocking copy otherwise; a device tensor is used where it is.  ``out`` as in
+        ``ops.preprocess_rgb``."""
+        from dvmvs.hip import ops
+        if isinstance(image_u8, torch.Tensor) and image_u8.device.type != "cpu":
+            raw = image_u8
+        elif uploader is not None:
+            raw = uploader.upload_rgb(image_u8)
+        else:
+            host = image_u8 if isinstance(image_u8, torch.Tensor) else torch.from_numpy(np.array(image_u8))
+            raw = host.to(torch.device("cuda") if device is None else device)
+        return ops.preprocess_rgb(raw, self.crop_x, self.crop_y, self.new_height, self.new_width, scale_rgb, mean_rgb, std_rgb,
+                                  normalize=normalize_colors, out=out)
+
+    def apply_depth_device(self, depth_u16, scaling=1000.0, device=None, uploader=None):
+        """``apply_depth(load_depth_png(...))`` of a raw 16-bit depth map (millimetres) as one kernel launch: float32
+        [1,new_height,new_width] in metres on the device, equal to the host result after ``astype(float32)``.  ``depth_u16``: a numpy
+        uint16 [H,W] (or [N,H,W]), or a host or device tensor (``torch.uint16``, or ``int16`` holding the same bits)."""
+        from dvmvs.hip import ops
+        if isinstance(depth_u16, torch.Tensor) and depth_u16.device.type != "cpu":
+            raw = depth_u16
+        elif uploader is not None:
+            raw = uploader.upload_depth(depth_u16)
+        else:
+            if isinstance(depth_u16, torch.Tensor):
+                host = depth_u16
+            else:
+                host = torch.from_numpy(np.array(depth_u16).view(np.int16))
+            raw = host.to(torch.device("cuda") if device is None else device)
+        return ops.preprocess_depth(raw, self.crop_x, self.crop_y, self.new_height, self.new_width, scaling=scaling)
 
     def get_updated_intrinsics(self):
         return np.array([[self.fx, 0, self.cx], [0, self.fy, self.cy], [0, 0, 1]])

@@ -27,6 +27,7 @@ _c_fpp = ctypes.POINTER(ctypes.c_void_p)  # host array of device pointers
 _c_int = ctypes.c_int
 _c_dbl = ctypes.c_double
 _c_stream = ctypes.c_void_p
+_c_f3 = ctypes.POINTER(ctypes.c_float)    # host array of floats
 
 # name -> (restype, argtypes); must list every symbol the header declares (checked by tests/test_capi_symbols.py)
 SIGNATURES = {
@@ -105,7 +106,14 @@ SIGNATURES = {
     "dvmvs_gp_filter_step": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_dbl, _c_int, _c_stream]),
     "dvmvs_dps_volume_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_stream]),
     "dvmvs_dps_regress_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_stream]),
+    "dvmvs_preprocess_rgb_fwd": (_c_int, [_c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int,
+                                          ctypes.c_longlong, _c_dbl, _c_f3, _c_f3, _c_int, _c_stream]),
+    "dvmvs_preprocess_depth_fwd": (_c_int, [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_stream]),
 }
+
+# Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
+# check below and only lacks these symbols, so their absence is reported as what it is.
+ADDED_WITHIN_ABI = ("dvmvs_preprocess_rgb_fwd", "dvmvs_preprocess_depth_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -124,6 +132,10 @@ def lib():
                 f"dvmvs HIP library not found at {LIB_PATH}. Build it with `make -C deep-video-mvs_amd/csrc` "
                 f"(or __graft_entry__.build()). The plane-sweep ops have no CPU / eager fallback.")
         handle = ctypes.CDLL(LIB_PATH)
+        missing = [name for name in ADDED_WITHIN_ABI if not hasattr(handle, name)]
+        if missing:
+            raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "
+                               f"rebuild it with `make -C deep-video-mvs_amd/csrc` (or __graft_entry__.build())")
         for name, (restype, argtypes) in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError here = header/library mismatch: let it propagate loudly
             fn.restype = restype
@@ -139,6 +151,11 @@ def check(code, what):
     if code != 0:
         msg = lib().dvmvs_error_string(code).decode()
         raise RuntimeError(f"{what} failed with code {code}: {msg}")
+
+
+def float_array(values):
+    """Host array of floats (``const float* ..._host`` in the header)."""
+    return (ctypes.c_float * len(values))(*[float(v) for v in values])
 
 
 def pointer_array(ptrs):

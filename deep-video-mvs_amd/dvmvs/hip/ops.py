@@ -15,7 +15,8 @@ from torch import Tensor
 from dvmvs.hip import _capi
 
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
-           "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress"]
+           "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress", "preprocess_rgb",
+           "preprocess_depth"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1172,3 +1173,97 @@ def _(costs, height, width, mindepth, with_pred=True):
 @dps_regress.register_kernel("cpu")
 def _(costs, height, width, mindepth, with_pred=True):
     _no_cpu("dps_regress")
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# frame pre-processing: raw 8-bit frames / 16-bit depth maps -> network input, one launch for N frames (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+def _raw_frames(name, raw, dtypes, channels):
+    """``raw`` as [N,H,W(,3)] on the device with unit element stride inside a row and frames H rows apart; returns (tensor, N, H, W)."""
+    if raw.device.type != "cuda":
+        _no_cpu(name)
+    if raw.dtype not in dtypes:
+        raise TypeError(f"dvmvs::{name}: expected {' or '.join(str(d) for d in dtypes)} frames, got {raw.dtype}")
+    want = 3 if channels else 2
+    if raw.dim() == want:
+        raw = raw.unsqueeze(0)
+    if raw.dim() != want + 1 or (channels and raw.shape[-1] != 3) or raw.numel() == 0:
+        layout = "[N,H,W,3] or [H,W,3]" if channels else "[N,H,W] or [H,W]"
+        raise ValueError(f"dvmvs::{name}: expected non-empty frames {layout}, got {tuple(raw.shape)}")
+    N, H, W = raw.shape[:3]
+    return raw, N, H, W
+
+
+def _check_crop(name, H, W, crop_x, crop_y, new_height, new_width):
+    if new_height < 1 or new_width < 1 or crop_x < 0 or crop_y < 0 or W - 2 * crop_x < 1 or H - 2 * crop_y < 1:
+        raise ValueError(f"dvmvs::{name}: crop ({crop_x}, {crop_y}) of a {H}x{W} frame to {new_height}x{new_width} leaves no pixels")
+
+
+def preprocess_rgb(raw: Tensor, crop_x: int, crop_y: int, new_height: int, new_width: int, scale: float, mean: Sequence[float],
+                   std: Sequence[float], normalize: bool = True, out: Optional[Tensor] = None) -> Tensor:
+    """``PreprocessImage.apply_rgb`` on the device, one launch: ``raw`` uint8 [N,H,W,3] (or [H,W,3]) interleaved RGB on the GPU -> float32
+    [N,3,new_height,new_width]: ``crop_x`` columns / ``crop_y`` rows dropped on each side, bilinear resampling (half-pixel centres, clamped
+    edges), ``(v / scale - mean[c]) / std[c]`` unless ``normalize`` is False (then the resampled 0..255 values), HWC -> CHW.  Rows may be
+    padded (``raw.stride(1) >= 3 W`` bytes; pixels and channels dense, frames H rows apart).  ``out``: a float32 [N,3,new_height,new_width]
+    view whose three planes are dense and whose batch stride is free (a slot of a larger buffer); it is returned.  Tap indices and blend
+    weights are the host function's bit for bit (evaluated in double); the fp32 blends follow its order without FMA contraction.  Runs on
+    the current stream."""
+    raw, N, H, W = _raw_frames("preprocess_rgb", raw, (torch.uint8,), True)
+    crop_x, crop_y, new_height, new_width = int(crop_x), int(crop_y), int(new_height), int(new_width)
+    _check_crop("preprocess_rgb", H, W, crop_x, crop_y, new_height, new_width)
+    if raw.stride(3) != 1 or raw.stride(2) != 3 or raw.stride(1) < 3 * W or (N > 1 and raw.stride(0) != H * raw.stride(1)):
+        raw = raw.contiguous()
+    normalize = bool(normalize)
+    if normalize:
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("dvmvs::preprocess_rgb: mean and std have 3 entries")
+        if float(scale) == 0.0 or any(float(v) == 0.0 for v in std):
+            raise ValueError("dvmvs::preprocess_rgb: scale and std must be non-zero")
+    frame = 3 * new_height * new_width
+    if out is None:
+        out = torch.empty((N, 3, new_height, new_width), dtype=torch.float32, device=raw.device)
+    else:
+        _dev_f32("preprocess_rgb", out)
+        if out.device != raw.device or tuple(out.shape) != (N, 3, new_height, new_width) or \
+                tuple(out.stride()[1:]) != (new_height * new_width, new_width, 1) or (N > 1 and out.stride(0) < frame):
+            raise ValueError(f"dvmvs::preprocess_rgb: out must be a float32 [{N},3,{new_height},{new_width}] view on {raw.device} with dense "
+                             f"planes, got {tuple(out.shape)} with strides {tuple(out.stride())} on {out.device}")
+    batch_stride = out.stride(0) if N > 1 else frame
+    with torch.cuda.device(raw.device):
+        rc = _capi.lib().dvmvs_preprocess_rgb_fwd(_ptr(raw), _ptr(out), N, H, W, raw.stride(1), crop_x, crop_y, new_height, new_width,
+                                                  batch_stride, float(scale) if normalize else 1.0,
+                                                  _capi.float_array(mean) if normalize else None,
+                                                  _capi.float_array(std) if normalize else None, int(normalize), _stream(raw))
+    _capi.check(rc, "dvmvs_preprocess_rgb_fwd")
+    return out
+
+
+# 16-bit unsigned frames on the device: torch.uint16 where this torch build has it; an int16 tensor is read as its bit pattern
+_U16_DTYPES = tuple(d for d in (getattr(torch, "uint16", None), torch.int16) if d is not None)
+
+
+def preprocess_depth(raw: Tensor, crop_x: int, crop_y: int, new_height: int, new_width: int, scaling: float = 1000.0,
+                     out: Optional[Tensor] = None) -> Tensor:
+    """``PreprocessImage.apply_depth(load_depth_png(...))`` on the device, one launch: ``raw`` 16-bit unsigned depth maps [N,H,W] (or [H,W])
+    in millimetres on the GPU -> float32 [N,new_height,new_width] in metres: crop, nearest resampling (source index
+    ``min(int(x * (w / new_w)), w - 1)``), ``float32(d / scaling)`` with the division in double.  ``raw`` is a ``torch.uint16`` tensor (this
+    torch build has the dtype and can hold and copy it on the device) or, equivalently, an ``int16`` tensor whose bits are read as unsigned
+    (``uint16_array.view(np.int16)``).  ``out``: a contiguous float32 [N,new_height,new_width] tensor; it is returned."""
+    raw, N, H, W = _raw_frames("preprocess_depth", raw, _U16_DTYPES, False)
+    crop_x, crop_y, new_height, new_width = int(crop_x), int(crop_y), int(new_height), int(new_width)
+    _check_crop("preprocess_depth", H, W, crop_x, crop_y, new_height, new_width)
+    if float(scaling) == 0.0:
+        raise ValueError("dvmvs::preprocess_depth: scaling must be non-zero")
+    raw = raw.contiguous()
+    if out is None:
+        out = torch.empty((N, new_height, new_width), dtype=torch.float32, device=raw.device)
+    else:
+        _dev_f32("preprocess_depth", out)
+        if out.device != raw.device or tuple(out.shape) != (N, new_height, new_width) or not out.is_contiguous():
+            raise ValueError(f"dvmvs::preprocess_depth: out must be a contiguous float32 [{N},{new_height},{new_width}] tensor on {raw.device}, "
+                             f"got {tuple(out.shape)} on {out.device}")
+    with torch.cuda.device(raw.device):
+        rc = _capi.lib().dvmvs_preprocess_depth_fwd(_ptr(raw), _ptr(out), N, H, W, crop_x, crop_y, new_height, new_width, float(scaling),
+                                                    _stream(raw))
+    _capi.check(rc, "dvmvs_preprocess_depth_fwd")
+    return out

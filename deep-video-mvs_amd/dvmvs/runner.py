@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from dvmvs.config import Config
-from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image
+from dvmvs.dataset_loader import FrameUploader, PreprocessImage, load_depth_png, load_depth_png_u16, load_image, load_image_u8
 from dvmvs.engine import DepthEngine
 from dvmvs.keyframe_buffer import KeyframeBuffer
 from dvmvs.utils import InferenceTimer
@@ -23,8 +23,11 @@ STD_RGB = [0.229, 0.224, 0.225]
 
 
 class Scene:
-    def __init__(self, folder):
+    """``raw=True``: ``image`` / ``depth`` return the files as decoded (uint8 RGB, uint16 millimetres) for pre-processing on the device."""
+
+    def __init__(self, folder, raw=False):
         self.folder = str(folder)
+        self.raw = bool(raw)
         self.K = np.loadtxt(os.path.join(self.folder, "K.txt")).astype(np.float32)
         self.poses = np.fromfile(os.path.join(self.folder, "poses.txt"), dtype=float, sep="\n ").reshape((-1, 4, 4))
         self.image_names = sorted(n for n in os.listdir(os.path.join(self.folder, "images")) if n.endswith(".png"))
@@ -32,10 +35,10 @@ class Scene:
         self.depth_names = sorted(n for n in os.listdir(depth_dir) if n.endswith(".png")) if os.path.isdir(depth_dir) else None
 
     def image(self, i):
-        return load_image(os.path.join(self.folder, "images", self.image_names[i]))
+        return (load_image_u8 if self.raw else load_image)(os.path.join(self.folder, "images", self.image_names[i]))
 
     def depth(self, i):
-        return load_depth_png(os.path.join(self.folder, "depth", self.depth_names[i]))
+        return (load_depth_png_u16 if self.raw else load_depth_png)(os.path.join(self.folder, "depth", self.depth_names[i]))
 
 
 def _to_device(image_hwc, device):
@@ -48,20 +51,29 @@ def _preprocessor(scene, raw_image):
                            perform_crop=Config.test_perform_crop)
 
 
+def _prepare(pre, raw, device, uploader):
+    """Network input [1,3,h,w] on the device: on the host (numpy, then a blocking copy) or, with an ``uploader``, from the raw 8-bit frame
+    in one kernel launch behind a pinned, non-blocking copy."""
+    if uploader is None:
+        return _to_device(pre.apply_rgb(raw, SCALE_RGB, MEAN_RGB, STD_RGB), device)
+    return pre.apply_rgb_device(raw, SCALE_RGB, MEAN_RGB, STD_RGB, device=device, uploader=uploader)
+
+
 def _run_frame(engine, scene, timer, device, reference_index, measurement_indices, evaluate, images=None, next_reference_index=None,
-               prepared=None, next_measurement_indices=None):
+               prepared=None, next_measurement_indices=None, uploader=None):
     """``next_reference_index``: the reference frame of the NEXT call when it is known (offline runs): its image is pre-processed now and
     handed to the engine as look-ahead (DepthEngine.step: its features are computed concurrently with this frame); ``prepared``
-    (a dict) carries the pre-processed device image to that next call."""
+    (a dict) carries the pre-processed device image to that next call.  ``uploader`` (a FrameUploader; ``scene`` then loads raw 8- / 16-bit
+    frames): images and the ground-truth depth are pre-processed on the device."""
     raw = images[reference_index] if images is not None and reference_index in images else scene.image(reference_index)
     pre = _preprocessor(scene, raw)
     ref_image = prepared.pop(reference_index, None) if prepared is not None else None
     if ref_image is None:
-        ref_image = _to_device(pre.apply_rgb(raw, SCALE_RGB, MEAN_RGB, STD_RGB), device)
+        ref_image = _prepare(pre, raw, device, uploader)
     next_image = None
     if next_reference_index is not None and prepared is not None:
         raw_next = images[next_reference_index] if images is not None and next_reference_index in images else scene.image(next_reference_index)
-        next_image = _to_device(_preprocessor(scene, raw_next).apply_rgb(raw_next, SCALE_RGB, MEAN_RGB, STD_RGB), device)
+        next_image = _prepare(_preprocessor(scene, raw_next), raw_next, device, uploader)
         prepared.clear()
         prepared[next_reference_index] = next_image
     ref_pose = torch.from_numpy(scene.poses[reference_index]).float().unsqueeze(0)   # poses / K stay on the host (engine.step)
@@ -72,8 +84,12 @@ def _run_frame(engine, scene, timer, device, reference_index, measurement_indice
             meas_images.append(None)     # features of this keyframe are cached: no need to load / pre-process the image again
         else:
             raw_m = images[m] if images is not None and m in images else scene.image(m)
-            meas_images.append(_to_device(pre.apply_rgb(raw_m, SCALE_RGB, MEAN_RGB, STD_RGB), device))
+            meas_images.append(_prepare(pre, raw_m, device, uploader))
         meas_poses.append(torch.from_numpy(scene.poses[m]).float().unsqueeze(0))
+    want_depth = bool(evaluate and scene.depth_names)
+    depth_on_device = None
+    if want_depth and uploader is not None:      # enqueued with the images, outside the timed region; fetched with the prediction
+        depth_on_device = pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader)
     timer.record_start_time()
     ahead = {}
     if next_image is not None:
@@ -85,16 +101,24 @@ def _run_frame(engine, scene, timer, device, reference_index, measurement_indice
     depth = engine.step(ref_image, ref_pose, meas_images, meas_poses, full_K, frame_id=reference_index,
                         measurement_ids=list(measurement_indices), **ahead)
     timer.record_end_time_and_elapsed_time()
+    if depth_on_device is not None:              # one transfer for both maps (same size: the network's)
+        both = torch.stack((depth.reshape(depth_on_device.shape[-2:]), depth_on_device[0])).cpu().numpy()
+        return both[0], both[1]
     prediction = depth.cpu().numpy().squeeze()
-    reference_depth = pre.apply_depth(scene.depth(reference_index)) if evaluate and scene.depth_names else None
+    reference_depth = pre.apply_depth(scene.depth(reference_index)) if want_depth else None
     return prediction, reference_depth
 
 
-def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, evaluate=True, max_frames=None, frame_log=None):
+def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, evaluate=True, max_frames=None, frame_log=None,
+                    device_preprocess=False):
     """Runs the lines of a keyframe index file ("ref meas1 meas2 ..." or "TRACKING LOST") through ``engine``.
-    ``frame_log`` (a list) receives the line each prediction belongs to: "ref meas1 ..." file names, or "TRACKING LOST"."""
-    scene = Scene(scene_folder)
+    ``frame_log`` (a list) receives the line each prediction belongs to: "ref meas1 ..." file names, or "TRACKING LOST".
+    ``device_preprocess``: frames are loaded as 8-bit images, uploaded through a ring of pinned buffers and cropped / resized / normalised
+    by one kernel launch each (dvmvs.hip.ops.preprocess_rgb; the ground-truth depth likewise, returned as float32) instead of by numpy
+    on the host.  Default False: the host path, unchanged."""
+    scene = Scene(scene_folder, raw=device_preprocess)
     device = engine.device
+    uploader = FrameUploader(device) if device_preprocess else None
     position = {name: i for i, name in enumerate(scene.image_names)}
     timer = InferenceTimer()
     predictions, reference_depths = [], []
@@ -112,18 +136,20 @@ def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, eval
         next_indices = [position[name] for name in upcoming.split(" ")] if upcoming is not None else None
         prediction, reference_depth = _run_frame(engine, scene, timer, device, indices[0], indices[1:], evaluate,
                                                  next_reference_index=next_indices[0] if next_indices else None, prepared=prepared,
-                                                 next_measurement_indices=next_indices[1:] if next_indices else None)
+                                                 next_measurement_indices=next_indices[1:] if next_indices else None, uploader=uploader)
         predictions.append(prediction)
         reference_depths.append(reference_depth)
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
 
 
-def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames=None, frame_log=None):
+def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames=None, frame_log=None, device_preprocess=False):
     """Feeds every frame of the scene to a KeyframeBuffer and predicts depth for the frames it accepts as keyframes.
     ``frame_log`` (a list) receives, in index-file syntax, what the buffer decided: one "ref meas1 ..." line per prediction and
-    "TRACKING LOST" where it cleared itself -- the lines simulate_keyframe_index would write for the same poses."""
-    scene = Scene(scene_folder)
+    "TRACKING LOST" where it cleared itself -- the lines simulate_keyframe_index would write for the same poses.
+    ``device_preprocess`` as in ``predict_offline``."""
+    scene = Scene(scene_folder, raw=device_preprocess)
     device = engine.device
+    uploader = FrameUploader(device) if device_preprocess else None
     buffer = KeyframeBuffer(buffer_size=Config.test_keyframe_buffer_size, keyframe_pose_distance=Config.test_keyframe_pose_distance,
                             optimal_t_score=Config.test_optimal_t_measure, optimal_R_score=Config.test_optimal_R_measure,
                             store_return_indices=True)
@@ -142,7 +168,7 @@ def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames
         measurement_indices = [frame[2] for frame in buffer.get_best_measurement_frames(Config.test_n_measurement_frames)]
         if frame_log is not None:
             frame_log.append(" ".join(scene.image_names[j] for j in [i] + measurement_indices))
-        prediction, reference_depth = _run_frame(engine, scene, timer, device, i, measurement_indices, evaluate)
+        prediction, reference_depth = _run_frame(engine, scene, timer, device, i, measurement_indices, evaluate, uploader=uploader)
         predictions.append(prediction)
         reference_depths.append(reference_depth)
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer

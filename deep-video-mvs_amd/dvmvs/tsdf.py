@@ -257,12 +257,16 @@ def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dat
 
 
 def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, scene_name, system_name, voxel_size, max_depth,
-        use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda"):
+        use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
-    loaders (no OpenCV)."""
-    from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, resize_nearest
+    loaders (no OpenCV).  ``device_preprocess`` (the switch the scene runners share): this program resamples its colour images with
+    nearest selection only and integrates them as 8-bit, so all the switch does here is keep them 8-bit from the decoder on
+    (``load_image_u8``: no float32 round trip); the values, and the meshes, are the same."""
+    from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, load_image_u8, resize_nearest
+    if device_preprocess:
+        load_image = load_image_u8       # resize_nearest only selects pixels: the uint8 values are those of the float path's astype
     scene_folder = os.path.join(data_folder, dataset_name, scene_name)
     original_K = np.loadtxt(os.path.join(scene_folder, "K.txt")).astype(np.float32)
     all_poses = np.fromfile(os.path.join(scene_folder, "poses.txt"), dtype=float, sep="\n ").reshape((-1, 4, 4))
@@ -347,6 +351,8 @@ def main(argv=None):
                         help="compute the volume bounds from the ground-truth depth maps (recommended when they are available)")
     parser.add_argument("--save_progressive", action="store_true", help="also write the mesh after every fused keyframe")
     parser.add_argument("--save_groundtruth", action="store_true", help="also write the reconstruction from the ground-truth depth maps")
+    parser.add_argument("--device-preprocess", dest="device_preprocess", action="store_true",
+                        help="load the colour images as 8-bit (no float32 round trip); same meshes")
     args = parser.parse_args(argv)
     run(**vars(args))
 

@@ -43,7 +43,9 @@ extern "C" {
  * ABI 10 = ABI 9 + the RGB SAD sweep of the MVDepthNet / GP-MVS baselines (dvmvs_rgb_sweep_fwd) and GP-MVS's filter step
  * (dvmvs_gp_filter_step); no earlier signature changed.
  * ABI 11 = ABI 10 + the DPSNet baseline's plane volume (dvmvs_dps_volume_fwd) and its up-sampling soft-argmin (dvmvs_dps_regress_fwd);
- * no earlier signature changed. */
+ * no earlier signature changed.
+ * ABI 11, later addition: dvmvs_preprocess_* (frame pre-processing on the device); no earlier signature changed.  The number stays 11:
+ * a library built before the addition reports the same version and simply lacks the two symbols, which a binding must check for. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -531,6 +533,39 @@ int dvmvs_dps_volume_fwd(const float* ref, const float* meas, const float* pose,
                          int B, int C, int h, int w, int nlabel, double mindepth, dvmvs_stream_t stream);
 int dvmvs_dps_regress_fwd(const float* costs, float* depth, float* pred, int B, int nlabel, int h, int w, int H, int W,
                           double mindepth, dvmvs_stream_t stream);
+
+/*
+ * Frame pre-processing (ABI 11, later addition): dvmvs/dataset_loader.py's PreprocessImage.apply_rgb / apply_depth on the camera's raw
+ * 8-bit frames and 16-bit depth maps, one launch per call for N frames.
+ *
+ * dvmvs_preprocess_rgb_fwd: centre crop, bilinear resampling (half-pixel centres, clamped edges, no anti-aliasing: resize_bilinear),
+ * optional colour normalisation, HWC -> CHW.
+ *   src   uint8 [N,H,W,3] interleaved RGB; row y of frame n starts at src + (n * H + y) * src_row_stride bytes (src_row_stride >= 3 W)
+ *   dst   fp32 [N,3,new_h,new_w]; frame n starts at dst + n * dst_batch_stride elements (>= 3 new_h new_w: a slot of a larger buffer),
+ *         its three planes are dense; 16-byte stores when new_w % 4 == 0 and dst and the stride are 16-byte aligned, scalar stores otherwise
+ *   crop_x, crop_y   columns / rows dropped on EACH side before resampling (PreprocessImage.crop_x / crop_y); w = W - 2 crop_x, h likewise
+ *   normalize  1: (v / scale - mean_host[c]) / std_host[c] with fp32(scale) and the two HOST arrays of 3 floats; 0: the resampled
+ *              0..255 values (scale, mean_host, std_host are not read and may be null)
+ * Arithmetic contract: xs = max((x + 0.5) * (w / new_w) - 0.5, 0), x0 = min(floor(xs), w - 1), x1 = min(x0 + 1, w - 1),
+ * fx = fp32(xs - x0) in DOUBLE, rows likewise: tap indices and weights are bit-identical to the host function's.  Then in fp32, every
+ * operation rounded (no FMA contraction), in the host's order: top = a (1 - fx) + b fx; bottom likewise; top (1 - fy) + bottom fy;
+ * / scale; - mean; / std, with correctly rounded divisions.
+ *
+ * dvmvs_preprocess_depth_fwd: crop, nearest resampling (source index min(int(x * (w / (double)new_w)), w - 1): resize_nearest), and
+ * fp32((double)d / scaling): the fp32 rounding of load_depth_png + apply_depth.
+ *   src   uint16 [N,H,W] dense      dst   fp32 [N,new_h,new_w] dense
+ *
+ * Both return DVMVS_EINVAL for a null src / dst, N < 1, a non-positive size, a negative crop or one that leaves no pixels, a row or
+ * batch stride smaller than a row / an output frame, normalize not 0 / 1, and -- with normalize = 1 -- a null mean_host / std_host,
+ * fp32(scale) == 0 or a std_host[c] == 0; scaling == 0.  DVMVS_EUNSUPPORTED for N > 65535 or a frame whose offsets do not fit the
+ * kernels' 32-bit indices: src_row_stride or H * src_row_stride >= 2^31 bytes, 3 new_h new_w >= 2^31 elements, dst_batch_stride >= 2^40
+ * elements (depth: H W or new_h new_w >= 2^31).
+ */
+int dvmvs_preprocess_rgb_fwd(const unsigned char* src, float* dst, int N, int H, int W, long long src_row_stride, int crop_x, int crop_y,
+                             int new_h, int new_w, long long dst_batch_stride, double scale, const float* mean_host,
+                             const float* std_host, int normalize, dvmvs_stream_t stream);
+int dvmvs_preprocess_depth_fwd(const unsigned short* src, float* dst, int N, int H, int W, int crop_x, int crop_y, int new_h, int new_w,
+                               double scaling, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
