@@ -27,7 +27,7 @@ from dvmvs.baselines.gpmvs.gplayer import GPlayer
 from dvmvs.dataset_loader import FrameUploader, PreprocessImage
 from dvmvs.hip import ops
 from dvmvs.pose_algebra import sweep_matrices_host
-from dvmvs.runner import Scene
+from dvmvs.runner import DeviceEvaluation, Scene, _finish_on_device
 from dvmvs.utils import InferenceTimer, pose_distance
 
 WIDTH, HEIGHT = 320, 256
@@ -226,14 +226,30 @@ def _reference_depth(pre, scene, reference_index, device, uploader):
     return pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader)[0].cpu().numpy()
 
 
-def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess=False):
+def _device_evaluation(device, scene, lines, evaluate, device_preprocess):
+    return DeviceEvaluation(device, evaluate and scene.depth_names, device_preprocess, capacity=sum(l != "TRACKING LOST" for l in lines))
+
+
+def _evaluation_slot(evaluation, pre, scene, reference_index, device, uploader):
+    """The frame's slot of the device stack, its ground truth enqueued (dvmvs.runner.DeviceEvaluation)."""
+    slot = evaluation.next_slot(pre.new_height, pre.new_width)
+    if evaluation.with_depth and uploader is not None:
+        pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader, out=slot.gt.unsqueeze(0))
+    elif evaluation.with_depth:
+        evaluation.stage(slot, pre.apply_depth(scene.depth(reference_index)))
+    return slot
+
+
+def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess=False, device_evaluate=False,
+             error_log=None):
     scene = Scene(scene_folder, raw=device_preprocess)
     device = frame.device
     uploader = FrameUploader(device) if device_preprocess else None
     rgb = (SCALE_RGB, MEAN_RGB, STD_RGB)
     position = {name: i for i, name in enumerate(scene.image_names)}
     lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
-    timer = InferenceTimer()
+    timer = InferenceTimer(deferred=device_evaluate)
+    evaluation = _device_evaluation(device, scene, lines, evaluate, device_preprocess) if device_evaluate else None
     predictions, reference_depths = [], []
     previous_index = None
     if frame.gp is not None:
@@ -257,32 +273,42 @@ def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, dev
                 if previous_index is None:
                     previous_index = measurement_indices[-1]     # the reference's leaked loop variable
                 dt = pose_distance(scene.poses[reference_index], scene.poses[previous_index])[0]
+            slot = _evaluation_slot(evaluation, pre, scene, reference_index, device, uploader) if evaluation is not None else None
             timer.record_start_time()
             depth = frame(reference_image, measurement_images, reference_pose, measurement_poses, K, dt=dt)
             timer.record_end_time_and_elapsed_time()
-            predictions.append(depth.cpu().numpy().squeeze())
             previous_index = reference_index
-            if evaluate and scene.depth_names:
-                reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
+            if evaluation is not None:           # prediction, ground truth and metrics stay on the device: nothing waits here
+                evaluation.commit(slot, depth)
+            else:
+                predictions.append(depth.cpu().numpy().squeeze())
+                if evaluate and scene.depth_names:
+                    reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
+    if evaluation is not None:
+        return _finish_on_device(evaluation, timer, error_log)
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
 
 
 def predict_mvdepthnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
-                       device_preprocess=False):
+                       device_preprocess=False, device_evaluate=False, error_log=None):
     """MVDepthNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
     ``device_preprocess``: raw 8-bit frames are uploaded through a pinned ring and pre-processed by dvmvs.hip.ops.preprocess_rgb (the
-    ground-truth depth by preprocess_depth, float32) instead of by numpy on the host."""
+    ground-truth depth by preprocess_depth, float32) instead of by numpy on the host.
+    ``device_evaluate``: predictions, ground truth and their eight error metrics (one dvmvs.hip.ops.depth_errors launch per frame) stay on
+    the device until the scene is done, the timer is the deferred one, and one download fetches everything; ``error_log`` (a list)
+    receives a float32 [8] row per prediction for ``save_results(..., errors=error_log)`` (dvmvs.runner.predict_offline)."""
     encoder, decoder = build_mvdepthnet(weights_folder, device)
-    return _predict(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess)
+    return _predict(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess,
+                    device_evaluate, error_log)
 
 
 def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
-                  device_preprocess=False):
+                  device_preprocess=False, device_evaluate=False, error_log=None):
     """GP-MVS over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
-    ``device_preprocess`` as in ``predict_mvdepthnet``."""
+    ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_mvdepthnet``."""
     encoder, decoder, gplayer = build_gpmvs(weights_folder, device)
     frame = BaselineFrame(encoder, decoder, device, gp=GPFilter.from_gplayer(gplayer))
-    return _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess)
+    return _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess, device_evaluate, error_log)
 
 
 def dpsnet_relative_pose(reference_pose, measurement_pose):
@@ -291,15 +317,16 @@ def dpsnet_relative_pose(reference_pose, measurement_pose):
 
 
 def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
-                   device_preprocess=False):
+                   device_preprocess=False, device_evaluate=False, error_log=None):
     """DPSNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
-    ``device_preprocess`` as in ``predict_mvdepthnet``."""
+    ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_mvdepthnet``."""
     dpsnet = build_dpsnet(weights_folder, device)
     scene = Scene(scene_folder, raw=device_preprocess)
     uploader = FrameUploader(device) if device_preprocess else None
     position = {name: i for i, name in enumerate(scene.image_names)}
     lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
-    timer = InferenceTimer()
+    timer = InferenceTimer(deferred=device_evaluate)
+    evaluation = _device_evaluation(torch.device(device), scene, lines, evaluate, device_preprocess) if device_evaluate else None
     predictions, reference_depths = [], []
     with torch.no_grad():
         for line in lines:
@@ -317,18 +344,24 @@ def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evalu
             camera_k = pre.get_updated_intrinsics()
             K = torch.from_numpy(camera_k).float().unsqueeze(0).to(device)
             K_inv = torch.from_numpy(np.linalg.inv(camera_k)).float().unsqueeze(0).to(device)
+            slot = _evaluation_slot(evaluation, pre, scene, reference_index, device, uploader) if evaluation is not None else None
             timer.record_start_time()
             _, prediction = dpsnet(reference_image, measurement_images, poses, K, K_inv)
             timer.record_end_time_and_elapsed_time()
-            predictions.append(prediction.cpu().numpy().squeeze())
-            if evaluate and scene.depth_names:
-                reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
+            if evaluation is not None:
+                evaluation.commit(slot, prediction)
+            else:
+                predictions.append(prediction.cpu().numpy().squeeze())
+                if evaluate and scene.depth_names:
+                    reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
+    if evaluation is not None:
+        return _finish_on_device(evaluation, timer, error_log)
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
 
 
 def main(method, argv=None):
     """``python -m dvmvs.baselines.{mvdepthnet,gpmvs,dpsnet} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]
-    [--device-preprocess]``."""
+    [--device-preprocess] [--device-evaluate]``."""
     import argparse
     from dvmvs.utils import save_results
     parser = argparse.ArgumentParser(prog=f"python -m dvmvs.baselines.{method}")
@@ -340,12 +373,17 @@ def main(method, argv=None):
     parser.add_argument("--max-frames", type=int, default=None)
     parser.add_argument("--device-preprocess", action="store_true",
                         help="crop / resize / normalise the raw 8-bit frames on the GPU (one launch per image) instead of with numpy")
+    parser.add_argument("--device-evaluate", action="store_true",
+                        help="keep predictions and ground truth on the GPU and evaluate the error metrics there (one launch per frame, one "
+                             "download per scene) instead of fetching every frame and evaluating with numpy")
     args = parser.parse_args(argv)
     predict = {"mvdepthnet": predict_mvdepthnet, "gpmvs": predict_gpmvs, "dpsnet": predict_dpsnet}[method]
     size = (DPS_WIDTH, DPS_HEIGHT) if method == "dpsnet" else (WIDTH, HEIGHT)
+    error_log = []
     predictions, reference_depths, timer = predict(args.scene_folder, args.keyframe_index_file, args.weights, max_frames=args.max_frames,
-                                                  device_preprocess=args.device_preprocess)
+                                                  device_preprocess=args.device_preprocess, device_evaluate=args.device_evaluate,
+                                                  error_log=error_log)
     timer.print_statistics()
-    save_results(predictions=predictions, groundtruths=reference_depths,
+    save_results(predictions=predictions, groundtruths=reference_depths, errors=error_log if args.device_evaluate else None,
                  system_name=system_name(method, args.keyframe_index_file, finetuned=not args.without_ft, size=size),
                  scene_name=_index_file_fields(args.keyframe_index_file)[2], save_folder=args.out)

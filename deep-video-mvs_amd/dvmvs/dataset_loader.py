@@ -186,10 +186,11 @@ class PreprocessImage:
         return ops.preprocess_rgb(raw, self.crop_x, self.crop_y, self.new_height, self.new_width, scale_rgb, mean_rgb, std_rgb,
                                   normalize=normalize_colors, out=out)
 
-    def apply_depth_device(self, depth_u16, scaling=1000.0, device=None, uploader=None):
+    def apply_depth_device(self, depth_u16, scaling=1000.0, device=None, uploader=None, out=None):
         """``apply_depth(load_depth_png(...))`` of a raw 16-bit depth map (millimetres) as one kernel launch: float32
         [1,new_height,new_width] in metres on the device, equal to the host result after ``astype(float32)``.  ``depth_u16``: a numpy
-        uint16 [H,W] (or [N,H,W]), or a host or device tensor (``torch.uint16``, or ``int16`` holding the same bits)."""
+        uint16 [H,W] (or [N,H,W]), or a host or device tensor (``torch.uint16``, or ``int16`` holding the same bits).  ``out`` as in
+        ``ops.preprocess_depth``."""
         from dvmvs.hip import ops
         if isinstance(depth_u16, torch.Tensor) and depth_u16.device.type != "cpu":
             raw = depth_u16
@@ -201,7 +202,7 @@ class PreprocessImage:
             else:
                 host = torch.from_numpy(np.array(depth_u16).view(np.int16))
             raw = host.to(torch.device("cuda") if device is None else device)
-        return ops.preprocess_depth(raw, self.crop_x, self.crop_y, self.new_height, self.new_width, scaling=scaling)
+        return ops.preprocess_depth(raw, self.crop_x, self.crop_y, self.new_height, self.new_width, scaling=scaling, out=out)
 
     def get_updated_intrinsics(self):
         return np.array([[self.fx, 0, self.cx], [0, self.fy, self.cy], [0, 0, 1]])

@@ -21,3 +21,12 @@ def compute_errors(gt, pred, max_depth=np.inf):
             np.mean(np.square(diff) / gt),
             np.sqrt(np.mean(np.square(diff))),
             *thresholds)
+
+
+def compute_errors_device(gt, pred, max_depth=np.inf):
+    """``compute_errors`` for depth maps that live on the GPU, as one kernel launch (dvmvs.hip.ops.depth_errors): float32 tensors
+    [H,W] -> a float32 device tensor [8]; [N,H,W] or [N,1,H,W] -> [N,8].  Same per-pixel float32 terms as ``compute_errors``, summed in
+    float64 on the device; nothing is copied to the host."""
+    from dvmvs.hip import ops      # (imported here: this module stays importable, and compute_errors usable, without a GPU)
+    rows = ops.depth_errors(gt, pred, max_depth=max_depth)
+    return rows[0] if gt.dim() == 2 else rows

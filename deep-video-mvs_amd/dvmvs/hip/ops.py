@@ -16,7 +16,7 @@ from dvmvs.hip import _capi
 
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
            "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress", "preprocess_rgb",
-           "preprocess_depth"]
+           "preprocess_depth", "depth_errors"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1266,4 +1266,77 @@ def preprocess_depth(raw: Tensor, crop_x: int, crop_y: int, new_height: int, new
         rc = _capi.lib().dvmvs_preprocess_depth_fwd(_ptr(raw), _ptr(out), N, H, W, crop_x, crop_y, new_height, new_width, float(scaling),
                                                     _stream(raw))
     _capi.check(rc, "dvmvs_preprocess_depth_fwd")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# depth evaluation: the eight metrics of dvmvs.errors.compute_errors for N frames, one launch (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+_error_workspaces = {}
+
+
+def depth_errors_workspace(device, n_frames, pixels):
+    """Persistent workspace of ``depth_errors`` for (device, N, pixels): zero-filled once here; every call leaves its ticket words zero
+    (contract in include/dvmvs_hip.h).  As with ``sweep_workspace``, calls that share it must be ordered with respect to each other (one
+    stream per process); allocated outside any graph capture when the first (eager / warm-up) call of a size happens."""
+    device = torch.device(device)
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    key = (index, n_frames, pixels)
+    workspace = _error_workspaces.get(key)
+    if workspace is None:
+        nbytes = _capi.lib().dvmvs_depth_errors_workspace_bytes(n_frames, pixels)
+        if nbytes == 0:
+            _capi.check(EUNSUPPORTED, "dvmvs_depth_errors_workspace_bytes")
+        workspace = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=device)
+        _error_workspaces[key] = workspace
+    return workspace
+
+
+def _frames_2d(name, t):
+    """[H,W], [N,H,W] or [N,1,H,W] -> (N, pixels)."""
+    if t.dim() == 2:
+        return 1, t.shape[0] * t.shape[1]
+    if t.dim() == 3:
+        return t.shape[0], t.shape[1] * t.shape[2]
+    if t.dim() == 4 and t.shape[1] == 1:
+        return t.shape[0], t.shape[2] * t.shape[3]
+    raise ValueError(f"dvmvs::{name}: expected depth maps [H,W], [N,H,W] or [N,1,H,W], got {tuple(t.shape)}")
+
+
+def depth_errors(gt: Tensor, pred: Tensor, max_depth: float = float("inf"), out: Optional[Tensor] = None,
+                 counts: Optional[Tensor] = None) -> Tensor:
+    """``dvmvs.errors.compute_errors`` on the device, one launch for all frames: ``gt`` and ``pred`` float32 depth maps [H,W], [N,H,W] or
+    [N,1,H,W] on the GPU -> float32 [N,8] (abs_error, abs_relative_error, abs_inverse_error, squared_relative_error, rmse, ratio_125,
+    ratio_125_2, ratio_125_3) over the pixels with ``0.5 <= gt <= max_depth``; a frame without such a pixel gives eight NaNs.  The
+    per-pixel terms are the host function's fp32 operations; they are summed in float64 in a fixed order, so a row is the float32
+    rounding of the exact mean, bit-identical run to run and for any batch size or alignment (include/dvmvs_hip.h).  ``out``: a
+    contiguous float32 [N,8] tensor (e.g. rows of a larger table), returned; ``counts``: a contiguous int32 [N,4] tensor that receives n
+    and the three inlier counts.  Runs on the current stream, without allocation once the workspace of this size exists."""
+    if gt.device.type != "cuda" or pred.device.type != "cuda":
+        _no_cpu("depth_errors")
+    if gt.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise ValueError(f"dvmvs::depth_errors: expected float32 depth maps, got {gt.dtype} and {pred.dtype}")
+    N, pixels = _frames_2d("depth_errors", gt)
+    if _frames_2d("depth_errors", pred) != (N, pixels) or tuple(gt.shape[-2:]) != tuple(pred.shape[-2:]) or gt.device != pred.device:
+        raise ValueError(f"dvmvs::depth_errors: gt {tuple(gt.shape)} on {gt.device} and pred {tuple(pred.shape)} on {pred.device} differ")
+    if N < 1 or pixels < 1:
+        raise ValueError(f"dvmvs::depth_errors: expected non-empty depth maps, got {tuple(gt.shape)}")
+    max_depth = float(max_depth)
+    if max_depth != max_depth:
+        raise ValueError("dvmvs::depth_errors: max_depth is NaN")
+    gt, pred = gt.contiguous(), pred.contiguous()
+    if out is None:
+        out = torch.empty((N, 8), dtype=torch.float32, device=gt.device)
+    elif out.device != gt.device or out.dtype != torch.float32 or tuple(out.shape) != (N, 8) or not out.is_contiguous():
+        raise ValueError(f"dvmvs::depth_errors: out must be a contiguous float32 [{N},8] tensor on {gt.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    if counts is not None and (counts.device != gt.device or counts.dtype != torch.int32 or tuple(counts.shape) != (N, 4)
+                               or not counts.is_contiguous()):
+        raise ValueError(f"dvmvs::depth_errors: counts must be a contiguous int32 [{N},4] tensor on {gt.device}, got {counts.dtype} "
+                         f"{tuple(counts.shape)} on {counts.device}")
+    workspace = depth_errors_workspace(gt.device, N, pixels)
+    with torch.cuda.device(gt.device):
+        rc = _capi.lib().dvmvs_depth_errors_fwd(_ptr(gt), _ptr(pred), N, pixels, max_depth, _ptr(out),
+                                                _ptr(counts) if counts is not None else None, _ptr(workspace), _stream(gt))
+    _capi.check(rc, "dvmvs_depth_errors_fwd")
     return out

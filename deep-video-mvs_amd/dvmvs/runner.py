@@ -59,12 +59,81 @@ def _prepare(pre, raw, device, uploader):
     return pre.apply_rgb_device(raw, SCALE_RGB, MEAN_RGB, STD_RGB, device=device, uploader=uploader)
 
 
+class DeviceEvaluation:
+    """Predictions, ground-truth depths and their error metrics kept on the device while a scene runs (``device_evaluate=True``), so that
+    no frame waits for a transfer: per prediction a slot of a pre-sized block -- the prediction copied device-to-device on the current
+    stream (the engine's output buffer is static: the next frame overwrites it), the ground truth next to it, and one
+    dvmvs.hip.ops.depth_errors launch that writes the frame's row of the block's metric table (max_depth = inf, save_results' default).
+    A block is ONE float32 buffer (predictions, ground truths, table), fetched with one copy by ``finish``; a runner that does not know
+    its number of predictions in advance gets further blocks of ``capacity`` slots as it goes.  The ground truth is either written into
+    its slot by the device pre-processing (``slot.gt`` as ``out=``) or, when it was pre-processed on the host, sent through a pinned
+    staging ring (``stage``: float32 on the device for the metrics; the host array itself is what ``finish`` returns)."""
+
+    class Slot:
+        def __init__(self, block, index):
+            self.pred, self.row = block["preds"][index], block["table"][index:index + 1]
+            self.gt = block["gts"][index] if block["gts"] is not None else None
+            self.staged = None
+
+    def __init__(self, device, with_depth, gt_on_device, capacity):
+        self.device = torch.device(device)
+        self.with_depth, self.gt_on_device, self.capacity = bool(with_depth), bool(gt_on_device), max(int(capacity), 1)
+        self.blocks, self.count, self.host_gts = [], 0, []
+        self.stager = FrameUploader(self.device) if self.with_depth and not self.gt_on_device else None
+
+    def next_slot(self, height, width):
+        index = self.count % self.capacity
+        if index == 0:
+            frame, n = height * width, self.capacity
+            maps = 2 if self.with_depth and self.gt_on_device else 1
+            buffer = torch.empty(n * (maps * frame + 8), dtype=torch.float32, device=self.device)
+            self.blocks.append({"buffer": buffer, "frame": frame, "shape": (height, width), "maps": maps,
+                                "preds": buffer[:n * frame].view(n, height, width),
+                                "gts": buffer[n * frame:2 * n * frame].view(n, height, width) if maps == 2 else None,
+                                "table": buffer[maps * n * frame:].view(n, 8)})
+        block = self.blocks[-1]
+        if block["shape"] != (height, width):
+            raise ValueError(f"device evaluation: a {height}x{width} frame in a scene of {block['shape'][0]}x{block['shape'][1]} frames")
+        return DeviceEvaluation.Slot(block, index)
+
+    def stage(self, slot, host_depth):
+        """Ground truth pre-processed on the host: kept as it is for the caller, and sent (as float32, without a blocking copy) for the metrics."""
+        self.host_gts.append(host_depth)
+        flat = self.stager.upload(np.ascontiguousarray(host_depth, dtype=np.float32))
+        slot.staged = flat.view(torch.float32).view(tuple(host_depth.shape))
+
+    def commit(self, slot, depth):
+        from dvmvs.hip import ops
+        slot.pred.copy_(depth.reshape(slot.pred.shape), non_blocking=True)
+        if self.with_depth:
+            ops.depth_errors(slot.staged if slot.staged is not None else slot.gt, slot.pred, out=slot.row)
+        self.count += 1
+
+    def finish(self, error_log=None):
+        """(predictions, ground truths or None) as lists of numpy arrays; ``error_log`` receives the float32 [8] rows.  One download per block."""
+        predictions, gts, left = [], [], self.count
+        for block in self.blocks:
+            n, used = self.capacity, min(left, self.capacity)
+            left -= used
+            host = block["buffer"].cpu().numpy()
+            frame, shape, maps = block["frame"], block["shape"], block["maps"]
+            predictions.extend(host[:n * frame].reshape((n,) + shape)[:used])
+            if maps == 2:
+                gts.extend(host[n * frame:2 * n * frame].reshape((n,) + shape)[:used])
+            if self.with_depth and error_log is not None:
+                error_log.extend(host[maps * n * frame:].reshape(n, 8)[:used].copy())
+        if not self.with_depth:
+            return predictions, None
+        return predictions, (gts if self.gt_on_device else self.host_gts)
+
+
 def _run_frame(engine, scene, timer, device, reference_index, measurement_indices, evaluate, images=None, next_reference_index=None,
-               prepared=None, next_measurement_indices=None, uploader=None):
+               prepared=None, next_measurement_indices=None, uploader=None, evaluation=None):
     """``next_reference_index``: the reference frame of the NEXT call when it is known (offline runs): its image is pre-processed now and
     handed to the engine as look-ahead (DepthEngine.step: its features are computed concurrently with this frame); ``prepared``
     (a dict) carries the pre-processed device image to that next call.  ``uploader`` (a FrameUploader; ``scene`` then loads raw 8- / 16-bit
-    frames): images and the ground-truth depth are pre-processed on the device."""
+    frames): images and the ground-truth depth are pre-processed on the device.  ``evaluation`` (a DeviceEvaluation): the prediction, the
+    ground truth and their metrics stay on the device, nothing here waits for it, and (None, None) is returned."""
     raw = images[reference_index] if images is not None and reference_index in images else scene.image(reference_index)
     pre = _preprocessor(scene, raw)
     ref_image = prepared.pop(reference_index, None) if prepared is not None else None
@@ -88,7 +157,14 @@ def _run_frame(engine, scene, timer, device, reference_index, measurement_indice
         meas_poses.append(torch.from_numpy(scene.poses[m]).float().unsqueeze(0))
     want_depth = bool(evaluate and scene.depth_names)
     depth_on_device = None
-    if want_depth and uploader is not None:      # enqueued with the images, outside the timed region; fetched with the prediction
+    slot = None
+    if evaluation is not None:                   # the frame's slot; its ground truth is enqueued with the images, outside the timed region
+        slot = evaluation.next_slot(pre.new_height, pre.new_width)
+        if want_depth and uploader is not None:
+            pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader, out=slot.gt.unsqueeze(0))
+        elif want_depth:
+            evaluation.stage(slot, pre.apply_depth(scene.depth(reference_index)))
+    elif want_depth and uploader is not None:      # enqueued with the images, outside the timed region; fetched with the prediction
         depth_on_device = pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader)
     timer.record_start_time()
     ahead = {}
@@ -101,6 +177,9 @@ def _run_frame(engine, scene, timer, device, reference_index, measurement_indice
     depth = engine.step(ref_image, ref_pose, meas_images, meas_poses, full_K, frame_id=reference_index,
                         measurement_ids=list(measurement_indices), **ahead)
     timer.record_end_time_and_elapsed_time()
+    if evaluation is not None:
+        evaluation.commit(slot, depth)
+        return None, None
     if depth_on_device is not None:              # one transfer for both maps (same size: the network's)
         both = torch.stack((depth.reshape(depth_on_device.shape[-2:]), depth_on_device[0])).cpu().numpy()
         return both[0], both[1]
@@ -109,21 +188,36 @@ def _run_frame(engine, scene, timer, device, reference_index, measurement_indice
     return prediction, reference_depth
 
 
+def _finish_on_device(evaluation, timer, error_log):
+    predictions, reference_depths = evaluation.finish(error_log)
+    timer.resolve()
+    return predictions, reference_depths, timer
+
+
 def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, evaluate=True, max_frames=None, frame_log=None,
-                    device_preprocess=False):
+                    device_preprocess=False, device_evaluate=False, error_log=None):
     """Runs the lines of a keyframe index file ("ref meas1 meas2 ..." or "TRACKING LOST") through ``engine``.
     ``frame_log`` (a list) receives the line each prediction belongs to: "ref meas1 ..." file names, or "TRACKING LOST".
     ``device_preprocess``: frames are loaded as 8-bit images, uploaded through a ring of pinned buffers and cropped / resized / normalised
     by one kernel launch each (dvmvs.hip.ops.preprocess_rgb; the ground-truth depth likewise, returned as float32) instead of by numpy
-    on the host.  Default False: the host path, unchanged."""
+    on the host.  Default False: the host path, unchanged.
+    ``device_evaluate``: predictions are kept on the device (copied out of the engine's output buffer on its stream), the ground truth goes
+    up without a blocking copy, one dvmvs.hip.ops.depth_errors launch per frame writes its eight metrics into a device table, the timer
+    is the deferred one, and nothing waits for the device inside the loop; ONE download after it fetches everything (DeviceEvaluation).
+    ``error_log`` (a list) then receives one float32 [8] row per prediction (``save_results(..., errors=error_log)``); it stays empty
+    without ground truth or with ``evaluate=False``.  Default False: today's path, unchanged."""
     scene = Scene(scene_folder, raw=device_preprocess)
     device = engine.device
     uploader = FrameUploader(device) if device_preprocess else None
     position = {name: i for i, name in enumerate(scene.image_names)}
-    timer = InferenceTimer()
+    timer = InferenceTimer(deferred=device_evaluate)
     predictions, reference_depths = [], []
     engine.new_sequence()
     lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
+    evaluation = None
+    if device_evaluate:
+        evaluation = DeviceEvaluation(device, evaluate and scene.depth_names, device_preprocess,
+                                      capacity=sum(l != "TRACKING LOST" for l in lines))
     prepared = {}      # the next keyframe's pre-processed image (the index file says which frame that is: feature look-ahead)
     for n, line in enumerate(lines):
         if frame_log is not None:
@@ -136,24 +230,31 @@ def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, eval
         next_indices = [position[name] for name in upcoming.split(" ")] if upcoming is not None else None
         prediction, reference_depth = _run_frame(engine, scene, timer, device, indices[0], indices[1:], evaluate,
                                                  next_reference_index=next_indices[0] if next_indices else None, prepared=prepared,
-                                                 next_measurement_indices=next_indices[1:] if next_indices else None, uploader=uploader)
-        predictions.append(prediction)
-        reference_depths.append(reference_depth)
+                                                 next_measurement_indices=next_indices[1:] if next_indices else None, uploader=uploader,
+                                                 evaluation=evaluation)
+        if evaluation is None:
+            predictions.append(prediction)
+            reference_depths.append(reference_depth)
+    if evaluation is not None:
+        return _finish_on_device(evaluation, timer, error_log)
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
 
 
-def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames=None, frame_log=None, device_preprocess=False):
+def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames=None, frame_log=None, device_preprocess=False,
+                   device_evaluate=False, error_log=None):
     """Feeds every frame of the scene to a KeyframeBuffer and predicts depth for the frames it accepts as keyframes.
     ``frame_log`` (a list) receives, in index-file syntax, what the buffer decided: one "ref meas1 ..." line per prediction and
     "TRACKING LOST" where it cleared itself -- the lines simulate_keyframe_index would write for the same poses.
-    ``device_preprocess`` as in ``predict_offline``."""
+    ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_offline``; the number of predictions is not known in
+    advance here, so the device stack grows in blocks of 32 frames."""
     scene = Scene(scene_folder, raw=device_preprocess)
     device = engine.device
     uploader = FrameUploader(device) if device_preprocess else None
+    evaluation = DeviceEvaluation(device, evaluate and scene.depth_names, device_preprocess, capacity=32) if device_evaluate else None
     buffer = KeyframeBuffer(buffer_size=Config.test_keyframe_buffer_size, keyframe_pose_distance=Config.test_keyframe_pose_distance,
                             optimal_t_score=Config.test_optimal_t_measure, optimal_R_score=Config.test_optimal_R_measure,
                             store_return_indices=True)
-    timer = InferenceTimer()
+    timer = InferenceTimer(deferred=device_evaluate)
     predictions, reference_depths = [], []
     engine.new_sequence()
     n = len(scene.poses) if max_frames is None else min(max_frames, len(scene.poses))
@@ -168,9 +269,13 @@ def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames
         measurement_indices = [frame[2] for frame in buffer.get_best_measurement_frames(Config.test_n_measurement_frames)]
         if frame_log is not None:
             frame_log.append(" ".join(scene.image_names[j] for j in [i] + measurement_indices))
-        prediction, reference_depth = _run_frame(engine, scene, timer, device, i, measurement_indices, evaluate, uploader=uploader)
-        predictions.append(prediction)
-        reference_depths.append(reference_depth)
+        prediction, reference_depth = _run_frame(engine, scene, timer, device, i, measurement_indices, evaluate, uploader=uploader,
+                                                 evaluation=evaluation)
+        if evaluation is None:
+            predictions.append(prediction)
+            reference_depths.append(reference_depth)
+    if evaluation is not None:
+        return _finish_on_device(evaluation, timer, error_log)
     return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
 
 

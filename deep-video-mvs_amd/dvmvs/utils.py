@@ -226,10 +226,17 @@ def print_number_of_trainable_parameters(optimizer):
 # ----------------------------------------------------------------------------------------------------------------------
 # inference helpers
 # ----------------------------------------------------------------------------------------------------------------------
-def save_results(predictions, groundtruths, system_name, scene_name, save_folder, max_depth=np.inf):
+def save_results(predictions, groundtruths, system_name, scene_name, save_folder, max_depth=np.inf, errors=None):
+    """``errors``: one row of eight metrics per prediction, already evaluated (the ``error_log`` of a runner called with
+    ``device_evaluate=True``): printed and saved instead of being recomputed from ``groundtruths``; same file, same layout."""
     from dvmvs.errors import compute_errors
     if groundtruths is not None:
-        errors = np.array([compute_errors(groundtruths[i], p, max_depth) for i, p in enumerate(predictions)])
+        if errors is None:
+            errors = np.array([compute_errors(groundtruths[i], p, max_depth) for i, p in enumerate(predictions)])
+        else:
+            errors = np.array(errors)
+            if errors.shape != (len(predictions), 8):
+                raise ValueError(f"save_results: expected one row of 8 metrics per prediction, got {errors.shape} for {len(predictions)}")
         names = ["abs_error", "abs_relative_error", "abs_inverse_error", "squared_relative_error", "rmse", "ratio_125",
                  "ratio_125_2", "ratio_125_3"]
         print("Metrics of {} for scene {}:".format(system_name, scene_name))
@@ -249,20 +256,38 @@ def visualize_predictions(*args, **kwargs):
 
 
 class InferenceTimer:
-    """HIP-event timer around the per-frame forward; same statistics as the reference (first ``n_skip`` dropped)."""
+    """HIP-event timer around the per-frame forward; same statistics as the reference (first ``n_skip`` dropped).
+    ``deferred=True``: every frame gets its own pair of events, ``record_end_time_and_elapsed_time`` only records (it does not wait for
+    the device), and ``times`` is filled in on first use -- by ``statistics()`` / ``print_statistics()``, by reading ``times``, or by an
+    explicit ``resolve()``, which waits for the last recorded frame."""
 
-    def __init__(self, n_skip=20):
-        self.times = []
+    def __init__(self, n_skip=20, deferred=False):
+        self._times = []
         self.n_skip = n_skip
+        self.deferred = bool(deferred)
+        self._pending = []       # deferred: (start, end) event pairs not yet turned into milliseconds
         # a stop-watch, not a compute path: without a GPU (the multi-process CPU tests drive the runners with a stub engine)
         # it measures host wall-clock milliseconds instead of HIP events
         self.on_gpu = torch.cuda.is_available()
-        if self.on_gpu:
+        if self.on_gpu and not self.deferred:
             self.forward_pass_start = torch.cuda.Event(enable_timing=True)
             self.forward_pass_end = torch.cuda.Event(enable_timing=True)
 
+    @property
+    def times(self):
+        if self._pending:
+            self.resolve()
+        return self._times
+
+    @times.setter
+    def times(self, value):
+        self._times = value
+
     def record_start_time(self):
         if self.on_gpu:
+            if self.deferred:
+                self.forward_pass_start = torch.cuda.Event(enable_timing=True)
+                self.forward_pass_end = torch.cuda.Event(enable_timing=True)
             self.forward_pass_start.record()
         else:
             self._t0 = time.perf_counter()
@@ -270,10 +295,20 @@ class InferenceTimer:
     def record_end_time_and_elapsed_time(self):
         if self.on_gpu:
             self.forward_pass_end.record()
+            if self.deferred:
+                self._pending.append((self.forward_pass_start, self.forward_pass_end))
+                return
             torch.cuda.synchronize()
-            self.times.append(self.forward_pass_start.elapsed_time(self.forward_pass_end))
+            self._times.append(self.forward_pass_start.elapsed_time(self.forward_pass_end))
         else:
-            self.times.append(1e3 * (time.perf_counter() - self._t0))
+            self._times.append(1e3 * (time.perf_counter() - self._t0))
+
+    def resolve(self):
+        """Deferred mode: waits for the recorded frames and appends their times; a no-op otherwise."""
+        pending, self._pending = self._pending, []
+        for start, end in pending:
+            end.synchronize()
+            self._times.append(start.elapsed_time(end))
 
     def statistics(self):
         times = np.array(self.times[self.n_skip:])

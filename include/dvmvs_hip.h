@@ -45,7 +45,9 @@ extern "C" {
  * ABI 11 = ABI 10 + the DPSNet baseline's plane volume (dvmvs_dps_volume_fwd) and its up-sampling soft-argmin (dvmvs_dps_regress_fwd);
  * no earlier signature changed.
  * ABI 11, later addition: dvmvs_preprocess_* (frame pre-processing on the device); no earlier signature changed.  The number stays 11:
- * a library built before the addition reports the same version and simply lacks the two symbols, which a binding must check for. */
+ * a library built before the addition reports the same version and simply lacks the two symbols, which a binding must check for.
+ * ABI 11, later addition: dvmvs_depth_errors_* (depth evaluation on the device); no earlier signature changed, the number stays 11 by the
+ * same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -566,6 +568,36 @@ int dvmvs_preprocess_rgb_fwd(const unsigned char* src, float* dst, int N, int H,
                              const float* std_host, int normalize, dvmvs_stream_t stream);
 int dvmvs_preprocess_depth_fwd(const unsigned short* src, float* dst, int N, int H, int W, int crop_x, int crop_y, int new_h, int new_w,
                                double scaling, dvmvs_stream_t stream);
+
+/*
+ * Depth evaluation (ABI 11, later addition): the eight metrics of dvmvs/errors.py::compute_errors (the reference's dvmvs/errors.py:4-28)
+ * for n_frames (ground truth, prediction) pairs in ONE launch.
+ *   gt, pred   fp32 [n_frames, pixels] dense; the base pointers need 4-byte alignment only and pixels may be any positive number: a
+ *              frame whose two rows are 16-byte aligned is read with 16-byte loads, any other with scalar loads, with the same result
+ *   max_depth  fp32; +inf = no upper bound
+ *   metrics    fp32 [n_frames, 8] out: abs_error, abs_relative_error, abs_inverse_error, squared_relative_error, rmse, ratio_125,
+ *              ratio_125_2, ratio_125_3
+ *   counts     int [n_frames, 4] out, or null: n and the three inlier counts
+ *   workspace  dvmvs_depth_errors_workspace_bytes(n_frames, pixels) bytes, 8-byte aligned: per-frame integer tickets followed by the
+ *              per-workgroup partial sums.  The ticket words (the first 4 n_frames bytes) must be ZERO before the first call; every
+ *              call leaves them zero, so consecutive calls need no memset.  Calls that share a workspace must be ordered (one stream).
+ * Arithmetic contract.  A pixel takes part iff gt >= 0.5f && gt <= max_depth (a NaN gt fails both).  Per pixel, in fp32, every
+ * operation rounded, no FMA contraction, correctly rounded divisions -- compute_errors' elementwise operations on fp32 arrays:
+ *   d = gt - pred;  |d|;  |d| / gt;  |1 / gt - 1 / pred|;  d d / gt;  d d;  ratio = max(gt / pred, pred / gt) where a NaN operand
+ *   gives NaN (np.maximum, not fmaxf).
+ * ratio < 1.25f, < 1.5625f, < 1.953125f are counted as integers; a NaN ratio is never an inlier.  pred is not filtered: a zero,
+ * negative, infinite or NaN prediction gives what IEEE arithmetic gives numpy (inf / NaN in the affected metrics).  The five sums are
+ * accumulated in fp64 in an order that is a function of `pixels` alone (per-thread strided partial sums, a fixed tree in the workgroup,
+ * per-workgroup partial sums added by index by the workgroup that draws the frame's last ticket; no floating-point atomics): results
+ * are bit-identical run to run, for any n_frames, and for either load width.  Row: fp32(sum / n) for the first four metrics,
+ * fp32(sqrt(sum / n)) for rmse, fp32(count_k) / fp32(n) for the ratios (both exact below 2^24); n = 0 gives eight NaNs.
+ * Returns DVMVS_EINVAL for a null gt / pred / metrics / workspace, n_frames < 1, pixels < 1, a NaN max_depth, a pointer that is not
+ * 4-byte (workspace: 8-byte) aligned; DVMVS_EUNSUPPORTED for pixels >= 2^24 (fp32 no longer holds the counts exactly) or
+ * n_frames > 65535.  dvmvs_depth_errors_workspace_bytes returns 0 for sizes the entry point refuses.
+ */
+size_t dvmvs_depth_errors_workspace_bytes(int n_frames, long long pixels);
+int dvmvs_depth_errors_fwd(const float* gt, const float* pred, int n_frames, long long pixels, float max_depth, float* metrics,
+                           int* counts, void* workspace, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
