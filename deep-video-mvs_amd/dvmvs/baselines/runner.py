@@ -24,10 +24,9 @@ import torch
 from dvmvs.baselines.networks import Decoder, Encoder
 from dvmvs.baselines.dpsnet.dpsnet import PSNet
 from dvmvs.baselines.gpmvs.gplayer import GPlayer
-from dvmvs.dataset_loader import FrameUploader, PreprocessImage
 from dvmvs.hip import ops
 from dvmvs.pose_algebra import sweep_matrices_host
-from dvmvs.runner import DeviceEvaluation, Scene, _finish_on_device
+from dvmvs.runner import FrameInput, KeyframeIndex, SceneResults
 from dvmvs.utils import InferenceTimer, pose_distance
 
 WIDTH, HEIGHT = 320, 256
@@ -209,84 +208,56 @@ def system_name(method, keyframe_index_file, finetuned=True, size=(WIDTH, HEIGHT
                                          "finetuned" if finetuned else "without_ft")
 
 
-def _to_device(image_hwc, device):
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(image_hwc, (2, 0, 1)))).float().unsqueeze(0).to(device)
-
-
-def _prepare(pre, raw, rgb, device, uploader):
-    """Network input [1,3,h,w] on the device: numpy on the host and a blocking copy, or (``uploader``) one kernel launch on the raw frame."""
-    if uploader is None:
-        return _to_device(pre.apply_rgb(raw, *rgb), device)
-    return pre.apply_rgb_device(raw, *rgb, device=device, uploader=uploader)
-
-
-def _reference_depth(pre, scene, reference_index, device, uploader):
-    if uploader is None:
-        return pre.apply_depth(scene.depth(reference_index))
-    return pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader)[0].cpu().numpy()
-
-
-def _device_evaluation(device, scene, lines, evaluate, device_preprocess):
-    return DeviceEvaluation(device, evaluate and scene.depth_names, device_preprocess, capacity=sum(l != "TRACKING LOST" for l in lines))
-
-
-def _evaluation_slot(evaluation, pre, scene, reference_index, device, uploader):
-    """The frame's slot of the device stack, its ground truth enqueued (dvmvs.runner.DeviceEvaluation)."""
-    slot = evaluation.next_slot(pre.new_height, pre.new_width)
-    if evaluation.with_depth and uploader is not None:
-        pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader, out=slot.gt.unsqueeze(0))
-    elif evaluation.with_depth:
-        evaluation.stage(slot, pre.apply_depth(scene.depth(reference_index)))
-    return slot
-
-
-def _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess=False, device_evaluate=False,
-             error_log=None):
-    scene = Scene(scene_folder, raw=device_preprocess)
-    device = frame.device
-    uploader = FrameUploader(device) if device_preprocess else None
-    rgb = (SCALE_RGB, MEAN_RGB, STD_RGB)
-    position = {name: i for i, name in enumerate(scene.image_names)}
-    lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
+def _predict(method_inputs, device, size, rgb, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess, device_evaluate,
+             error_log):
+    """The loop of the three baselines: "TRACKING LOST" lines are skipped.  ``method_inputs(scene, pre, reference_index,
+    measurement_indices)`` evaluates what the method's network takes besides the images (poses, intrinsics), outside the timed region,
+    and returns the timed call ``(reference_image, measurement_images) -> depth``."""
+    frames = FrameInput(scene_folder, device, device_preprocess, rgb=rgb, size=size, crop=(0, False))
+    index = KeyframeIndex(keyframe_index_file, frames.scene.image_names, max_frames)
+    results = SceneResults(frames, evaluate, device_evaluate, index.n_predictions, error_log)
     timer = InferenceTimer(deferred=device_evaluate)
-    evaluation = _device_evaluation(device, scene, lines, evaluate, device_preprocess) if device_evaluate else None
-    predictions, reference_depths = [], []
+    with torch.no_grad():
+        for _, indices, _ in index:
+            if indices is None:
+                continue
+            reference_index, measurement_indices = indices[0], indices[1:]
+            raw = frames.scene.image(reference_index)
+            pre = frames.preprocessor(raw)
+            reference_image = frames.prepare(pre, raw)
+            measurement_images = [frames.image(pre, m) for m in measurement_indices]
+            network = method_inputs(frames.scene, pre, reference_index, measurement_indices)
+            results.begin(pre, reference_index)
+            timer.record_start_time()
+            depth = network(reference_image, measurement_images)
+            timer.record_end_time_and_elapsed_time()
+            results.add(depth)
+    return results.finish(timer)
+
+
+def _predict_baseline(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess=False, device_evaluate=False,
+                      error_log=None):
+    """MVDepthNet and GP-MVS (``frame``: a BaselineFrame): float32 host poses and K; GP-MVS also gets ``dt``, the pose distance to the
+    previous prediction's frame, which a tracking loss does not reset."""
     previous_index = None
     if frame.gp is not None:
         frame.gp.reset()
-    with torch.no_grad():
-        for line in lines:
-            if line == "TRACKING LOST":
-                continue
-            indices = [position[name] for name in line.split(" ")]
-            reference_index, measurement_indices = indices[0], indices[1:]
-            raw = scene.image(reference_index)
-            pre = PreprocessImage(K=scene.K, old_width=raw.shape[1], old_height=raw.shape[0], new_width=WIDTH, new_height=HEIGHT,
-                                  distortion_crop=0, perform_crop=False)
-            reference_image = _prepare(pre, raw, rgb, device, uploader)
-            measurement_images = [_prepare(pre, scene.image(m), rgb, device, uploader) for m in measurement_indices]
-            reference_pose = torch.from_numpy(scene.poses[reference_index]).float().unsqueeze(0)
-            measurement_poses = [torch.from_numpy(scene.poses[m]).float().unsqueeze(0) for m in measurement_indices]
-            K = torch.from_numpy(pre.get_updated_intrinsics()).float().unsqueeze(0)
-            dt = None
-            if frame.gp is not None:
-                if previous_index is None:
-                    previous_index = measurement_indices[-1]     # the reference's leaked loop variable
-                dt = pose_distance(scene.poses[reference_index], scene.poses[previous_index])[0]
-            slot = _evaluation_slot(evaluation, pre, scene, reference_index, device, uploader) if evaluation is not None else None
-            timer.record_start_time()
-            depth = frame(reference_image, measurement_images, reference_pose, measurement_poses, K, dt=dt)
-            timer.record_end_time_and_elapsed_time()
-            previous_index = reference_index
-            if evaluation is not None:           # prediction, ground truth and metrics stay on the device: nothing waits here
-                evaluation.commit(slot, depth)
-            else:
-                predictions.append(depth.cpu().numpy().squeeze())
-                if evaluate and scene.depth_names:
-                    reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
-    if evaluation is not None:
-        return _finish_on_device(evaluation, timer, error_log)
-    return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
+
+    def inputs(scene, pre, reference_index, measurement_indices):
+        nonlocal previous_index
+        reference_pose, measurement_poses = scene.pose(reference_index), [scene.pose(m) for m in measurement_indices]
+        K = FrameInput.intrinsics(pre)
+        dt = None
+        if frame.gp is not None:
+            if previous_index is None:
+                previous_index = measurement_indices[-1]     # the reference's leaked loop variable
+            dt = pose_distance(scene.poses[reference_index], scene.poses[previous_index])[0]
+        previous_index = reference_index
+        return lambda reference_image, measurement_images: frame(reference_image, measurement_images, reference_pose, measurement_poses, K,
+                                                                 dt=dt)
+
+    return _predict(inputs, frame.device, (WIDTH, HEIGHT), (SCALE_RGB, MEAN_RGB, STD_RGB), scene_folder, keyframe_index_file, evaluate,
+                    max_frames, device_preprocess, device_evaluate, error_log)
 
 
 def predict_mvdepthnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
@@ -298,8 +269,8 @@ def predict_mvdepthnet(scene_folder, keyframe_index_file, weights_folder=None, e
     the device until the scene is done, the timer is the deferred one, and one download fetches everything; ``error_log`` (a list)
     receives a float32 [8] row per prediction for ``save_results(..., errors=error_log)`` (dvmvs.runner.predict_offline)."""
     encoder, decoder = build_mvdepthnet(weights_folder, device)
-    return _predict(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess,
-                    device_evaluate, error_log)
+    return _predict_baseline(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames,
+                             device_preprocess, device_evaluate, error_log)
 
 
 def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
@@ -308,7 +279,7 @@ def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evalua
     ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_mvdepthnet``."""
     encoder, decoder, gplayer = build_gpmvs(weights_folder, device)
     frame = BaselineFrame(encoder, decoder, device, gp=GPFilter.from_gplayer(gplayer))
-    return _predict(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess, device_evaluate, error_log)
+    return _predict_baseline(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess, device_evaluate, error_log)
 
 
 def dpsnet_relative_pose(reference_pose, measurement_pose):
@@ -321,42 +292,16 @@ def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evalu
     """DPSNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
     ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_mvdepthnet``."""
     dpsnet = build_dpsnet(weights_folder, device)
-    scene = Scene(scene_folder, raw=device_preprocess)
-    uploader = FrameUploader(device) if device_preprocess else None
-    position = {name: i for i, name in enumerate(scene.image_names)}
-    lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
-    timer = InferenceTimer(deferred=device_evaluate)
-    evaluation = _device_evaluation(torch.device(device), scene, lines, evaluate, device_preprocess) if device_evaluate else None
-    predictions, reference_depths = [], []
-    with torch.no_grad():
-        for line in lines:
-            if line == "TRACKING LOST":
-                continue
-            indices = [position[name] for name in line.split(" ")]
-            reference_index, measurement_indices = indices[0], indices[1:]
-            raw = scene.image(reference_index)
-            pre = PreprocessImage(K=scene.K, old_width=raw.shape[1], old_height=raw.shape[0], new_width=DPS_WIDTH, new_height=DPS_HEIGHT,
-                                  distortion_crop=0, perform_crop=False)
-            rgb = (DPS_SCALE_RGB, DPS_MEAN_RGB, DPS_STD_RGB)
-            reference_image = _prepare(pre, raw, rgb, device, uploader)
-            measurement_images = [_prepare(pre, scene.image(m), rgb, device, uploader) for m in measurement_indices]
-            poses = [dpsnet_relative_pose(scene.poses[reference_index], scene.poses[m]).to(device) for m in measurement_indices]
-            camera_k = pre.get_updated_intrinsics()
-            K = torch.from_numpy(camera_k).float().unsqueeze(0).to(device)
-            K_inv = torch.from_numpy(np.linalg.inv(camera_k)).float().unsqueeze(0).to(device)
-            slot = _evaluation_slot(evaluation, pre, scene, reference_index, device, uploader) if evaluation is not None else None
-            timer.record_start_time()
-            _, prediction = dpsnet(reference_image, measurement_images, poses, K, K_inv)
-            timer.record_end_time_and_elapsed_time()
-            if evaluation is not None:
-                evaluation.commit(slot, prediction)
-            else:
-                predictions.append(prediction.cpu().numpy().squeeze())
-                if evaluate and scene.depth_names:
-                    reference_depths.append(_reference_depth(pre, scene, reference_index, device, uploader))
-    if evaluation is not None:
-        return _finish_on_device(evaluation, timer, error_log)
-    return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
+
+    def inputs(scene, pre, reference_index, measurement_indices):
+        poses = [dpsnet_relative_pose(scene.poses[reference_index], scene.poses[m]).to(device) for m in measurement_indices]
+        camera_k = pre.get_updated_intrinsics()
+        K = torch.from_numpy(camera_k).float().unsqueeze(0).to(device)
+        K_inv = torch.from_numpy(np.linalg.inv(camera_k)).float().unsqueeze(0).to(device)
+        return lambda reference_image, measurement_images: dpsnet(reference_image, measurement_images, poses, K, K_inv)[1]
+
+    return _predict(inputs, device, (DPS_WIDTH, DPS_HEIGHT), (DPS_SCALE_RGB, DPS_MEAN_RGB, DPS_STD_RGB), scene_folder, keyframe_index_file,
+                    evaluate, max_frames, device_preprocess, device_evaluate, error_log)
 
 
 def main(method, argv=None):

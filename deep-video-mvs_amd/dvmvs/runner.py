@@ -40,23 +40,74 @@ class Scene:
     def depth(self, i):
         return (load_depth_png_u16 if self.raw else load_depth_png)(os.path.join(self.folder, "depth", self.depth_names[i]))
 
+    def pose(self, i):
+        """[1,4,4] float32 on the host (poses and K stay there: DepthEngine.step)."""
+        return torch.from_numpy(self.poses[i]).float().unsqueeze(0)
+
 
 def _to_device(image_hwc, device):
     return torch.from_numpy(np.ascontiguousarray(np.transpose(image_hwc, (2, 0, 1)))).float().unsqueeze(0).to(device)
 
 
-def _preprocessor(scene, raw_image):
-    return PreprocessImage(K=scene.K, old_width=raw_image.shape[1], old_height=raw_image.shape[0], new_width=Config.test_image_width,
-                           new_height=Config.test_image_height, distortion_crop=Config.test_distortion_crop,
-                           perform_crop=Config.test_perform_crop)
+def _preprocessor(scene, raw_image, size=None, crop=None):
+    """The PreprocessImage of a raw frame of ``scene``: the one place a scene run builds it.  ``size`` = (width, height) and ``crop`` =
+    (distortion_crop, perform_crop) default to the fusionnet's (Config.test_*)."""
+    width, height = size or (Config.test_image_width, Config.test_image_height)
+    distortion_crop, perform_crop = crop or (Config.test_distortion_crop, Config.test_perform_crop)
+    return PreprocessImage(K=scene.K, old_width=raw_image.shape[1], old_height=raw_image.shape[0], new_width=width, new_height=height,
+                           distortion_crop=distortion_crop, perform_crop=perform_crop)
 
 
-def _prepare(pre, raw, device, uploader):
-    """Network input [1,3,h,w] on the device: on the host (numpy, then a blocking copy) or, with an ``uploader``, from the raw 8-bit frame
-    in one kernel launch behind a pinned, non-blocking copy."""
-    if uploader is None:
-        return _to_device(pre.apply_rgb(raw, SCALE_RGB, MEAN_RGB, STD_RGB), device)
-    return pre.apply_rgb_device(raw, SCALE_RGB, MEAN_RGB, STD_RGB, device=device, uploader=uploader)
+class FrameInput:
+    """The frames of one scene run as network inputs: opens the scene and, with ``device_preprocess``, owns the FrameUploader.  ``rgb`` =
+    (scale, mean, std); ``size`` and ``crop`` as in ``_preprocessor``.  ``ahead`` holds an image that was prepared before its turn (the
+    offline fusionnet loop's look-ahead), by frame index."""
+
+    def __init__(self, scene_folder, device, device_preprocess, rgb=(SCALE_RGB, MEAN_RGB, STD_RGB), size=None, crop=None):
+        self.scene = Scene(scene_folder, raw=device_preprocess)
+        self.device, self.rgb, self.size, self.crop = torch.device(device), rgb, size, crop
+        self.uploader = FrameUploader(self.device) if device_preprocess else None
+        self.ahead = {}
+
+    def preprocessor(self, raw):
+        return _preprocessor(self.scene, raw, self.size, self.crop)
+
+    def prepare(self, pre, raw):
+        """Network input [1,3,h,w] on the device: on the host (numpy, then a blocking copy) or, with ``device_preprocess``, from the raw 8-bit
+        frame in one kernel launch behind a pinned, non-blocking copy."""
+        if self.uploader is None:
+            return _to_device(pre.apply_rgb(raw, *self.rgb), self.device)
+        return pre.apply_rgb_device(raw, *self.rgb, device=self.device, uploader=self.uploader)
+
+    def image(self, pre, index):
+        return self.prepare(pre, self.scene.image(index))
+
+    @staticmethod
+    def intrinsics(pre):
+        return torch.from_numpy(pre.get_updated_intrinsics()).float().unsqueeze(0)
+
+
+class KeyframeIndex:
+    """A keyframe index file ("ref meas1 meas2 ..." or "TRACKING LOST" per line), cut to ``max_frames`` lines and then parsed: ``lines``
+    (stripped, for ``frame_log``), ``frames`` (per line the frame positions [ref, meas1, ...], or None where tracking was lost),
+    ``next_keyframe`` (per line the number of the next line that is not a tracking loss, or None) and ``n_predictions``."""
+
+    def __init__(self, keyframe_index_file, image_names, max_frames=None):
+        position = {name: i for i, name in enumerate(image_names)}
+        with open(keyframe_index_file) as f:
+            self.lines = [l.strip() for l in f if l.strip()][:max_frames]
+        self.frames = [None if line == "TRACKING LOST" else [position[name] for name in line.split(" ")] for line in self.lines]
+        self.n_predictions = sum(frames is not None for frames in self.frames)
+        self.next_keyframe, upcoming = [None] * len(self.lines), None
+        for n in reversed(range(len(self.lines))):
+            self.next_keyframe[n] = upcoming
+            if self.frames[n] is not None:
+                upcoming = n
+
+    def __iter__(self):
+        """(line, its frames or None, the next keyframe's frames or None) per line."""
+        for line, frames, upcoming in zip(self.lines, self.frames, self.next_keyframe):
+            yield line, frames, (self.frames[upcoming] if upcoming is not None else None)
 
 
 class DeviceEvaluation:
@@ -127,71 +178,89 @@ class DeviceEvaluation:
         return predictions, (gts if self.gt_on_device else self.host_gts)
 
 
-def _run_frame(engine, scene, timer, device, reference_index, measurement_indices, evaluate, images=None, next_reference_index=None,
-               prepared=None, next_measurement_indices=None, uploader=None, evaluation=None):
-    """``next_reference_index``: the reference frame of the NEXT call when it is known (offline runs): its image is pre-processed now and
-    handed to the engine as look-ahead (DepthEngine.step: its features are computed concurrently with this frame); ``prepared``
-    (a dict) carries the pre-processed device image to that next call.  ``uploader`` (a FrameUploader; ``scene`` then loads raw 8- / 16-bit
-    frames): images and the ground-truth depth are pre-processed on the device.  ``evaluation`` (a DeviceEvaluation): the prediction, the
-    ground truth and their metrics stay on the device, nothing here waits for it, and (None, None) is returned."""
-    raw = images[reference_index] if images is not None and reference_index in images else scene.image(reference_index)
-    pre = _preprocessor(scene, raw)
-    ref_image = prepared.pop(reference_index, None) if prepared is not None else None
+class SceneResults:
+    """What a scene run returns, by one of three routes chosen here: the host route (the prediction is fetched per frame, the ground truth
+    pre-processed with numpy), ``device_preprocess`` alone (the ground truth is pre-processed on the device and fetched together with the
+    prediction) and ``device_evaluate`` (a DeviceEvaluation: nothing is fetched before ``finish``).  ``frames``: the run's FrameInput
+    (scene, device, uploader); ``capacity``: the number of predictions, or the block size where it is not known."""
+
+    def __init__(self, frames, evaluate, device_evaluate, capacity, error_log=None):
+        self.frames, self.error_log = frames, error_log
+        self.want_depth = bool(evaluate and frames.scene.depth_names)
+        self.evaluation = None
+        if device_evaluate:
+            self.evaluation = DeviceEvaluation(frames.device, self.want_depth, frames.uploader is not None, capacity)
+        self.predictions, self.reference_depths = [], []
+
+    def begin(self, pre, reference_index):
+        """Before the timed region: enqueues the ground truth of the frame (``pre``: its PreprocessImage) where the route has it on the device."""
+        scene, device, uploader = self.frames.scene, self.frames.device, self.frames.uploader
+        self.pre, self.reference_index, self.slot, self.depth_on_device = pre, reference_index, None, None
+        if self.evaluation is not None:
+            self.slot = self.evaluation.next_slot(pre.new_height, pre.new_width)
+            if self.want_depth and uploader is not None:
+                pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader, out=self.slot.gt.unsqueeze(0))
+            elif self.want_depth:
+                self.evaluation.stage(self.slot, pre.apply_depth(scene.depth(reference_index)))
+        elif self.want_depth and uploader is not None:
+            self.depth_on_device = pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader)
+
+    def add(self, depth):
+        """After the timed region: the network's depth [1,1,h,w] (a static buffer is fine: it is copied or fetched here)."""
+        if self.evaluation is not None:              # prediction, ground truth and metrics stay on the device: nothing waits here
+            self.evaluation.commit(self.slot, depth)
+            return
+        if self.depth_on_device is not None:         # one transfer for both maps (same size: the network's)
+            prediction, reference_depth = torch.stack((depth.reshape(self.depth_on_device.shape[-2:]), self.depth_on_device[0])).cpu().numpy()
+        else:
+            prediction = depth.cpu().numpy().squeeze()
+            reference_depth = self.pre.apply_depth(self.frames.scene.depth(self.reference_index)) if self.want_depth else None
+        self.predictions.append(prediction)
+        self.reference_depths.append(reference_depth)
+
+    def finish(self, timer):
+        """(predictions, reference depths or None, timer); ``device_evaluate``: one download, the rows into ``error_log``, the timer resolved."""
+        if self.evaluation is not None:
+            predictions, reference_depths = self.evaluation.finish(self.error_log)
+            timer.resolve()
+            return predictions, reference_depths, timer
+        return self.predictions, (self.reference_depths if self.want_depth else None), timer
+
+
+def _run_frame(engine, frames, results, timer, indices, upcoming=None):
+    """One prediction: ``indices`` = [reference, measurement, ...] frame positions.  ``upcoming``: the same of the NEXT call when it is known
+    (offline runs): its reference image is pre-processed now and handed to the engine as look-ahead (DepthEngine.step: its features, sweep
+    and encoder run concurrently with this frame), and kept in ``frames.ahead`` for that next call."""
+    scene = frames.scene
+    reference_index, measurement_indices = indices[0], indices[1:]
+    raw = scene.image(reference_index)
+    pre = frames.preprocessor(raw)
+    ref_image = frames.ahead.pop(reference_index, None)
     if ref_image is None:
-        ref_image = _prepare(pre, raw, device, uploader)
+        ref_image = frames.prepare(pre, raw)
     next_image = None
-    if next_reference_index is not None and prepared is not None:
-        raw_next = images[next_reference_index] if images is not None and next_reference_index in images else scene.image(next_reference_index)
-        next_image = _prepare(_preprocessor(scene, raw_next), raw_next, device, uploader)
-        prepared.clear()
-        prepared[next_reference_index] = next_image
-    ref_pose = torch.from_numpy(scene.poses[reference_index]).float().unsqueeze(0)   # poses / K stay on the host (engine.step)
-    full_K = torch.from_numpy(pre.get_updated_intrinsics()).float().unsqueeze(0)
+    if upcoming is not None:
+        raw_next = scene.image(upcoming[0])
+        next_image = frames.prepare(frames.preprocessor(raw_next), raw_next)
+        frames.ahead = {upcoming[0]: next_image}
+    ref_pose, full_K = scene.pose(reference_index), FrameInput.intrinsics(pre)
     meas_images, meas_poses = [], []
     for m in measurement_indices:
         if engine.cache_features and m in engine._feature_cache:
             meas_images.append(None)     # features of this keyframe are cached: no need to load / pre-process the image again
         else:
-            raw_m = images[m] if images is not None and m in images else scene.image(m)
-            meas_images.append(_prepare(pre, raw_m, device, uploader))
-        meas_poses.append(torch.from_numpy(scene.poses[m]).float().unsqueeze(0))
-    want_depth = bool(evaluate and scene.depth_names)
-    depth_on_device = None
-    slot = None
-    if evaluation is not None:                   # the frame's slot; its ground truth is enqueued with the images, outside the timed region
-        slot = evaluation.next_slot(pre.new_height, pre.new_width)
-        if want_depth and uploader is not None:
-            pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader, out=slot.gt.unsqueeze(0))
-        elif want_depth:
-            evaluation.stage(slot, pre.apply_depth(scene.depth(reference_index)))
-    elif want_depth and uploader is not None:      # enqueued with the images, outside the timed region; fetched with the prediction
-        depth_on_device = pre.apply_depth_device(scene.depth(reference_index), device=device, uploader=uploader)
+            meas_images.append(frames.image(pre, m))
+        meas_poses.append(scene.pose(m))
+    results.begin(pre, reference_index)
     timer.record_start_time()
     ahead = {}
-    if next_image is not None:
-        ahead = dict(next_reference_image=next_image, next_frame_id=next_reference_index)
-        if next_measurement_indices is not None:      # ... and its poses: the engine then also runs its sweep + encoder a frame ahead
-            ahead.update(next_reference_pose=torch.from_numpy(scene.poses[next_reference_index]).float().unsqueeze(0),
-                         next_measurement_poses=[torch.from_numpy(scene.poses[m]).float().unsqueeze(0) for m in next_measurement_indices],
-                         next_measurement_ids=list(next_measurement_indices))
+    if upcoming is not None:      # the next reference image and its poses: the engine then also runs its sweep + encoder a frame ahead
+        ahead = dict(next_reference_image=next_image, next_frame_id=upcoming[0], next_reference_pose=scene.pose(upcoming[0]),
+                     next_measurement_poses=[scene.pose(m) for m in upcoming[1:]], next_measurement_ids=list(upcoming[1:]))
     depth = engine.step(ref_image, ref_pose, meas_images, meas_poses, full_K, frame_id=reference_index,
                         measurement_ids=list(measurement_indices), **ahead)
     timer.record_end_time_and_elapsed_time()
-    if evaluation is not None:
-        evaluation.commit(slot, depth)
-        return None, None
-    if depth_on_device is not None:              # one transfer for both maps (same size: the network's)
-        both = torch.stack((depth.reshape(depth_on_device.shape[-2:]), depth_on_device[0])).cpu().numpy()
-        return both[0], both[1]
-    prediction = depth.cpu().numpy().squeeze()
-    reference_depth = pre.apply_depth(scene.depth(reference_index)) if want_depth else None
-    return prediction, reference_depth
-
-
-def _finish_on_device(evaluation, timer, error_log):
-    predictions, reference_depths = evaluation.finish(error_log)
-    timer.resolve()
-    return predictions, reference_depths, timer
+    results.add(depth)
 
 
 def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, evaluate=True, max_frames=None, frame_log=None,
@@ -206,38 +275,19 @@ def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, eval
     is the deferred one, and nothing waits for the device inside the loop; ONE download after it fetches everything (DeviceEvaluation).
     ``error_log`` (a list) then receives one float32 [8] row per prediction (``save_results(..., errors=error_log)``); it stays empty
     without ground truth or with ``evaluate=False``.  Default False: today's path, unchanged."""
-    scene = Scene(scene_folder, raw=device_preprocess)
-    device = engine.device
-    uploader = FrameUploader(device) if device_preprocess else None
-    position = {name: i for i, name in enumerate(scene.image_names)}
+    frames = FrameInput(scene_folder, engine.device, device_preprocess)
+    index = KeyframeIndex(keyframe_index_file, frames.scene.image_names, max_frames)
+    results = SceneResults(frames, evaluate, device_evaluate, index.n_predictions, error_log)
     timer = InferenceTimer(deferred=device_evaluate)
-    predictions, reference_depths = [], []
     engine.new_sequence()
-    lines = [l.strip() for l in open(keyframe_index_file) if l.strip()][:max_frames]
-    evaluation = None
-    if device_evaluate:
-        evaluation = DeviceEvaluation(device, evaluate and scene.depth_names, device_preprocess,
-                                      capacity=sum(l != "TRACKING LOST" for l in lines))
-    prepared = {}      # the next keyframe's pre-processed image (the index file says which frame that is: feature look-ahead)
-    for n, line in enumerate(lines):
+    for line, indices, upcoming in index:     # ``upcoming``: the index file says which keyframe is next (look-ahead)
         if frame_log is not None:
             frame_log.append(line)
-        if line == "TRACKING LOST":
+        if indices is None:
             engine.reset()
             continue
-        indices = [position[name] for name in line.split(" ")]
-        upcoming = next((l for l in lines[n + 1:] if l != "TRACKING LOST"), None)
-        next_indices = [position[name] for name in upcoming.split(" ")] if upcoming is not None else None
-        prediction, reference_depth = _run_frame(engine, scene, timer, device, indices[0], indices[1:], evaluate,
-                                                 next_reference_index=next_indices[0] if next_indices else None, prepared=prepared,
-                                                 next_measurement_indices=next_indices[1:] if next_indices else None, uploader=uploader,
-                                                 evaluation=evaluation)
-        if evaluation is None:
-            predictions.append(prediction)
-            reference_depths.append(reference_depth)
-    if evaluation is not None:
-        return _finish_on_device(evaluation, timer, error_log)
-    return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
+        _run_frame(engine, frames, results, timer, indices, upcoming)
+    return results.finish(timer)
 
 
 def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames=None, frame_log=None, device_preprocess=False,
@@ -247,15 +297,13 @@ def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames
     "TRACKING LOST" where it cleared itself -- the lines simulate_keyframe_index would write for the same poses.
     ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_offline``; the number of predictions is not known in
     advance here, so the device stack grows in blocks of 32 frames."""
-    scene = Scene(scene_folder, raw=device_preprocess)
-    device = engine.device
-    uploader = FrameUploader(device) if device_preprocess else None
-    evaluation = DeviceEvaluation(device, evaluate and scene.depth_names, device_preprocess, capacity=32) if device_evaluate else None
+    frames = FrameInput(scene_folder, engine.device, device_preprocess)
+    scene = frames.scene
+    results = SceneResults(frames, evaluate, device_evaluate, 32, error_log)
+    timer = InferenceTimer(deferred=device_evaluate)
     buffer = KeyframeBuffer(buffer_size=Config.test_keyframe_buffer_size, keyframe_pose_distance=Config.test_keyframe_pose_distance,
                             optimal_t_score=Config.test_optimal_t_measure, optimal_R_score=Config.test_optimal_R_measure,
                             store_return_indices=True)
-    timer = InferenceTimer(deferred=device_evaluate)
-    predictions, reference_depths = [], []
     engine.new_sequence()
     n = len(scene.poses) if max_frames is None else min(max_frames, len(scene.poses))
     for i in range(n):
@@ -266,17 +314,11 @@ def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames
                 frame_log.append("TRACKING LOST")
         if response != 1:
             continue
-        measurement_indices = [frame[2] for frame in buffer.get_best_measurement_frames(Config.test_n_measurement_frames)]
+        indices = [i] + [frame[2] for frame in buffer.get_best_measurement_frames(Config.test_n_measurement_frames)]
         if frame_log is not None:
-            frame_log.append(" ".join(scene.image_names[j] for j in [i] + measurement_indices))
-        prediction, reference_depth = _run_frame(engine, scene, timer, device, i, measurement_indices, evaluate, uploader=uploader,
-                                                 evaluation=evaluation)
-        if evaluation is None:
-            predictions.append(prediction)
-            reference_depths.append(reference_depth)
-    if evaluation is not None:
-        return _finish_on_device(evaluation, timer, error_log)
-    return predictions, (reference_depths if evaluate and scene.depth_names else None), timer
+            frame_log.append(" ".join(scene.image_names[j] for j in indices))
+        _run_frame(engine, frames, results, timer, indices)
+    return results.finish(timer)
 
 
 def predict_sharded(make_engine, scene_folders, keyframe_index_files, evaluate=True, max_frames=None, rank=None, world=None):

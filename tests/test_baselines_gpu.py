@@ -242,3 +242,48 @@ def test_runner_on_the_sample_scene(hip_device, tmp_path, method):
     saved = np.load(out / f"{name}_predictions_000.npz")
     assert list(saved.keys()) == ["arr_0"] and saved["arr_0"].shape == (2, 256, 320)
     assert np.load(out / f"{name}_errors_000.npz")["arr_0"].shape == (2, 8)
+
+
+class ModeRuns:
+    """One predict_* entry point on one scene under the (device_preprocess, device_evaluate) combinations: each combination is run once
+    (a fresh network per run, as the entry points build it), kept, and compared read-only."""
+
+    def __init__(self, predict, scene, index, device, **keywords):
+        self.predict, self.scene, self.index, self.device, self.keywords = predict, scene, index, device, keywords
+        self.done = {}
+
+    def __call__(self, device_preprocess, device_evaluate):
+        """(predictions, ground truths, timer, error rows)"""
+        mode = (bool(device_preprocess), bool(device_evaluate))
+        if mode not in self.done:
+            rows = []
+            self.done[mode] = self.predict(self.scene, self.index, device=self.device, device_preprocess=mode[0], device_evaluate=mode[1],
+                                           error_log=rows, **self.keywords) + (rows,)
+        return self.done[mode]
+
+    def check(self, device_preprocess, device_evaluate, what):
+        """Against the default call: tests/test_preprocess_gpu.py's rule wherever device_preprocess is set, tests/test_depth_errors_gpu.py's
+        wherever device_evaluate is (its two runs share ``device_preprocess``: it asks for the ground truth's dtype to stay)."""
+        from test_depth_errors_gpu import _compare_evaluation_modes
+        from test_preprocess_gpu import _compare_modes
+        what = f"{what}(device_preprocess={device_preprocess}, device_evaluate={device_evaluate})"
+        assert len(self(False, False)[0]) == 2 and self(False, False)[3] == []
+        if device_preprocess:
+            _compare_modes(lambda flag, log: self(flag, flag and device_evaluate)[:2], what)
+        if device_evaluate:
+            def run(flag, rows):
+                if rows is not None:
+                    rows.extend(self(device_preprocess, flag)[3])
+                return self(device_preprocess, flag)[:3]
+            _compare_evaluation_modes(run, what)
+
+
+@pytest.fixture(scope="module")
+def gpmvs_runs(hip_device, tmp_path_factory):
+    scene = str(tmp_path_factory.mktemp("gpmvs") / "scene")
+    return ModeRuns(runner.predict_gpmvs, scene, _write_scene(scene), hip_device)
+
+
+@pytest.mark.parametrize("device_preprocess,device_evaluate", [(True, False), (False, True), (True, True)])
+def test_predict_gpmvs_in_every_mode(gpmvs_runs, device_preprocess, device_evaluate):
+    gpmvs_runs.check(device_preprocess, device_evaluate, "predict_gpmvs")

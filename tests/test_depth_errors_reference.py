@@ -177,3 +177,87 @@ def test_runner_bookkeeping_with_a_stub_engine(monkeypatch, tmp_path):
     shutil.rmtree(os.path.join(scene, "depth"))
     preds, gts, _ = predict_offline(_StubEngine(True), scene, index, evaluate=True, device_evaluate=True, error_log=rows)
     assert len(preds) == 3 and gts is None and rows == []
+
+
+class _StubBaselineFrame:
+    """Stands in for BaselineFrame on the CPU: MVDepthNet's attributes, and a depth that depends on the reference image and pose, written
+    into ONE static buffer (``static``) as the networks' outputs may be."""
+    gp = None
+
+    def __init__(self, static=False):
+        self.static = static
+        self.device = torch.device("cpu")
+        self.output = torch.zeros((1, 1, 256, 320))
+
+    def __call__(self, reference_image, measurement_images, reference_pose, measurement_poses, K, dt=None):
+        assert dt is None and len(measurement_images) == len(measurement_poses) == 2 and not torch.is_grad_enabled()
+        self.output.copy_(1.6 + 0.05 * reference_pose.abs().sum() + 0.001 * reference_image.mean(1, keepdim=True))
+        return self.output if self.static else self.output.clone()
+
+
+def test_baseline_loop_bookkeeping_with_a_stub_frame(monkeypatch, tmp_path):
+    """The baselines' loop with device_evaluate on a CPU stub: same predictions and ground truth (array and dtype) as the default path, one
+    row per prediction that obeys the triangle rule against compute_errors, one positive time per prediction, and an empty error_log
+    without ground truth or with evaluate=False."""
+    import shutil
+    from test_runner import _write_scene
+    from dvmvs.baselines.runner import _predict_baseline
+    from dvmvs.hip import ops
+    monkeypatch.setattr(ops, "depth_errors", _reference_op)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    scene = str(tmp_path / "scene")
+    _write_scene(scene, 14)
+    index = str(tmp_path / "index")
+    with open(index, "w") as f:
+        f.write("00009.png 00006.png 00003.png\n00010.png 00009.png 00006.png\nTRACKING LOST\n00013.png 00010.png 00009.png\n")
+    preds, gts, timer = _predict_baseline(_StubBaselineFrame(), scene, index, True, None)
+    rows = []
+    preds_dev, gts_dev, timer_dev = _predict_baseline(_StubBaselineFrame(static=True), scene, index, True, None, device_evaluate=True,
+                                                      error_log=rows)
+    assert len(preds) == len(preds_dev) == len(gts) == len(gts_dev) == len(rows) == len(timer_dev.times) == len(timer.times) == 3
+    assert not np.array_equal(preds[0], preds[1])            # the stub's static buffer was copied out frame by frame
+    for p, g, pd, gd, row in zip(preds, gts, preds_dev, gts_dev, rows):
+        assert pd.shape == (256, 320) and np.array_equal(p, pd) and gd.dtype == g.dtype and np.array_equal(g, gd)
+        assert row.dtype == np.float32 and row.shape == (8,)
+        ref.check_against_host(row, ref.reference(g.astype(np.float32), p)[0], ref.host_errors(g, p))
+    assert all(t > 0 for t in timer_dev.times)
+    rows = []
+    preds, gts, _ = _predict_baseline(_StubBaselineFrame(True), scene, index, False, None, device_evaluate=True, error_log=rows)
+    assert len(preds) == 3 and gts is None and rows == []
+    shutil.rmtree(os.path.join(scene, "depth"))
+    preds, gts, _ = _predict_baseline(_StubBaselineFrame(True), scene, index, True, None, device_evaluate=True, error_log=rows)
+    assert len(preds) == 3 and gts is None and rows == []
+
+
+def test_keyframe_index_reader(tmp_path):
+    """Blank lines dropped, ``max_frames`` applied to the stripped lines BEFORE they are parsed (a name the scene does not have, past the
+    cut, is never looked up), tracking losses as None, and per line the next keyframe the scene loop of the earlier runner looked for
+    with ``next(l for l in lines[n + 1:] if l != "TRACKING LOST")`` -- written out here."""
+    from dvmvs.runner import KeyframeIndex
+    names = [f"{i:05d}.png" for i in range(8)]
+    text = ("\n00003.png 00002.png 00001.png\n  \nTRACKING LOST\nTRACKING LOST\n00004.png 00003.png\n   00005.png 00004.png 00003.png  \n\n"
+            "TRACKING LOST\n00007.png 00005.png\nTRACKING LOST\n")
+    path = str(tmp_path / "index")
+    with open(path, "w") as f:
+        f.write(text + "99999.png 00001.png\n")
+    lines = [l.strip() for l in text.split("\n") if l.strip()]
+    assert len(lines) == 8
+    with pytest.raises(KeyError):
+        KeyframeIndex(path, names)
+    for max_frames in (8, 7, 5, 3, 1, 0):
+        index = KeyframeIndex(path, names, max_frames)
+        want = lines[:max_frames]
+        assert index.lines == want and len(index.frames) == len(index.next_keyframe) == len(want)
+        assert index.n_predictions == sum(l != "TRACKING LOST" for l in want)
+        for n, line in enumerate(want):
+            frames = None if line == "TRACKING LOST" else [int(name[:5]) for name in line.split(" ")]
+            assert index.frames[n] == frames
+            upcoming = next((l for l in want[n + 1:] if l != "TRACKING LOST"), None)
+            found = index.next_keyframe[n]
+            assert (want[found] if found is not None else None) == upcoming and (found is None or found > n)
+        walked = list(index)
+        assert [w[0] for w in walked] == want and [w[1] for w in walked] == index.frames
+        assert [w[2] for w in walked] == [index.frames[k] if k is not None else None for k in index.next_keyframe]
+    with open(path, "w") as f:
+        f.write(text)
+    assert KeyframeIndex(path, names).lines == lines and KeyframeIndex(path, names).n_predictions == 4

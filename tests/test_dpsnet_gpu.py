@@ -240,3 +240,22 @@ def test_runner_on_the_sample_scene(hip_device, tmp_path):
     save_results(predictions, depths, name, "000", str(out))
     assert sorted(os.listdir(out)) == [f"{name}_errors_000.npz", f"{name}_predictions_000.npz"]
     assert np.load(out / f"{name}_predictions_000.npz")["arr_0"].shape == (2, 240, 320)
+
+
+@pytest.fixture(scope="module")
+def dpsnet_runs(hip_device, tmp_path_factory):
+    """predict_dpsnet with the fixtures' network (dpsnet_fixtures.seeded_dpsnet, loaded as a ``*dpsnet*`` checkpoint), not the default
+    initialisation: that one saturates the soft-argmin -- the disparity sits at its 1e-16 clamp and the "depth" is 32 / 1e-16 = 3.2e17 on
+    most pixels -- which is the case the fixtures' factors exist to avoid, and no depth map: compute_errors on float32 maps is defined
+    only while the sum of the squared differences stays below float32's 3.4e38, i.e. below 6.6e16 per pixel over 320 x 240 pixels."""
+    from test_baselines_gpu import ModeRuns
+    folder = tmp_path_factory.mktemp("dpsnet")
+    torch.save(fx.seeded_dpsnet(PSNet).state_dict(), str(folder / "dpsnet_fixture_weights"))
+    scene = str(folder / "scene")
+    return ModeRuns(runner.predict_dpsnet, scene, _write_scene(scene), hip_device, weights_folder=str(folder))
+
+
+@pytest.mark.parametrize("device_preprocess,device_evaluate", [(True, False), (False, True), (True, True)])
+def test_predict_dpsnet_in_every_mode(dpsnet_runs, device_preprocess, device_evaluate):
+    dpsnet_runs.check(device_preprocess, device_evaluate, "predict_dpsnet")
+    assert all(np.isfinite(p).all() and p.max() < 6.6e16 for p in dpsnet_runs(False, False)[0])
