@@ -16,7 +16,7 @@ from dvmvs.hip import _capi
 
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
            "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress", "preprocess_rgb",
-           "preprocess_depth", "depth_errors"]
+           "preprocess_depth", "depth_errors", "tsdf_raycast", "tsdf_raycast_mask"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1340,3 +1340,95 @@ def depth_errors(gt: Tensor, pred: Tensor, max_depth: float = float("inf"), out:
                                                 _ptr(counts) if counts is not None else None, _ptr(workspace), _stream(gt))
     _capi.check(rc, "dvmvs_depth_errors_fwd")
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# ray-casting a fused TSDF volume from camera views (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+def _raycast_volumes(name, tsdf, weight, color=None):
+    for label, t in (("tsdf", tsdf), ("weight", weight), ("color", color)):
+        if t is None:
+            continue
+        if t.device.type != "cuda":
+            _no_cpu(name)
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape != tsdf.shape or t.device != tsdf.device or not t.is_contiguous():
+            raise ValueError(f"dvmvs::{name}: {label} must be a contiguous float32 [X,Y,Z] tensor like tsdf {tuple(tsdf.shape)} on "
+                             f"{tsdf.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    X, Y, Z = (int(d) for d in tsdf.shape)
+    if min(X, Y, Z) < 2:
+        raise ValueError(f"dvmvs::{name}: every dimension of the volume must be at least 2, got {X}x{Y}x{Z}")
+    return X, Y, Z
+
+
+def tsdf_raycast_mask(tsdf: Tensor, weight: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """Brick mask of a TSDF volume for ``tsdf_raycast``: uint8 [ceil((X-1)/8), ceil((Y-1)/8), ceil((Z-1)/8)], 1 where one of the brick's
+    8x8x8 cells has a corner with ``weight > 0 and tsdf <= 0``.  It describes the volume's CURRENT contents: rebuild it after every
+    change.  ``out``: a contiguous uint8 tensor of that shape; it is returned."""
+    X, Y, Z = _raycast_volumes("tsdf_raycast_mask", tsdf, weight)
+    shape = ((X + 6) // 8, (Y + 6) // 8, (Z + 6) // 8)
+    nbytes = _capi.lib().dvmvs_tsdf_raycast_mask_bytes(X, Y, Z)
+    if nbytes == 0:
+        _capi.check(EUNSUPPORTED, "dvmvs_tsdf_raycast_mask_bytes")
+    assert nbytes == shape[0] * shape[1] * shape[2]
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=tsdf.device)
+    elif out.device != tsdf.device or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"dvmvs::tsdf_raycast_mask: out must be a contiguous uint8 {shape} tensor on {tsdf.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    with torch.cuda.device(tsdf.device):
+        rc = _capi.lib().dvmvs_tsdf_raycast_mask(_ptr(tsdf), _ptr(weight), X, Y, Z, _ptr(out), _stream(tsdf))
+    _capi.check(rc, "dvmvs_tsdf_raycast_mask")
+    return out
+
+
+def tsdf_raycast(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], origin: Sequence[float], voxel_size: float, cam_intr: Tensor,
+                 cam_pose: Tensor, height: int, width: int, near: float = 0.0, far: float = float("inf"), step: float = 1.0,
+                 mask: Optional[Tensor] = None, normals: bool = True, colour: bool = True):
+    """Renders a TSDF volume (the three float32 [X,Y,Z] device tensors of ``dvmvs.tsdf.TSDFVolume``; ``color`` may be None without
+    ``colour``) from N views in one launch: ``cam_intr`` [N,3,3] and camera-to-world ``cam_pose`` [N,4,4], float32 on the volume's device.
+    Returns ``(depth [N,height,width] float32, normals [N,height,width,3] float32 or None, rgb [N,height,width,3] uint8 or None)``: the
+    camera depth of the first zero crossing along each pixel's ray (0 = no surface), the world-space unit normal there (zero where it is
+    undefined) and the colour of the nearest voxel.  ``step``: sample spacing in voxels, in (0, 5].  ``mask``: the result of
+    ``tsdf_raycast_mask`` for the same volume contents (empty bricks are jumped over; same bits) or None for the dense march.
+    Definition: include/dvmvs_hip.h.  Runs on the current stream without touching the host."""
+    X, Y, Z = _raycast_volumes("tsdf_raycast", tsdf, weight, color)
+    dev = tsdf.device
+    if colour and color is None:
+        raise ValueError("dvmvs::tsdf_raycast: colour output needs the colour volume")
+    for label, t, tail in (("cam_intr", cam_intr, (3, 3)), ("cam_pose", cam_pose, (4, 4))):
+        if t.device.type != "cuda":
+            _no_cpu("tsdf_raycast")
+        if t.dtype != torch.float32 or t.dim() != 3 or tuple(t.shape[1:]) != tail or t.device != dev:
+            raise ValueError(f"dvmvs::tsdf_raycast: {label} must be float32 [N,{tail[0]},{tail[1]}] on {dev}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    N = int(cam_pose.shape[0])
+    height, width = int(height), int(width)
+    if N < 1 or cam_intr.shape[0] != N or height < 1 or width < 1:
+        raise ValueError(f"dvmvs::tsdf_raycast: expected N >= 1 poses and as many intrinsics and a positive image size, got "
+                         f"{tuple(cam_pose.shape)}, {tuple(cam_intr.shape)}, {height}x{width}")
+    near, far, step, voxel_size = float(near), float(far), float(step), float(voxel_size)
+    if not (0.0 < step <= 5.0):
+        raise ValueError(f"dvmvs::tsdf_raycast: step must be in (0, 5] voxels (the truncation), got {step}")
+    if not (0.0 <= near < float("inf")) or far != far:
+        raise ValueError(f"dvmvs::tsdf_raycast: near must be finite and >= 0 and far not NaN, got {near}, {far}")
+    if not voxel_size > 0.0:
+        raise ValueError(f"dvmvs::tsdf_raycast: voxel_size must be positive, got {voxel_size}")
+    origin = [float(o) for o in origin]
+    if len(origin) != 3:
+        raise ValueError("dvmvs::tsdf_raycast: origin must have three components")
+    if mask is not None:
+        shape = ((X + 6) // 8, (Y + 6) // 8, (Z + 6) // 8)
+        if mask.device != dev or mask.dtype != torch.uint8 or tuple(mask.shape) != shape or not mask.is_contiguous():
+            raise ValueError(f"dvmvs::tsdf_raycast: mask must be the contiguous uint8 {shape} tensor of tsdf_raycast_mask on {dev}, got "
+                             f"{mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    cam_intr, cam_pose = cam_intr.contiguous(), cam_pose.contiguous()
+    depth = torch.empty((N, height, width), dtype=torch.float32, device=dev)
+    normal = torch.empty((N, height, width, 3), dtype=torch.float32, device=dev) if normals else None
+    rgb = torch.empty((N, height, width, 3), dtype=torch.uint8, device=dev) if colour else None
+    with torch.cuda.device(dev):
+        rc = _capi.lib().dvmvs_tsdf_raycast_fwd(
+            _ptr(tsdf), _ptr(weight), None if color is None else _ptr(color), X, Y, Z, origin[0], origin[1], origin[2], voxel_size,
+            None if mask is None else _ptr(mask), _ptr(cam_intr), _ptr(cam_pose), N, height, width, near, far, step, _ptr(depth),
+            None if normal is None else _ptr(normal), None if rgb is None else _ptr(rgb), _stream(tsdf))
+    _capi.check(rc, "dvmvs_tsdf_raycast_fwd")
+    return depth, normal, rgb

@@ -106,6 +106,7 @@ class TSDFVolume:
         self._tsdf = torch.ones(dims, dtype=torch.float32, device=self.device)
         self._weight = torch.zeros(dims, dtype=torch.float32, device=self.device)
         self._color = torch.zeros(dims, dtype=torch.float32, device=self.device)
+        self._raycast_mask = None     # brick mask of render(): describes the volumes' contents, so integrate() drops it
 
     @property
     def vol_dim(self):
@@ -135,7 +136,40 @@ class TSDFVolume:
                 float(self._vol_origin[0]), float(self._vol_origin[1]), float(self._vol_origin[2]), self._voxel_size,
                 K.data_ptr(), P.data_ptr(), color.data_ptr(), depth.data_ptr(), im_h, im_w, self._trunc_margin, float(obs_weight),
                 torch.cuda.current_stream(dev).cuda_stream)
+        self._raycast_mask = None      # (before the check: a failed call may have been enqueued)
         _capi.check(rc, "dvmvs_tsdf_integrate")
+
+    def render(self, cam_intr, cam_poses, height, width, near=0.0, far=float("inf"), step=1.0, normals=True, colour=True, skip_empty=True):
+        """Ray-casts the volume from N views in one launch (csrc/tsdf_raycast.hip; definition in include/dvmvs_hip.h): ``cam_poses``
+        camera-to-world [N,4,4] or one [4,4], ``cam_intr`` [N,3,3] or one [3,3] for all views; numpy arrays or tensors.  Returns device
+        tensors ``(depth [N,height,width] float32, normals [N,height,width,3] float32 or None, rgb [N,height,width,3] uint8 or None)``:
+        the camera depth of the fused surface along each pixel's ray (0 where the ray meets none between ``near`` and ``far``), its
+        world-space unit normal (pointing toward increasing distance, i.e. to the observer's side; zero where undefined) and its colour.
+        ``step``: sample spacing in voxels, in (0, 5].  ``skip_empty``: jump over bricks that cannot hold a crossing, with a mask
+        cached on the volume until the next ``integrate``; the result is bit-identical either way."""
+        from dvmvs.hip import ops
+        dev = self.device
+
+        def as_dev(a, tail):
+            t = torch.as_tensor(np.asarray(a, dtype=np.float32) if not torch.is_tensor(a) else a, dtype=torch.float32, device=dev)
+            if t.dim() == 2:
+                t = t.unsqueeze(0)
+            if t.dim() != 3 or tuple(t.shape[1:]) != tail:
+                raise ValueError(f"expected [{tail[0]},{tail[1]}] or [N,{tail[0]},{tail[1]}], got {tuple(t.shape)}")
+            return t
+
+        P, K = as_dev(cam_poses, (4, 4)), as_dev(cam_intr, (3, 3))
+        if K.shape[0] == 1 and P.shape[0] > 1:
+            K = K.expand(P.shape[0], 3, 3)
+        if K.shape[0] != P.shape[0]:
+            raise ValueError(f"{K.shape[0]} intrinsics for {P.shape[0]} poses")
+        mask = None
+        if skip_empty:
+            if self._raycast_mask is None:
+                self._raycast_mask = ops.tsdf_raycast_mask(self._tsdf, self._weight)
+            mask = self._raycast_mask
+        return ops.tsdf_raycast(self._tsdf, self._weight, self._color if colour else None, self._vol_origin, self._voxel_size, K.contiguous(),
+                                P.contiguous(), height, width, near=near, far=far, step=step, mask=mask, normals=normals, colour=colour)
 
     def get_volume(self):
         """(tsdf, colour) as numpy arrays, like the reference; ``get_weight_volume()`` for the weights."""
@@ -257,13 +291,18 @@ def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dat
 
 
 def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, scene_name, system_name, voxel_size, max_depth,
-        use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False):
+        use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
     loaders (no OpenCV).  ``device_preprocess`` (the switch the scene runners share): this program resamples its colour images with
     nearest selection only and integrates them as 8-bit, so all the switch does here is keep them 8-bit from the decoder on
-    (``load_image_u8``: no float32 round trip); the values, and the meshes, are the same."""
+    (``load_image_u8``: no float32 round trip); the values, and the meshes, are the same.
+
+    ``render_keyframes``: after fusion, ray-cast the volume from every fused keyframe's own view at the prediction size (one launch,
+    ``TSDFVolume.render``) and save the fused depth maps next to the meshes as ``keyframe_<dataset>_<system>+tsdf_predictions_<scene>.npz``,
+    the layout of the network's predictions; if the scene has ground-truth depth, also their error metrics (``..._errors_<scene>.npz``),
+    evaluated on the device over the pixels where a surface was hit.  Without the flag nothing else is written or changed."""
     from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, load_image_u8, resize_nearest
     if device_preprocess:
         load_image = load_image_u8       # resize_nearest only selects pixels: the uint8 values are those of the float path's astype
@@ -335,6 +374,32 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K,
                          _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name,
                                     dataset_name, scene_name), save_progressive)
+    if render_keyframes:
+        _render_keyframes(volume, keyframe_poses, keyframe_image_filenames, scaled_K, preprocessor, prediction_height, prediction_width,
+                          scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
+
+
+def _render_keyframes(volume, poses, image_filenames, K, preprocessor, height, width, scene_folder, system_name, scene_name, save_folder):
+    """The fused depth of every keyframe: rendered, saved like predictions and, where ground truth exists, scored on the device."""
+    from dvmvs.dataset_loader import load_depth_png
+    from dvmvs.errors import compute_errors_device
+    from dvmvs.utils import save_predictions, save_results
+    if not poses:
+        print("No keyframe to render")
+        return
+    depth, _, _ = volume.render(K, np.stack(poses), height, width, normals=False, colour=False)
+    hit = depth > 0
+    print("Rendered {} keyframes from the fused volume: {:.1f} % of the pixels hit a surface".format(len(poses), 100.0 * float(hit.float().mean())))
+    rendered = depth.cpu().numpy()
+    depth_files = [os.path.join(scene_folder, "depth", os.path.basename(f)) for f in image_filenames]
+    if os.path.isdir(os.path.join(scene_folder, "depth")) and all(os.path.exists(f) for f in depth_files):
+        groundtruths = np.stack([preprocessor.apply_depth(load_depth_png(f)) for f in depth_files]).astype(np.float32)
+        gt = torch.from_numpy(groundtruths).to(depth.device)
+        gt = torch.where(hit, gt, torch.zeros_like(gt))       # a miss takes no part in the metrics
+        rows = compute_errors_device(gt, depth).cpu().numpy()
+        save_results(rendered, groundtruths, system_name, scene_name, save_folder, errors=rows)
+    else:
+        save_predictions(rendered, system_name, scene_name, save_folder)
 
 
 def main(argv=None):
@@ -353,6 +418,8 @@ def main(argv=None):
     parser.add_argument("--save_groundtruth", action="store_true", help="also write the reconstruction from the ground-truth depth maps")
     parser.add_argument("--device-preprocess", dest="device_preprocess", action="store_true",
                         help="load the colour images as 8-bit (no float32 round trip); same meshes")
+    parser.add_argument("--render_keyframes", action="store_true",
+                        help="also ray-cast the fused volume from every keyframe's view and save the fused depth maps (<system>+tsdf)")
     args = parser.parse_args(argv)
     run(**vars(args))
 

@@ -47,7 +47,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_preprocess_* (frame pre-processing on the device); no earlier signature changed.  The number stays 11:
  * a library built before the addition reports the same version and simply lacks the two symbols, which a binding must check for.
  * ABI 11, later addition: dvmvs_depth_errors_* (depth evaluation on the device); no earlier signature changed, the number stays 11 by the
- * same rule. */
+ * same rule.
+ * ABI 11, later addition: dvmvs_tsdf_raycast_* (ray-casting a fused TSDF volume from camera views); no earlier signature changed, the
+ * number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -598,6 +600,49 @@ int dvmvs_preprocess_depth_fwd(const unsigned short* src, float* dst, int N, int
 size_t dvmvs_depth_errors_workspace_bytes(int n_frames, long long pixels);
 int dvmvs_depth_errors_fwd(const float* gt, const float* pred, int n_frames, long long pixels, float max_depth, float* metrics,
                            int* counts, void* workspace, dvmvs_stream_t stream);
+
+/*
+ * TSDF ray-casting (ABI 11, later addition): depth, world-space normal and colour of the first zero crossing of a fused volume along
+ * every pixel's ray, for n_views cameras in ONE launch.  The reference project has no ray-caster: the definition is this project's own.
+ *   tsdf_vol, weight_vol, color_vol [dim_x,dim_y,dim_z]   the volumes of dvmvs_tsdf_integrate (z fastest); color_vol may be NULL when rgb is
+ *   origin_*, voxel_size    world position of voxel (0,0,0) and the voxel edge, metres
+ *   mask                    brick mask written by dvmvs_tsdf_raycast_mask for the SAME volume contents, or NULL = dense march.  Both
+ *                           give the same bits; a mask built before the volume changed is stale and must not be passed.
+ *   cam_intr [n_views,3,3], cam_pose [n_views,4,4] camera-to-world   (device pointers)
+ *   near, far               depth range in metres: 0 <= near < inf; far may be +inf
+ *   step                    sample spacing along the ray in voxels, 0 < step <= 5 (the truncation)
+ *   depth [n_views,im_h,im_w] fp32 out (0 = no surface); normal [n_views,im_h,im_w,3] fp32 out or NULL; rgb [n_views,im_h,im_w,3] uint8
+ *   out or NULL.
+ * Per pixel (u, v), in fp32, every operation rounded, no FMA contraction, correctly rounded divisions and square roots:
+ *   d_c = ((u - cx) / fx, (v - cy) / fy, 1);  o_g = (t - origin) / voxel_size;  d_g = (R d_c) / voxel_size with each row of R d_c summed left
+ *   to right;  g(z) = o_g + z d_g is the ray in voxel coordinates and z is the camera depth.
+ *   [z0, z1] = the slab intersection of the ray with the box [0, dim - 1]^3 cut to [near, far]; a component d_g == 0 contributes
+ *   (-inf, +inf) when o_g lies in its slab and nothing otherwise.  A non-finite o_g, d_g, z0, z1 or step / |d_g|, or z0 > z1: a miss.
+ *   dz = step / |d_g|;  n = min(floor((z1 - z0) / dz), n_cap), n_cap = floor(sqrt(sum (dim - 1)^2) / step) + 2 evaluated in double;
+ *   z_k = z0 + float(k) dz for k = 0..n (never accumulated).
+ *   f_k = trilinear tsdf at g(z_k) clamped to the box, in the cell i0 = min(floor(g), dim - 2), as lerp(a, b, w) = a (1 - w) + b w along
+ *   z, then y, then x.  Sample k is valid when all eight corner weights of its cell are > 0.
+ *   Hit: the first k >= 1 with samples k - 1 and k valid and f_{k-1} > 0 >= f_k;  depth = z_{k-1} + dz (f_{k-1} / (f_{k-1} - f_k)).
+ *   Normal at the hit point g* = clamp(o_g + depth d_g): per axis the difference of the same trilinear tsdf at clamp(g* + 1 voxel) and
+ *   clamp(g* - 1 voxel), the three differences divided by their Euclidean norm; (0,0,0) when one of the six samples is invalid, the norm
+ *   is zero, or on a miss.  Colour: the folded colour voxel at rint(g*) per axis (clamped), decoded as dvmvs_marching_cubes_emit decodes a
+ *   vertex colour; 0 on a miss.
+ * dvmvs_tsdf_raycast_mask_bytes: host only, no HIP call: one byte per 8x8x8 brick of cells,
+ *   ceil((dim_x - 1) / 8) * ceil((dim_y - 1) / 8) * ceil((dim_z - 1) / 8); 0 for a shape the entry points refuse.
+ * dvmvs_tsdf_raycast_mask: mask[brick] (z fastest) <- 1 when a corner of one of the brick's cells has weight > 0 && tsdf <= 0, else 0.
+ * Returns DVMVS_EINVAL for a null tsdf_vol / weight_vol / cam_intr / cam_pose / depth (mask entry point: mask), rgb without color_vol,
+ * a dimension below 2, n_views, im_h or im_w < 1, voxel_size <= 0, step outside (0, 5], near < 0 or not finite, a NaN far;
+ * DVMVS_EUNSUPPORTED for dim_y * dim_z >= 2^31, 2^26 bricks or more, im_h * im_w >= 2^31, im_h > 16 * 65535, n_views > 65535,
+ * ceil(im_w / 16) * ceil(im_h / 16) * n_views >= 2^24 (a launch of 256-thread workgroups holds fewer than 2^32 threads), or a
+ * march of 2^20 samples or more (n_cap).  Nothing is enqueued in either case.
+ */
+size_t dvmvs_tsdf_raycast_mask_bytes(int dim_x, int dim_y, int dim_z);
+int dvmvs_tsdf_raycast_mask(const float* tsdf_vol, const float* weight_vol, int dim_x, int dim_y, int dim_z, unsigned char* mask,
+                            dvmvs_stream_t stream);
+int dvmvs_tsdf_raycast_fwd(const float* tsdf_vol, const float* weight_vol, const float* color_vol, int dim_x, int dim_y, int dim_z,
+                           float origin_x, float origin_y, float origin_z, float voxel_size, const unsigned char* mask,
+                           const float* cam_intr, const float* cam_pose, int n_views, int im_h, int im_w, float near, float far, float step,
+                           float* depth, float* normal, unsigned char* rgb, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
