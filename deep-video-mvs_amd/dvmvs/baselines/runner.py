@@ -209,13 +209,13 @@ def system_name(method, keyframe_index_file, finetuned=True, size=(WIDTH, HEIGHT
 
 
 def _predict(method_inputs, device, size, rgb, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess, device_evaluate,
-             error_log):
+             error_log, fuse=None):
     """The loop of the three baselines: "TRACKING LOST" lines are skipped.  ``method_inputs(scene, pre, reference_index,
     measurement_indices)`` evaluates what the method's network takes besides the images (poses, intrinsics), outside the timed region,
     and returns the timed call ``(reference_image, measurement_images) -> depth``."""
     frames = FrameInput(scene_folder, device, device_preprocess, rgb=rgb, size=size, crop=(0, False))
     index = KeyframeIndex(keyframe_index_file, frames.scene.image_names, max_frames)
-    results = SceneResults(frames, evaluate, device_evaluate, index.n_predictions, error_log)
+    results = SceneResults(frames, evaluate, device_evaluate, index.n_predictions, error_log, fuse)
     timer = InferenceTimer(deferred=device_evaluate)
     with torch.no_grad():
         for _, indices, _ in index:
@@ -227,7 +227,7 @@ def _predict(method_inputs, device, size, rgb, scene_folder, keyframe_index_file
             reference_image = frames.prepare(pre, raw)
             measurement_images = [frames.image(pre, m) for m in measurement_indices]
             network = method_inputs(frames.scene, pre, reference_index, measurement_indices)
-            results.begin(pre, reference_index)
+            results.begin(pre, reference_index, raw=raw)
             timer.record_start_time()
             depth = network(reference_image, measurement_images)
             timer.record_end_time_and_elapsed_time()
@@ -236,7 +236,7 @@ def _predict(method_inputs, device, size, rgb, scene_folder, keyframe_index_file
 
 
 def _predict_baseline(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess=False, device_evaluate=False,
-                      error_log=None):
+                      error_log=None, fuse=None):
     """MVDepthNet and GP-MVS (``frame``: a BaselineFrame): float32 host poses and K; GP-MVS also gets ``dt``, the pose distance to the
     previous prediction's frame, which a tracking loss does not reset."""
     previous_index = None
@@ -257,29 +257,31 @@ def _predict_baseline(frame, scene_folder, keyframe_index_file, evaluate, max_fr
                                                                  dt=dt)
 
     return _predict(inputs, frame.device, (WIDTH, HEIGHT), (SCALE_RGB, MEAN_RGB, STD_RGB), scene_folder, keyframe_index_file, evaluate,
-                    max_frames, device_preprocess, device_evaluate, error_log)
+                    max_frames, device_preprocess, device_evaluate, error_log, fuse)
 
 
 def predict_mvdepthnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
-                       device_preprocess=False, device_evaluate=False, error_log=None):
+                       device_preprocess=False, device_evaluate=False, error_log=None, fuse=None):
     """MVDepthNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
     ``device_preprocess``: raw 8-bit frames are uploaded through a pinned ring and pre-processed by dvmvs.hip.ops.preprocess_rgb (the
     ground-truth depth by preprocess_depth, float32) instead of by numpy on the host.
     ``device_evaluate``: predictions, ground truth and their eight error metrics (one dvmvs.hip.ops.depth_errors launch per frame) stay on
     the device until the scene is done, the timer is the deferred one, and one download fetches everything; ``error_log`` (a list)
-    receives a float32 [8] row per prediction for ``save_results(..., errors=error_log)`` (dvmvs.runner.predict_offline)."""
+    receives a float32 [8] row per prediction for ``save_results(..., errors=error_log)`` (dvmvs.runner.predict_offline).
+    ``fuse``: a ``dvmvs.tsdf.LiveFusion`` that also receives every prediction as it is made (dvmvs.runner.predict_offline)."""
     encoder, decoder = build_mvdepthnet(weights_folder, device)
     return _predict_baseline(BaselineFrame(encoder, decoder, device), scene_folder, keyframe_index_file, evaluate, max_frames,
-                             device_preprocess, device_evaluate, error_log)
+                             device_preprocess, device_evaluate, error_log, fuse)
 
 
 def predict_gpmvs(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
-                  device_preprocess=False, device_evaluate=False, error_log=None):
+                  device_preprocess=False, device_evaluate=False, error_log=None, fuse=None):
     """GP-MVS over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
-    ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_mvdepthnet``."""
+    ``device_preprocess``, ``device_evaluate``, ``error_log`` and ``fuse`` as in ``predict_mvdepthnet``."""
     encoder, decoder, gplayer = build_gpmvs(weights_folder, device)
     frame = BaselineFrame(encoder, decoder, device, gp=GPFilter.from_gplayer(gplayer))
-    return _predict_baseline(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess, device_evaluate, error_log)
+    return _predict_baseline(frame, scene_folder, keyframe_index_file, evaluate, max_frames, device_preprocess, device_evaluate, error_log,
+                             fuse)
 
 
 def dpsnet_relative_pose(reference_pose, measurement_pose):
@@ -288,9 +290,9 @@ def dpsnet_relative_pose(reference_pose, measurement_pose):
 
 
 def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evaluate=True, max_frames=None, device="cuda",
-                   device_preprocess=False, device_evaluate=False, error_log=None):
+                   device_preprocess=False, device_evaluate=False, error_log=None, fuse=None):
     """DPSNet over the lines of a keyframe index file.  Returns (predictions, reference depths or None, InferenceTimer).
-    ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_mvdepthnet``."""
+    ``device_preprocess``, ``device_evaluate``, ``error_log`` and ``fuse`` as in ``predict_mvdepthnet``."""
     dpsnet = build_dpsnet(weights_folder, device)
 
     def inputs(scene, pre, reference_index, measurement_indices):
@@ -301,12 +303,23 @@ def predict_dpsnet(scene_folder, keyframe_index_file, weights_folder=None, evalu
         return lambda reference_image, measurement_images: dpsnet(reference_image, measurement_images, poses, K, K_inv)[1]
 
     return _predict(inputs, device, (DPS_WIDTH, DPS_HEIGHT), (DPS_SCALE_RGB, DPS_MEAN_RGB, DPS_STD_RGB), scene_folder, keyframe_index_file,
-                    evaluate, max_frames, device_preprocess, device_evaluate, error_log)
+                    evaluate, max_frames, device_preprocess, device_evaluate, error_log, fuse)
+
+
+def live_fusion_for_scene(scene_folder, size, voxel_size, max_depth, batch, device="cuda"):
+    """The ``LiveFusion`` of ``--fuse``: its volume spans the frusta of ALL the scene's poses cut at ``max_depth`` (``frustum_bounds``, with
+    the reconstruction program's 5 % margin), at the intrinsics of a ``size`` = (width, height) prediction -- sized before any depth exists."""
+    from dvmvs.runner import Scene, _preprocessor
+    from dvmvs.tsdf import LiveFusion, TSDFFusion
+    scene = Scene(scene_folder)
+    K = _preprocessor(scene, scene.image(0), size, (0, False)).get_updated_intrinsics()
+    bounds = TSDFFusion.frustum_bounds(list(scene.poses), K, size[1], size[0], max_depth) * 1.05
+    return LiveFusion(bounds, voxel_size=voxel_size, max_depth=max_depth, batch=batch, device=device)
 
 
 def main(method, argv=None):
     """``python -m dvmvs.baselines.{mvdepthnet,gpmvs,dpsnet} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]
-    [--device-preprocess] [--device-evaluate]``."""
+    [--device-preprocess] [--device-evaluate] [--fuse [--fuse_voxel_size M] [--fuse_max_depth M] [--fuse_batch N]]``."""
     import argparse
     from dvmvs.utils import save_results
     parser = argparse.ArgumentParser(prog=f"python -m dvmvs.baselines.{method}")
@@ -321,14 +334,29 @@ def main(method, argv=None):
     parser.add_argument("--device-evaluate", action="store_true",
                         help="keep predictions and ground truth on the GPU and evaluate the error metrics there (one launch per frame, one "
                              "download per scene) instead of fetching every frame and evaluating with numpy")
+    parser.add_argument("--fuse", action="store_true",
+                        help="fuse every prediction into a TSDF volume while the scene runs and write <out>/<system>_<scene>_live_complete.ply")
+    parser.add_argument("--fuse_voxel_size", default=0.025, type=float)
+    parser.add_argument("--fuse_max_depth", default=5.0, type=float)
+    parser.add_argument("--fuse_batch", default=8, type=int, help="frames fused per launch")
     args = parser.parse_args(argv)
     predict = {"mvdepthnet": predict_mvdepthnet, "gpmvs": predict_gpmvs, "dpsnet": predict_dpsnet}[method]
     size = (DPS_WIDTH, DPS_HEIGHT) if method == "dpsnet" else (WIDTH, HEIGHT)
     error_log = []
+    fuse = None
+    if args.fuse:
+        fuse = live_fusion_for_scene(args.scene_folder, size, args.fuse_voxel_size, args.fuse_max_depth, args.fuse_batch)
     predictions, reference_depths, timer = predict(args.scene_folder, args.keyframe_index_file, args.weights, max_frames=args.max_frames,
                                                   device_preprocess=args.device_preprocess, device_evaluate=args.device_evaluate,
-                                                  error_log=error_log)
+                                                  error_log=error_log, fuse=fuse)
     timer.print_statistics()
+    name, scene_name = system_name(method, args.keyframe_index_file, finetuned=not args.without_ft, size=size), \
+        _index_file_fields(args.keyframe_index_file)[2]
     save_results(predictions=predictions, groundtruths=reference_depths, errors=error_log if args.device_evaluate else None,
-                 system_name=system_name(method, args.keyframe_index_file, finetuned=not args.without_ft, size=size),
-                 scene_name=_index_file_fields(args.keyframe_index_file)[2], save_folder=args.out)
+                 system_name=name, scene_name=scene_name, save_folder=args.out)
+    if fuse is not None:
+        from dvmvs.tsdf import TSDFFusion
+        os.makedirs(args.out, exist_ok=True)
+        mesh = os.path.join(args.out, f"{name}_{scene_name}_live")
+        print("Saving mesh to", mesh)
+        TSDFFusion.meshwrite(mesh + "_complete.ply", *fuse.volume.get_mesh())

@@ -116,6 +116,10 @@ SIGNATURES = {
     "dvmvs_tsdf_raycast_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_tsdf_integrate_frames_workspace_bytes": (ctypes.c_size_t, [_c_int]),
+    "dvmvs_tsdf_integrate_frames": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                             ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float,
+                                             _c_f3, ctypes.c_float, _c_fp, _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -125,6 +129,8 @@ ADDED_WITHIN_ABI = ("dvmvs_preprocess_rgb_fwd", "dvmvs_preprocess_depth_fwd")
 ADDED_WITHIN_ABI_DEPTH_ERRORS = ("dvmvs_depth_errors_workspace_bytes", "dvmvs_depth_errors_fwd")
 # ... and the third (ray-casting a TSDF volume)
 ADDED_WITHIN_ABI_TSDF_RAYCAST = ("dvmvs_tsdf_raycast_mask_bytes", "dvmvs_tsdf_raycast_mask", "dvmvs_tsdf_raycast_fwd")
+# ... and the fourth (fusing a batch of frames into a TSDF volume)
+ADDED_WITHIN_ABI_TSDF_FUSE = ("dvmvs_tsdf_integrate_frames_workspace_bytes", "dvmvs_tsdf_integrate_frames")
 
 _lib = None
 _lock = threading.Lock()
@@ -143,7 +149,8 @@ def lib():
                 f"dvmvs HIP library not found at {LIB_PATH}. Build it with `make -C deep-video-mvs_amd/csrc` "
                 f"(or __graft_entry__.build()). The plane-sweep ops have no CPU / eager fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        missing = [name for name in ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST if not hasattr(handle, name)]
+        added = ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
+        missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "
                                f"rebuild it with `make -C deep-video-mvs_amd/csrc` (or __graft_entry__.build())")

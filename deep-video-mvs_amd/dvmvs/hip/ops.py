@@ -16,7 +16,7 @@ from dvmvs.hip import _capi
 
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
            "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress", "preprocess_rgb",
-           "preprocess_depth", "depth_errors", "tsdf_raycast", "tsdf_raycast_mask"]
+           "preprocess_depth", "depth_errors", "tsdf_raycast", "tsdf_raycast_mask", "tsdf_integrate_frames"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1432,3 +1432,105 @@ def tsdf_raycast(tsdf: Tensor, weight: Tensor, color: Optional[Tensor], origin: 
             None if normal is None else _ptr(normal), None if rgb is None else _ptr(rgb), _stream(tsdf))
     _capi.check(rc, "dvmvs_tsdf_raycast_fwd")
     return depth, normal, rgb
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# fusing a batch of frames into a TSDF volume: one pass over the volume, the bits of per-frame integration (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+_fuse_workspaces = {}
+# the tile (voxels in x, y, z) one workgroup of csrc/tsdf_fuse.hip takes: kFuseTX, kFuseTY, kFuseTZ there.  Only the tile counters depend on
+# it, never the volume.
+TSDF_FUSE_TILE = (4, 4, 32)
+
+
+def tsdf_fuse_tile_count(dims, tile=TSDF_FUSE_TILE):
+    """Number of tiles (workgroups) ``tsdf_integrate_frames`` cuts a volume of ``dims`` voxels into."""
+    count = 1
+    for d, t in zip(dims, tile):
+        count *= -(-int(d) // t)
+    return count
+
+
+def tsdf_integrate_frames_workspace(device, n_frames):
+    """Persistent workspace of ``tsdf_integrate_frames`` per device: grown to the largest batch seen, written by every call before it is
+    read (the per-frame largest depth), so it needs no initialisation; calls that share it must be ordered (one stream per process)."""
+    device = torch.device(device)
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    workspace = _fuse_workspaces.get(index)
+    nbytes = _capi.lib().dvmvs_tsdf_integrate_frames_workspace_bytes(n_frames)
+    if workspace is None or workspace.numel() * 4 < nbytes:
+        workspace = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+        _fuse_workspaces[index] = workspace
+    return workspace
+
+
+def tsdf_integrate_frames(tsdf: Tensor, weight: Tensor, color: Tensor, origin: Sequence[float], voxel_size: float, cam_intr: Tensor,
+                          cam_pose: Tensor, depth: Tensor, rgb_u8: Optional[Tensor] = None, folded: Optional[Tensor] = None,
+                          trunc_margin: Optional[float] = None, obs_weight=1.0, max_depth: float = float("inf"), stats=False):
+    """Fuses N frames into a TSDF volume in place (the three contiguous float32 [X,Y,Z] device tensors of ``dvmvs.tsdf.TSDFVolume``) with
+    one pass over the volume and the bits of N ``dvmvs_tsdf_integrate`` calls in frame order (csrc/tsdf_fuse.hip; contract in
+    include/dvmvs_hip.h).  ``cam_intr`` [N,3,3], camera-to-world ``cam_pose`` [N,4,4] and ``depth`` [N,h,w] are contiguous float32 tensors on
+    the volume's device; the colour is EITHER ``rgb_u8`` [N,h,w,3] uint8 OR ``folded`` [N,h,w] float32 (``dvmvs.tsdf.fold_color``).
+    ``trunc_margin`` defaults to 5 voxels; ``obs_weight``: one number or N; a depth above ``max_depth`` counts as invalid.  ``stats``:
+    True returns a fresh int64 [2] device tensor holding the (tile, frame) pairs the culling kept and the tiles that loaded the volume;
+    a tensor is added to and returned; False (default) returns None and the kernel does not count.  Runs on the current stream without
+    touching the host."""
+    if (rgb_u8 is None) == (folded is None):
+        raise ValueError("dvmvs::tsdf_integrate_frames: exactly one of rgb_u8 and folded must be given")
+    tensors = [("tsdf", tsdf), ("weight", weight), ("color", color), ("cam_intr", cam_intr), ("cam_pose", cam_pose), ("depth", depth),
+               ("rgb_u8", rgb_u8) if rgb_u8 is not None else ("folded", folded)]
+    for label, t in tensors:
+        if not torch.is_tensor(t):
+            raise TypeError(f"dvmvs::tsdf_integrate_frames: {label} must be a tensor, got {type(t).__name__}")
+    if depth.dim() != 3 or depth.dtype != torch.float32:
+        raise ValueError(f"dvmvs::tsdf_integrate_frames: depth must be float32 [N,h,w], got {depth.dtype} {tuple(depth.shape)}")
+    N, h, w = (int(d) for d in depth.shape)
+    if N < 1 or h < 1 or w < 1:
+        raise ValueError(f"dvmvs::tsdf_integrate_frames: expected at least one non-empty frame, got depth {tuple(depth.shape)}")
+    for label, t in tensors[:3]:
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape != tsdf.shape or t.numel() == 0:
+            raise ValueError(f"dvmvs::tsdf_integrate_frames: {label} must be a non-empty float32 [X,Y,Z] tensor like tsdf "
+                             f"{tuple(tsdf.shape)}, got {t.dtype} {tuple(t.shape)}")
+    for label, t, tail in (("cam_intr", cam_intr, (N, 3, 3)), ("cam_pose", cam_pose, (N, 4, 4))):
+        if t.dtype != torch.float32 or tuple(t.shape) != tail:
+            raise ValueError(f"dvmvs::tsdf_integrate_frames: {label} must be float32 {list(tail)} for {N} frames, got {t.dtype} {tuple(t.shape)}")
+    if rgb_u8 is not None and (rgb_u8.dtype != torch.uint8 or tuple(rgb_u8.shape) != (N, h, w, 3)):
+        raise ValueError(f"dvmvs::tsdf_integrate_frames: rgb_u8 must be uint8 [{N},{h},{w},3] like depth, got {rgb_u8.dtype} {tuple(rgb_u8.shape)}")
+    if folded is not None and (folded.dtype != torch.float32 or tuple(folded.shape) != (N, h, w)):
+        raise ValueError(f"dvmvs::tsdf_integrate_frames: folded must be float32 [{N},{h},{w}] like depth, got {folded.dtype} {tuple(folded.shape)}")
+    if hasattr(obs_weight, "tolist"):       # a numpy array or a tensor (one download, not one per element): a 0-d one becomes a number
+        obs_weight = obs_weight.tolist()
+    weights = [float(x) for x in obs_weight] if isinstance(obs_weight, (list, tuple)) else [float(obs_weight)] * N
+    if len(weights) != N:
+        raise ValueError(f"dvmvs::tsdf_integrate_frames: {len(weights)} observation weights for {N} frames")
+    voxel_size, max_depth = float(voxel_size), float(max_depth)
+    trunc_margin = 5.0 * voxel_size if trunc_margin is None else float(trunc_margin)
+    if not voxel_size > 0.0 or not trunc_margin > 0.0 or max_depth != max_depth:
+        raise ValueError(f"dvmvs::tsdf_integrate_frames: voxel_size and trunc_margin must be positive and max_depth not NaN, got "
+                         f"{voxel_size}, {trunc_margin}, {max_depth}")
+    origin = [float(o) for o in origin]
+    if len(origin) != 3:
+        raise ValueError("dvmvs::tsdf_integrate_frames: origin must have three components")
+    dev = tsdf.device
+    for label, t in tensors:
+        if t.device.type != "cuda":
+            _no_cpu("tsdf_integrate_frames")
+        if t.device != dev or not t.is_contiguous():
+            raise ValueError(f"dvmvs::tsdf_integrate_frames: {label} must be contiguous and on {dev} like tsdf (got {t.device}, "
+                             f"contiguous={t.is_contiguous()})")
+    counters = None
+    if torch.is_tensor(stats):
+        if stats.device != dev or stats.dtype != torch.int64 or tuple(stats.shape) != (2,) or not stats.is_contiguous():
+            raise ValueError(f"dvmvs::tsdf_integrate_frames: stats must be a contiguous int64 [2] tensor on {dev}")
+        counters = stats
+    elif stats:
+        counters = torch.zeros(2, dtype=torch.int64, device=dev)
+    X, Y, Z = (int(d) for d in tsdf.shape)
+    workspace = tsdf_integrate_frames_workspace(dev, N)
+    with torch.cuda.device(dev):
+        rc = _capi.lib().dvmvs_tsdf_integrate_frames(
+            _ptr(tsdf), _ptr(weight), _ptr(color), X, Y, Z, origin[0], origin[1], origin[2], voxel_size, _ptr(cam_intr), _ptr(cam_pose),
+            None if rgb_u8 is None else _ptr(rgb_u8), None if folded is None else _ptr(folded), _ptr(depth), N, h, w, trunc_margin,
+            _capi.float_array(weights), max_depth, _ptr(workspace), None if counters is None else _ptr(counters), _stream(tsdf))
+    _capi.check(rc, "dvmvs_tsdf_integrate_frames")
+    return counters

@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from dvmvs.config import Config
-from dvmvs.dataset_loader import FrameUploader, PreprocessImage, load_depth_png, load_depth_png_u16, load_image, load_image_u8
+from dvmvs.dataset_loader import (FrameUploader, PreprocessImage, load_depth_png, load_depth_png_u16, load_image, load_image_u8,
+                                  resize_nearest)
 from dvmvs.engine import DepthEngine
 from dvmvs.keyframe_buffer import KeyframeBuffer
 from dvmvs.utils import InferenceTimer
@@ -182,20 +183,28 @@ class SceneResults:
     """What a scene run returns, by one of three routes chosen here: the host route (the prediction is fetched per frame, the ground truth
     pre-processed with numpy), ``device_preprocess`` alone (the ground truth is pre-processed on the device and fetched together with the
     prediction) and ``device_evaluate`` (a DeviceEvaluation: nothing is fetched before ``finish``).  ``frames``: the run's FrameInput
-    (scene, device, uploader); ``capacity``: the number of predictions, or the block size where it is not known."""
+    (scene, device, uploader); ``capacity``: the number of predictions, or the block size where it is not known.
+    ``fuse``: a ``dvmvs.tsdf.LiveFusion`` (or None): every prediction is also handed to ``fuse.add`` where it lies on the device, with the
+    inputs ``dvmvs.tsdf.run`` would read back from files -- the pre-processor's updated intrinsics, the frame's pose as float32 and the
+    frame's colour resized (nearest) to the prediction size as 8-bit.  ``add`` enqueues and returns: no route waits longer for it."""
 
-    def __init__(self, frames, evaluate, device_evaluate, capacity, error_log=None):
-        self.frames, self.error_log = frames, error_log
+    def __init__(self, frames, evaluate, device_evaluate, capacity, error_log=None, fuse=None):
+        self.frames, self.error_log, self.fuse = frames, error_log, fuse
         self.want_depth = bool(evaluate and frames.scene.depth_names)
         self.evaluation = None
         if device_evaluate:
             self.evaluation = DeviceEvaluation(frames.device, self.want_depth, frames.uploader is not None, capacity)
         self.predictions, self.reference_depths = [], []
 
-    def begin(self, pre, reference_index):
-        """Before the timed region: enqueues the ground truth of the frame (``pre``: its PreprocessImage) where the route has it on the device."""
+    def begin(self, pre, reference_index, raw=None):
+        """Before the timed region: enqueues the ground truth of the frame (``pre``: its PreprocessImage) where the route has it on the device.
+        ``raw``: the frame as the scene decoded it, when the caller has it (used by ``fuse`` only: no image is decoded twice)."""
         scene, device, uploader = self.frames.scene, self.frames.device, self.frames.uploader
         self.pre, self.reference_index, self.slot, self.depth_on_device = pre, reference_index, None, None
+        if self.fuse is not None:       # the colour dvmvs.tsdf.run integrates: crop window (if any), nearest resize, 8 bits
+            raw = scene.image(reference_index) if raw is None else raw
+            self.fuse_colour = np.ascontiguousarray(resize_nearest(pre._crop(raw) if pre.perform_crop else raw, pre.new_width,
+                                                                   pre.new_height).astype(np.uint8))
         if self.evaluation is not None:
             self.slot = self.evaluation.next_slot(pre.new_height, pre.new_width)
             if self.want_depth and uploader is not None:
@@ -207,6 +216,9 @@ class SceneResults:
 
     def add(self, depth):
         """After the timed region: the network's depth [1,1,h,w] (a static buffer is fine: it is copied or fetched here)."""
+        if self.fuse is not None:
+            self.fuse.add(depth, self.fuse_colour, self.pre.get_updated_intrinsics(),
+                          self.frames.scene.poses[self.reference_index].astype(np.float32))
         if self.evaluation is not None:              # prediction, ground truth and metrics stay on the device: nothing waits here
             self.evaluation.commit(self.slot, depth)
             return
@@ -251,7 +263,7 @@ def _run_frame(engine, frames, results, timer, indices, upcoming=None):
         else:
             meas_images.append(frames.image(pre, m))
         meas_poses.append(scene.pose(m))
-    results.begin(pre, reference_index)
+    results.begin(pre, reference_index, raw=raw)
     timer.record_start_time()
     ahead = {}
     if upcoming is not None:      # the next reference image and its poses: the engine then also runs its sweep + encoder a frame ahead
@@ -264,7 +276,7 @@ def _run_frame(engine, frames, results, timer, indices, upcoming=None):
 
 
 def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, evaluate=True, max_frames=None, frame_log=None,
-                    device_preprocess=False, device_evaluate=False, error_log=None):
+                    device_preprocess=False, device_evaluate=False, error_log=None, fuse=None):
     """Runs the lines of a keyframe index file ("ref meas1 meas2 ..." or "TRACKING LOST") through ``engine``.
     ``frame_log`` (a list) receives the line each prediction belongs to: "ref meas1 ..." file names, or "TRACKING LOST".
     ``device_preprocess``: frames are loaded as 8-bit images, uploaded through a ring of pinned buffers and cropped / resized / normalised
@@ -274,10 +286,12 @@ def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, eval
     up without a blocking copy, one dvmvs.hip.ops.depth_errors launch per frame writes its eight metrics into a device table, the timer
     is the deferred one, and nothing waits for the device inside the loop; ONE download after it fetches everything (DeviceEvaluation).
     ``error_log`` (a list) then receives one float32 [8] row per prediction (``save_results(..., errors=error_log)``); it stays empty
-    without ground truth or with ``evaluate=False``.  Default False: today's path, unchanged."""
+    without ground truth or with ``evaluate=False``.  Default False: today's path, unchanged.
+    ``fuse``: a ``dvmvs.tsdf.LiveFusion``: every prediction is also fused into its TSDF volume as it is made (``SceneResults``); after
+    the run ``fuse.volume`` is the reconstruction.  "TRACKING LOST" lines do not touch it.  Default None: nothing changes."""
     frames = FrameInput(scene_folder, engine.device, device_preprocess)
     index = KeyframeIndex(keyframe_index_file, frames.scene.image_names, max_frames)
-    results = SceneResults(frames, evaluate, device_evaluate, index.n_predictions, error_log)
+    results = SceneResults(frames, evaluate, device_evaluate, index.n_predictions, error_log, fuse)
     timer = InferenceTimer(deferred=device_evaluate)
     engine.new_sequence()
     for line, indices, upcoming in index:     # ``upcoming``: the index file says which keyframe is next (look-ahead)
@@ -291,15 +305,15 @@ def predict_offline(engine: DepthEngine, scene_folder, keyframe_index_file, eval
 
 
 def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames=None, frame_log=None, device_preprocess=False,
-                   device_evaluate=False, error_log=None):
+                   device_evaluate=False, error_log=None, fuse=None):
     """Feeds every frame of the scene to a KeyframeBuffer and predicts depth for the frames it accepts as keyframes.
     ``frame_log`` (a list) receives, in index-file syntax, what the buffer decided: one "ref meas1 ..." line per prediction and
     "TRACKING LOST" where it cleared itself -- the lines simulate_keyframe_index would write for the same poses.
     ``device_preprocess``, ``device_evaluate`` and ``error_log`` as in ``predict_offline``; the number of predictions is not known in
-    advance here, so the device stack grows in blocks of 32 frames."""
+    advance here, so the device stack grows in blocks of 32 frames.  ``fuse`` as in ``predict_offline``."""
     frames = FrameInput(scene_folder, engine.device, device_preprocess)
     scene = frames.scene
-    results = SceneResults(frames, evaluate, device_evaluate, 32, error_log)
+    results = SceneResults(frames, evaluate, device_evaluate, 32, error_log, fuse)
     timer = InferenceTimer(deferred=device_evaluate)
     buffer = KeyframeBuffer(buffer_size=Config.test_keyframe_buffer_size, keyframe_pose_distance=Config.test_keyframe_pose_distance,
                             optimal_t_score=Config.test_optimal_t_measure, optimal_R_score=Config.test_optimal_R_measure,
@@ -321,11 +335,13 @@ def predict_online(engine: DepthEngine, scene_folder, evaluate=False, max_frames
     return results.finish(timer)
 
 
-def predict_sharded(make_engine, scene_folders, keyframe_index_files, evaluate=True, max_frames=None, rank=None, world=None):
+def predict_sharded(make_engine, scene_folders, keyframe_index_files, evaluate=True, max_frames=None, rank=None, world=None, fuse=None):
     """BASELINE.json configs[3]: independent scenes sharded over the ranks of one node (scene ``s`` belongs to rank
     ``s % world``, dvmvs.sharding), each run through ``predict_offline`` on this rank's engine; no data-path collective.
     ``make_engine()`` builds the rank's DepthEngine lazily (a rank that owns no scene builds none).  Returns
-    ({scene number: (predictions, reference depths or None, InferenceTimer)}, (frames, seconds, frames/s) of the whole job)."""
+    ({scene number: (predictions, reference depths or None, InferenceTimer)}, (frames, seconds, frames/s) of the whole job).
+    ``fuse``: a factory ``fuse(s)`` -> the ``dvmvs.tsdf.LiveFusion`` of scene number ``s`` (or None for that scene), called on the rank that
+    owns the scene; the caller keeps the objects it hands out and reads their volumes after the job."""
     import time
 
     from dvmvs.sharding import reduce_throughput, run_sharded
@@ -336,7 +352,8 @@ def predict_sharded(make_engine, scene_folders, keyframe_index_files, evaluate=T
     def run_scene(s):
         if state["engine"] is None:
             state["engine"] = make_engine()
-        return predict_offline(state["engine"], scene_folders[s], keyframe_index_files[s], evaluate=evaluate, max_frames=max_frames)
+        return predict_offline(state["engine"], scene_folders[s], keyframe_index_files[s], evaluate=evaluate, max_frames=max_frames,
+                               fuse=fuse(s) if fuse is not None else None)
 
     t0 = time.perf_counter()
     results = run_sharded(len(scene_folders), run_scene, rank=rank, world=world)

@@ -121,7 +121,8 @@ class TSDFVolume:
         if torch.is_tensor(color_im) and color_im.dim() == 2:
             color = color_im.to(dev, torch.float32).contiguous()            # already folded
         else:
-            color = torch.from_numpy(fold_color(color_im.cpu().numpy() if torch.is_tensor(color_im) else color_im)).to(dev)
+            # (contiguous: an image that numpy indexing produced, e.g. by resize_nearest, is not row-major, and neither is its fold)
+            color = torch.from_numpy(np.ascontiguousarray(fold_color(color_im.cpu().numpy() if torch.is_tensor(color_im) else color_im))).to(dev)
         if color.shape != depth.shape:
             raise ValueError(f"colour {tuple(color.shape)} and depth {tuple(depth.shape)} images differ in size")
         K = torch.as_tensor(np.asarray(cam_intr, dtype=np.float32) if not torch.is_tensor(cam_intr) else cam_intr,
@@ -138,6 +139,49 @@ class TSDFVolume:
                 torch.cuda.current_stream(dev).cuda_stream)
         self._raycast_mask = None      # (before the check: a failed call may have been enqueued)
         _capi.check(rc, "dvmvs_tsdf_integrate")
+
+    def integrate_frames(self, color_ims, depth_ims, cam_intr, cam_poses, obs_weight=1.0, max_depth=float("inf"), stats=False):
+        """Fuses N frames with ONE pass over the volume (``dvmvs.hip.ops.tsdf_integrate_frames``, csrc/tsdf_fuse.hip): the same bits as
+        ``integrate`` called for frame 0, 1, ... N-1, after ``depth[depth > max_depth] = 0``.  ``color_ims`` [N,H,W,3] uint8 RGB or
+        [N,H,W] folded colour, ``depth_ims`` [N,H,W] metres, ``cam_intr`` [3,3] or [N,3,3], ``cam_poses`` [N,4,4] camera-to-world,
+        ``obs_weight`` one number or N; numpy arrays or tensors.  Contiguous device tensors of the kernel's types (float32; uint8 colour)
+        are used in place: no copy and no synchronisation.  ``stats`` as in the op (tile counters, for tests and benchmarks)."""
+        from dvmvs.hip import ops
+        dev = self.device
+
+        def as_dev(a, dtype):
+            if torch.is_tensor(a):
+                return a.to(dev, dtype).contiguous()     # the same tensor when it is already there in that type
+            return torch.as_tensor(np.ascontiguousarray(a, dtype={torch.float32: np.float32, torch.uint8: np.uint8}[dtype]), device=dev)
+
+        depth = as_dev(depth_ims, torch.float32)
+        if depth.dim() != 3:
+            raise ValueError(f"depth images must be [N,H,W], got {tuple(depth.shape)}")
+        n = depth.shape[0]
+        colour_dims = color_ims.dim() if torch.is_tensor(color_ims) else np.ndim(color_ims)
+        if colour_dims == 4:
+            is_u8 = color_ims.dtype == (torch.uint8 if torch.is_tensor(color_ims) else np.uint8)
+            if is_u8:
+                rgb, folded = as_dev(color_ims, torch.uint8), None
+            else:         # float RGB, as ``integrate`` accepts it: folded on the host
+                host = color_ims.cpu().numpy() if torch.is_tensor(color_ims) else np.asarray(color_ims)
+                rgb, folded = None, torch.from_numpy(np.stack([fold_color(c) for c in host])).to(dev)
+        elif colour_dims == 3:
+            rgb, folded = None, as_dev(color_ims, torch.float32)
+        else:
+            raise ValueError("colour images must be [N,H,W,3] RGB or [N,H,W] folded")
+        colour = rgb if rgb is not None else folded
+        if tuple(colour.shape[:3]) != tuple(depth.shape):
+            raise ValueError(f"colour {tuple(colour.shape)} and depth {tuple(depth.shape)} images differ in size")
+        K, P = as_dev(cam_intr, torch.float32), as_dev(cam_poses, torch.float32)
+        if K.dim() == 2:
+            K = K.unsqueeze(0).expand(n, 3, 3).contiguous()
+        if tuple(K.shape) != (n, 3, 3) or tuple(P.shape) != (n, 4, 4):
+            raise ValueError(f"expected intrinsics [3,3] or [{n},3,3] and poses [{n},4,4], got {tuple(K.shape)} and {tuple(P.shape)}")
+        self._raycast_mask = None      # (before the call: a failed call may have been enqueued)
+        return ops.tsdf_integrate_frames(self._tsdf, self._weight, self._color, self._vol_origin, self._voxel_size, K, P, depth, rgb_u8=rgb,
+                                         folded=folded, trunc_margin=self._trunc_margin, obs_weight=obs_weight, max_depth=max_depth,
+                                         stats=stats)
 
     def render(self, cam_intr, cam_poses, height, width, near=0.0, far=float("inf"), step=1.0, normals=True, colour=True, skip_empty=True):
         """Ray-casts the volume from N views in one launch (csrc/tsdf_raycast.hip; definition in include/dvmvs_hip.h): ``cam_poses``
@@ -233,6 +277,14 @@ class TSDFFusion:
         return bounds
 
     @staticmethod
+    def frustum_bounds(poses, K, height, width, max_depth):
+        """``calculate_volume_bounds`` of depth maps that are ``max_depth`` everywhere, without the maps: the bounds of every view's frustum
+        cut at ``max_depth`` (and of the world origin, as there).  They contain the bounds of any depth maps <= ``max_depth`` seen from the
+        same poses, so a live run can size its volume before a depth exists."""
+        constant = np.full((int(height), int(width)), max_depth)
+        return TSDFFusion.calculate_volume_bounds([constant] * len(poses), poses, K)
+
+    @staticmethod
     def _columns(formats, columns):
         """Rows of space-separated, %-formatted columns, each ending in a newline: one string, built without a Python loop
         over the rows (np.char formats each column element with the same % operator a per-row write uses)."""
@@ -283,6 +335,95 @@ class TSDFFusion:
         print("Average FPS: {:.2f}".format(n / max(time.time() - start, 1e-9)))
         print("Saving mesh to", mesh_name)
         TSDFFusion.meshwrite(mesh_name + "_complete.ply", *tsdf_volume.get_mesh())
+
+
+class LiveFusion:
+    """Fuses depth maps into a TSDF volume WHILE a scene runs: ``add`` takes the network's depth where it lies on the device and returns
+    at once; every ``batch`` frames one ``TSDFVolume.integrate_frames`` launch fuses them (one pass over the volume; the bits of per-frame
+    ``integrate`` on depths with ``depth > max_depth`` set to 0).  ``volume`` is the reconstruction at any moment, ready for ``get_mesh()``,
+    ``render(...)`` and ``get_point_cloud()``.
+
+    ``add`` enqueues and returns: the depth is copied device-to-device on the current stream into the next slot of a ring [batch,h,w] (the
+    engine's output buffer is static and the next frame overwrites it); the intrinsics, the pose and a host colour image go up together
+    through one slot of a ring of 8 pinned buffers with one non-blocking copy (``FrameUploader``) and from there into their rings
+    [batch,3,3], [batch,4,4], [batch,h,w,3].  It never waits for the device to finish work of the CURRENT frame; the one wait it can
+    make is ``FrameUploader``'s, before a pinned slot is written again, for the upload that last read that slot -- the one of 8 ``add``
+    calls earlier.  So the host runs at most 8 frames ahead of the device's copy queue, and no further.  (That wait is on an event, which
+    torch's synchronisation detector does not see.)
+    ASSUMPTION: every call (``add``, ``flush``, ``volume`` and whatever uses the volume) is issued on ONE stream.  Everything is then in
+    stream order -- a ring slot is rewritten only by copies enqueued after the launch that read it -- so no event guards the rings."""
+
+    def __init__(self, vol_bnds, voxel_size=0.025, max_depth=5.0, batch=8, device="cuda"):
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f"LiveFusion: batch must be at least 1, got {batch}")
+        if not float(voxel_size) > 0.0:
+            raise ValueError(f"LiveFusion: voxel_size must be positive, got {voxel_size}")
+        if float(max_depth) != float(max_depth):
+            raise ValueError("LiveFusion: max_depth is NaN")
+        from dvmvs.dataset_loader import FrameUploader
+        self.batch, self.max_depth = batch, float(max_depth)
+        self._volume = TSDFVolume(vol_bnds, voxel_size, device=device)
+        self.device = self._volume._tsdf.device      # with its index ("cuda" -> "cuda:0"): what a tensor's ``.device`` compares equal to
+        self._uploader = FrameUploader(self.device, slots=8)
+        self._depth = self._rgb = self._K = self._P = None
+        self._weights, self._pending, self.frames = [], 0, 0
+
+    def _rings(self, h, w):
+        if self._depth is None:
+            dev = self.device
+            self._depth = torch.empty((self.batch, h, w), dtype=torch.float32, device=dev)
+            self._rgb = torch.empty((self.batch, h, w, 3), dtype=torch.uint8, device=dev)
+            self._K = torch.empty((self.batch, 3, 3), dtype=torch.float32, device=dev)
+            self._P = torch.empty((self.batch, 4, 4), dtype=torch.float32, device=dev)
+        elif tuple(self._depth.shape[1:]) != (h, w):
+            raise ValueError(f"LiveFusion: a {h}x{w} frame in a run of {self._depth.shape[1]}x{self._depth.shape[2]} frames")
+
+    def add(self, depth, rgb_u8, K, pose, obs_weight=1.0):
+        """``depth``: float32 device tensor with h * w elements in its last two dimensions ([h,w], [1,h,w], [1,1,h,w]); ``rgb_u8``
+        [h,w,3] uint8 (numpy, host or device tensor); ``K`` [3,3] and camera-to-world ``pose`` [4,4] (numpy or host tensors)."""
+        if not torch.is_tensor(depth) or depth.device != self.device or depth.dtype != torch.float32 or depth.dim() < 2:
+            raise ValueError(f"LiveFusion.add: depth must be a float32 tensor on {self.device}")
+        h, w = int(depth.shape[-2]), int(depth.shape[-1])
+        if depth.numel() != h * w:
+            raise ValueError(f"LiveFusion.add: one depth map at a time, got {tuple(depth.shape)}")
+        if tuple(rgb_u8.shape) != (h, w, 3) or rgb_u8.dtype != (torch.uint8 if torch.is_tensor(rgb_u8) else np.uint8):
+            raise ValueError(f"LiveFusion.add: colour must be uint8 [{h},{w},3] like the depth, got {rgb_u8.dtype} {tuple(rgb_u8.shape)}")
+        matrices = np.concatenate([np.asarray(K, dtype=np.float32).reshape(9), np.asarray(pose, dtype=np.float32).reshape(16)])
+        self._rings(h, w)
+        slot = self._pending
+        self._depth[slot].copy_(depth.reshape(h, w), non_blocking=True)
+        staged = matrices.view(np.uint8)             # 100 bytes first, so the floats are aligned; a host colour image goes behind them
+        if torch.is_tensor(rgb_u8) and rgb_u8.device.type != "cpu":
+            self._rgb[slot].copy_(rgb_u8, non_blocking=True)
+        else:
+            host = rgb_u8.numpy() if torch.is_tensor(rgb_u8) else rgb_u8
+            staged = np.concatenate([staged, np.ascontiguousarray(host).reshape(-1)])
+        staged = self._uploader.upload(staged)       # ONE pinned slot and one host-to-device copy per frame
+        if staged.numel() > 100:
+            self._rgb[slot].copy_(staged[100:].view(h, w, 3), non_blocking=True)
+        floats = staged[:100].view(torch.float32)
+        self._K[slot].copy_(floats[:9].view(3, 3), non_blocking=True)
+        self._P[slot].copy_(floats[9:].view(4, 4), non_blocking=True)
+        self._weights.append(float(obs_weight))
+        self._pending += 1
+        self.frames += 1
+        if self._pending == self.batch:
+            self.flush()
+
+    def flush(self):
+        """Fuses the frames that are pending (fewer than ``batch``); nothing happens when there is none."""
+        n = self._pending
+        if n == 0:
+            return
+        self._volume.integrate_frames(self._rgb[:n], self._depth[:n], self._K[:n], self._P[:n], obs_weight=self._weights,
+                                      max_depth=self.max_depth)
+        self._weights, self._pending = [], 0
+
+    @property
+    def volume(self):
+        self.flush()
+        return self._volume
 
 
 def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dataset_name, scene_name):

@@ -49,7 +49,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_depth_errors_* (depth evaluation on the device); no earlier signature changed, the number stays 11 by the
  * same rule.
  * ABI 11, later addition: dvmvs_tsdf_raycast_* (ray-casting a fused TSDF volume from camera views); no earlier signature changed, the
- * number stays 11 by the same rule. */
+ * number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_tsdf_integrate_frames* (fusing a batch of frames into a TSDF volume in one launch); no earlier signature
+ * changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -643,6 +645,39 @@ int dvmvs_tsdf_raycast_fwd(const float* tsdf_vol, const float* weight_vol, const
                            float origin_x, float origin_y, float origin_z, float voxel_size, const unsigned char* mask,
                            const float* cam_intr, const float* cam_pose, int n_views, int im_h, int im_w, float near, float far, float step,
                            float* depth, float* normal, unsigned char* rgb, dvmvs_stream_t stream);
+
+/*
+ * TSDF fusion of a batch of frames (ABI 11, later addition): dvmvs_tsdf_integrate applied to n_frames frames in index order, in ONE pass
+ * over the volume, with the SAME BITS as n_frames calls of dvmvs_tsdf_integrate: a thread owns its voxels for the launch, loads them once,
+ * applies the frames 0..n_frames-1 in registers with that kernel's float32 statements and stores a voxel only if a frame updated it.
+ *   tsdf_vol, weight_vol, color_vol, dim_*, origin_*, voxel_size, trunc_margin   as dvmvs_tsdf_integrate
+ *   cam_intr [n_frames,3,3], cam_pose [n_frames,4,4] camera-to-world, depth [n_frames,im_h,im_w] fp32 metres   (device pointers)
+ *   rgb_u8 [n_frames,im_h,im_w,3] uint8 RGB or NULL; folded [n_frames,im_h,im_w] fp32 (b * 65536 + g * 256 + r) or NULL   (device pointers):
+ *                           exactly one of the two; 8-bit colour is folded in the kernel, exactly
+ *   obs_weight_host         HOST array of n_frames weights, read during the call (it travels in the kernel arguments)
+ *   max_depth               a depth > max_depth counts as 0 (invalid); +inf = no clamp; a NaN depth stays NaN and, as in the dense kernel,
+ *                           is integrated with dist = 1
+ *   workspace               dvmvs_tsdf_integrate_frames_workspace_bytes(n_frames) bytes on the device, 4-byte aligned, written by a first
+ *                           kernel of the call (the largest clamped depth of every frame) and read by the fusion kernel: no host read.  Calls
+ *                           that share it must be ordered (one stream)
+ *   tile_stats              device long long[2] or NULL; when given, the call ADDS to element 0 the number of (tile, frame) pairs its
+ *                           culling kept and to element 1 the number of tiles that loaded the volume (integer atomics, one thread per
+ *                           workgroup).  For tests and benchmarks
+ * The volume is cut into tiles, one workgroup each.  A frame is dropped for a tile only when no voxel of the tile can pass that frame's
+ * per-voxel tests (behind the camera, outside the four image sides, beyond the frame's largest depth + trunc_margin), with margins that
+ * cover the float32 error of the per-voxel projection (derivation in csrc/tsdf_fuse.hip); a tile that no frame can touch makes no volume
+ * access.  A launch takes 64 frames; more are split into consecutive launches in frame order by the call.
+ * dvmvs_tsdf_integrate_frames_workspace_bytes: host only, no HIP call; 0 for n_frames <= 0, non-decreasing in n_frames.
+ * Returns DVMVS_EINVAL for a null tsdf_vol / weight_vol / color_vol / cam_intr / cam_pose / depth / obs_weight_host / workspace, both or neither
+ * of rgb_u8 and folded, a dimension, image size or n_frames < 1, voxel_size or trunc_margin <= 0, a NaN max_depth; DVMVS_EUNSUPPORTED for
+ * dim_y * dim_z >= 2^31, im_h * im_w >= 2^31, n_frames > 65535 or 2^31 tiles or more.  Nothing is enqueued in either case.
+ */
+size_t dvmvs_tsdf_integrate_frames_workspace_bytes(int n_frames);
+int dvmvs_tsdf_integrate_frames(float* tsdf_vol, float* weight_vol, float* color_vol, int dim_x, int dim_y, int dim_z, float origin_x,
+                                float origin_y, float origin_z, float voxel_size, const float* cam_intr, const float* cam_pose,
+                                const unsigned char* rgb_u8, const float* folded, const float* depth, int n_frames, int im_h, int im_w,
+                                float trunc_margin, const float* obs_weight_host, float max_depth, void* workspace, long long* tile_stats,
+                                dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
