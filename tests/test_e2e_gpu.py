@@ -175,6 +175,39 @@ def test_fusionnet_frames_from_the_reference_state(hip_device, golden_dir, mode,
     assert checked == 17
 
 
+def test_all_tiled_engine_sweeps_from_work_lists(hip_device, golden_dir, monkeypatch, fixture_host_algebra):
+    """DVMVS_SWEEP_MFMA=0 (read in DepthEngine.__init__): the engine keeps NCHW measurement maps and every frame's sweep is the LDS-tiled kernel launched
+    from the host-planned work list (variants 2 / 3 / 4 / 5; tests/test_sweep_work_list_gpu.py at op level).  Teacher-forced over the 3 golden frames it
+    meets the bound every other engine mode meets, and a second engine built the same way repeats every depth map bit for bit."""
+    dev = hip_device
+    monkeypatch.setenv("DVMVS_SWEEP_MFMA", "0")
+    z3 = np.load(os.path.join(golden_dir, "fusionnet_e2e.npz"))
+    state = np.load(os.path.join(golden_dir, "fusionnet_state.npz"))
+    runs = []
+    for _ in range(2):
+        mods, engine = build(dev, fusion=True, fold_bn=True, cache_features=True, use_graphs=True)
+        assert not engine.sweep_mfma and engine.sweep_work_list
+        depths, step = [], engine.step
+
+        def recording_step(*args, _step=step, _depths=depths, **kw):
+            depth = _step(*args, **kw)
+            _depths.append(depth.clone())
+            return depth
+
+        monkeypatch.setattr(engine, "step", recording_step)
+        rows = run_teacher_forced(engine, dev, "f", list(syn.E2E_FRAMES), state, lambda n: z3[f"f{n}_depth_estimation_full"])
+        assert len(rows) == len(depths) == 3
+        for n, vs_reference, flipped in rows:
+            print("all-tiled engine, step %d: depth rel-L1 vs the reference %.3e, flipped estimate pixels %d; sweep variants so far %s"
+                  % (n, vs_reference, flipped, engine.sweep_variant_counts))
+            assert vs_reference <= REL_L1_TARGET, (n, vs_reference)
+            assert flipped == 0, (n, flipped)
+        assert engine.sweep_variant_counts and set(engine.sweep_variant_counts) <= {2, 3, 4, 5}, engine.sweep_variant_counts
+        runs.append(depths)
+    for n, (a, b) in enumerate(zip(*runs)):
+        assert torch.equal(a, b), n
+
+
 def test_fusionnet_long_reference_run(hip_device, golden_dir, fixture_host_algebra):
     """Free-running engine as benchmarked (BN folded, feature cache, hipGraph replay) over the REFERENCE's 14-keyframe run
     (tests/golden/fusionnet_long.npz).  Per frame: depth rel-L1 vs the reference and the number of low-resolution estimate pixels

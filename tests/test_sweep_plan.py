@@ -289,3 +289,47 @@ def test_plan6_takes_every_single_item_pair_and_no_batch():
                                allow_mfma=True)
     assert both in (2, 3, 4, 5)
     assert lib.dvmvs_sweep_mfma_estimate(None, kt.contiguous().data_ptr(), 1, 2, H, W, D, 0.25, 20.0, (ctypes.c_double * 4)()) == -1
+
+
+def test_work_list_cases_of_the_gpu_tests_have_what_they_are_there_for():
+    """The plans tests/test_sweep_work_list_gpu.py launches (tests/sweep_lists.py: PLAN_CASES), checked where no GPU is needed: every list partitions
+    (batch, tile, plane); the cases that are there for their cuts have more items than static positions and items that start off a multiple of 8; the
+    full shape brings back all four tiled variants; the forced plan of line 170 has 2-plane pieces; the tiny shape has 0-plane padding positions (20
+    pairs in 24 positions); the ragged shapes have a short last chunk; a batch's list is its items' lists, with the batch item in bits 16 and up; the
+    hand-made halved list fits the buffer and partitions too."""
+    import sweep_lists as sl
+    variants = {}
+    for name, ((shape, k_scale), line, forced, cuts) in sl.PLAN_CASES.items():
+        B, C, Hc, Wc, Dc, M = shape
+        Hm, kt = sl.matrices([line], k_scale)
+        variant, words = sl.planned(Hm, kt, Hc, Wc, Dc, forced)
+        n, items = sl.parse(words)
+        static = sl.static_positions(B, Hc, Wc, Dc)
+        sizes = items[:, 1] >> 16
+        assert (sl.coverage(items, B, Hc, Wc, Dc) == 1).all(), name
+        assert variant in (2, 3, 4, 5) and (forced == 0 or variant == forced), (name, variant)
+        if cuts:
+            assert static < n <= 2 * static and ((items[:, 1] & 0xffff) % 8 != 0).any(), (name, n, static)
+        else:
+            assert n == static and (sizes == 8).all(), (name, n)
+        assert int((sizes == 0).sum()) == static - B * np.prod(sl.tiles_and_chunks(Hc, Wc, Dc)), name       # only padding positions are empty
+        if Dc % 8:
+            assert (sizes[(items[:, 1] & 0xffff) + sizes == Dc] < 8).all(), name                             # the ragged last chunk
+        variants[name] = variant
+        print(f"{name}: variant {variant}, {n} items against {static} static positions, plane counts {sorted(set(sizes.tolist()))}")
+    assert {v for name, v in variants.items() if name.startswith("full-")} == {2, 3, 4, 5}
+    assert variants["full-0"] == 4 and variants["full-117"] == 4                                             # single pass without and WITH cuts
+    n, items = sl.parse(sl.planned(*sl.matrices([170], 2.0), H, W, D, 2)[1])
+    assert (items[:, 1] >> 16 == 2).any()
+    n, items = sl.parse(sl.planned(*sl.matrices([170], 320.0 / 47), 33, 47, 10, 2)[1])
+    assert n > sl.static_positions(1, 33, 47, 10) == 24 and int((items[:24, 1] >> 16 == 0).sum()) == 4
+    for forced in (0, 2):
+        variant, words = sl.planned(*sl.matrices([0, 170, 202], 2.0), H, W, D, forced)
+        n, items = sl.parse(words)
+        assert variant == (2 if forced else 3)
+        assert (sl.coverage(items, 3, H, W, D) == 1).all() and set((items[:, 0] >> 16).tolist()) == {0, 1, 2}
+        assert n == sum(sl.parse(sl.planned(*sl.matrices([line], 2.0), H, W, D, variant)[1])[0] for line in (0, 170, 202)) > 1920
+    for shape in ((1, H, W, D), (1, 61, 83, 37), (3, 33, 47, 10)):
+        n, items = sl.parse(sl.halved(*shape))
+        assert (sl.coverage(items, *shape) == 1).all() and sl.static_positions(*shape) <= n + 7 and n <= 2 * sl.static_positions(*shape)
+        assert ((items[:, 1] >> 16) <= 4).all() and ((items[:, 1] & 0xffff) % 8 != 0).any()

@@ -4,7 +4,7 @@ rotations up to 15 degrees about a random axis, focal lengths +- 30 % -- at the 
 Since round 6 ``dvmvs_sweep_plan6`` gives every single-item launch to variant 6 (the correlate-then-interpolate sweep in its persistent form with
 gather passes, csrc/sweep_mfma.hip) instead of choosing between it and the LDS-tiled sweep from thresholds fitted to one scene.  What is checked:
 * parity on every geometry: variant 6 against the reference-order generic kernel (summation-order round-off), no unwritten element, and
-  bit-identical to its one-item-per-workgroup form (variant 7);
+  bit-identical to its one-item-per-workgroup form (variant 7); where the generic kernel runs, the tiled plan launched from its work list too;
 * regret of "always variant 6": its duration against the tiled plan's (configuration + work list as dvmvs_sweep_plan makes them) on the same
   geometry -- never more than 1.3 x + 6 us (the bound the verdict asked of the selector), and the mean over all geometries not above the tiled one's.
 Semantics under test: /root/reference/dvmvs/utils.py:45-107."""
@@ -108,10 +108,16 @@ def test_variant_6_on_random_geometries_parity_and_regret(hip_device):
         assert not torch.isnan(six).any(), trial
         if trial % 4 == 0:      # (the generic kernel takes 100 - 200 us: every fourth geometry)
             launch(1, False)
-            assert float((six - out).abs().max()) < 3e-5, trial
+            generic = out.clone()
+            assert float((six - generic).abs().max()) < 3e-5, trial
             out.fill_(float("nan"))
             launch(7, False)
             assert torch.equal(six, out), trial
+            # the tiled plan with its work list -- what the regret part below only times: every element written, the same volume
+            out.fill_(float("nan"))
+            launch(tiled, True)
+            assert not torch.isnan(out).any(), (trial, tiled)
+            assert float((out - generic).abs().max()) < 3e-5, (trial, tiled)
             checked += 1
         # ---- regret ----
         a, b = microseconds(6, False), microseconds(tiled, True)
