@@ -146,4 +146,34 @@ __device__ inline BilinearTaps make_taps(float ix, float iy, int W, int H) {
 // grid_sample's align_corners=True un-normalisation, in the op order ATen uses: ((g + 1) / 2) * (size - 1)
 __device__ inline float unnormalize_ac(float g, int size) { return ((g + 1.0f) * 0.5f) * static_cast<float>(size - 1); }
 
+// ---- scans ------------------------------------------------------------------------------------------------------
+__device__ inline int wave_inclusive_scan(int x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  return x;
+}
+
+// Exclusive scan of one int per thread over a block of kBlock threads (a multiple of 64); `total` = the block's sum.  `lds` holds
+// kBlock / 64 ints.
+template <int kBlock = 256>
+__device__ inline int block_exclusive_scan(int v, int* lds, int& total) {
+  const int incl = wave_inclusive_scan(v);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) lds[wave] = incl;
+  __syncthreads();
+  int prefix = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < kBlock / 64; ++w) {
+    const int t = lds[w];
+    if (w < wave) prefix += t;
+    total += t;
+  }
+  return prefix + incl - v;
+}
+
 }  // namespace dvmvs

@@ -31,32 +31,7 @@ struct McGeom {
   long long plane;   // Y * Z
 };
 
-__device__ inline int wave_inclusive_scan(int x) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  return x;
-}
-
-// Exclusive scan of one int per thread over a 256-thread block; `total` = the block's sum.  `lds` holds 4 ints.
-__device__ inline int block_exclusive_scan(int v, int* lds, int& total) {
-  const int incl = wave_inclusive_scan(v);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 63) lds[wave] = incl;
-  __syncthreads();
-  int prefix = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kMcBlock / 64; ++w) {
-    const int t = lds[w];
-    if (w < wave) prefix += t;
-    total += t;
-  }
-  return prefix + incl - v;
-}
+// (wave_inclusive_scan / block_exclusive_scan: dvmvs_device.h, over kMcBlock = 256 threads)
 
 // Bits 0..2: the voxel's +x / +y / +z edge crosses the level.
 __device__ inline unsigned owned_mask(const float* __restrict__ vol, const McGeom& g, int i, int j, int k, long long idx, float level) {

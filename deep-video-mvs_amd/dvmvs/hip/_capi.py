@@ -120,6 +120,12 @@ SIGNATURES = {
     "dvmvs_tsdf_integrate_frames": (_c_int, [_c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                              ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float,
                                              _c_f3, ctypes.c_float, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_nearest_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "dvmvs_nearest_query_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "dvmvs_nearest_build": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_size_t, _c_stream]),
+    "dvmvs_nearest_distance_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_size_t, _c_fp, _c_fp,
+                                            _c_stream]),
+    "dvmvs_distance_metrics_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, ctypes.c_float, _c_fp, _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -131,6 +137,9 @@ ADDED_WITHIN_ABI_DEPTH_ERRORS = ("dvmvs_depth_errors_workspace_bytes", "dvmvs_de
 ADDED_WITHIN_ABI_TSDF_RAYCAST = ("dvmvs_tsdf_raycast_mask_bytes", "dvmvs_tsdf_raycast_mask", "dvmvs_tsdf_raycast_fwd")
 # ... and the fourth (fusing a batch of frames into a TSDF volume)
 ADDED_WITHIN_ABI_TSDF_FUSE = ("dvmvs_tsdf_integrate_frames_workspace_bytes", "dvmvs_tsdf_integrate_frames")
+# ... and the fifth (nearest-point distances between point clouds and the 3-D reconstruction metrics)
+ADDED_WITHIN_ABI_NEAREST = ("dvmvs_nearest_workspace_bytes", "dvmvs_nearest_query_workspace_bytes", "dvmvs_nearest_build",
+                            "dvmvs_nearest_distance_fwd", "dvmvs_distance_metrics_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -149,7 +158,8 @@ def lib():
                 f"dvmvs HIP library not found at {LIB_PATH}. Build it with `make -C deep-video-mvs_amd/csrc` "
                 f"(or __graft_entry__.build()). The plane-sweep ops have no CPU / eager fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        added = ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
+        added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
+                 + ADDED_WITHIN_ABI_NEAREST)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

@@ -9,6 +9,7 @@ import ctypes
 import os
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -16,7 +17,8 @@ from dvmvs.hip import _capi
 
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
            "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress", "preprocess_rgb",
-           "preprocess_depth", "depth_errors", "tsdf_raycast", "tsdf_raycast_mask", "tsdf_integrate_frames"]
+           "preprocess_depth", "depth_errors", "tsdf_raycast", "tsdf_raycast_mask", "tsdf_integrate_frames", "nearest_distance", "nearest_build",
+           "nearest_query", "distance_metrics"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1534,3 +1536,140 @@ def tsdf_integrate_frames(tsdf: Tensor, weight: Tensor, color: Tensor, origin: S
             _capi.float_array(weights), max_depth, _ptr(workspace), None if counters is None else _ptr(counters), _stream(tsdf))
     _capi.check(rc, "dvmvs_tsdf_integrate_frames")
     return counters
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# exact nearest-point distances between point clouds, and the 3-D reconstruction metrics they reduce to (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+_nearest_workspaces = {}
+
+
+def _grown_workspace(key, device, nbytes):
+    """The persistent buffer of ``key`` on ``device`` with room for ``nbytes``: grown to the largest request seen, never initialised.  A
+    buffer that is replaced is marked as in use on the current stream, so the allocator does not hand its memory out again before the
+    work enqueued there has read it."""
+    workspace = _nearest_workspaces.get(key)
+    if workspace is None or workspace.numel() < nbytes:
+        if workspace is not None:
+            workspace.record_stream(torch.cuda.current_stream(device))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _nearest_workspaces[key] = workspace
+    return workspace
+
+
+def nearest_distance_workspace(device, M):
+    """Persistent grid workspace of ``nearest_build`` per device: grown to the largest target cloud seen (its size follows from ``M`` alone)
+    and written by every build before a query reads it, so it needs no initialisation.  A build overwrites the grid of the build before
+    it: calls that share the workspace must be ordered with respect to each other (one stream per process), and a grid that has to
+    outlive the next build needs a buffer of its own (``nearest_build(target, workspace=...)``)."""
+    device = torch.device(device)
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    nbytes = _capi.lib().dvmvs_nearest_workspace_bytes(int(M))
+    if nbytes == 0:
+        raise ValueError(f"dvmvs::nearest_distance: a target cloud of {M} points is outside what the kernels take (1 .. 2^28)")
+    return _grown_workspace(("grid", index), device, nbytes)
+
+
+def _points(name, label, t):
+    if not torch.is_tensor(t):
+        raise TypeError(f"dvmvs::{name}: {label} must be a tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        _no_cpu(name)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"dvmvs::{name}: {label} must be float32 [n,3] points, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def nearest_build(target: Tensor, workspace: Optional[Tensor] = None) -> Tensor:
+    """Bins ``target`` (float32 [M,3] on the GPU, finite, M >= 1) into a uniform grid over its bounding box (csrc/nearest_points.hip) and
+    returns the workspace that holds it, for ``nearest_query``.  The box, the cell edge and the grid's dimensions are computed on the
+    device; the host sizes the workspace from M alone.  ``workspace``: a uint8 device tensor of at least
+    ``dvmvs_nearest_workspace_bytes(M)`` bytes to build into, instead of the per-device one of ``nearest_distance_workspace``.  Runs on
+    the current stream, no synchronisation."""
+    target = _points("nearest_build", "target", target)
+    M = int(target.shape[0])
+    if M < 1:
+        raise ValueError("dvmvs::nearest_build: the target cloud is empty")
+    if workspace is None:
+        workspace = nearest_distance_workspace(target.device, M)
+    elif (not torch.is_tensor(workspace) or workspace.device != target.device or workspace.dtype != torch.uint8 or not workspace.is_contiguous()
+          or workspace.numel() < _capi.lib().dvmvs_nearest_workspace_bytes(M)):
+        raise ValueError(f"dvmvs::nearest_build: workspace must be a contiguous uint8 tensor on {target.device} of at least "
+                         f"{_capi.lib().dvmvs_nearest_workspace_bytes(M)} bytes")
+    with torch.cuda.device(target.device):
+        rc = _capi.lib().dvmvs_nearest_build(_ptr(target), M, _ptr(workspace), workspace.numel(), _stream(target))
+    _capi.check(rc, "dvmvs_nearest_build")
+    return workspace
+
+
+def nearest_grid_header(workspace: Tensor) -> dict:
+    """The grid a ``nearest_build`` left in ``workspace``, DOWNLOADED (a synchronisation: for tests and tools, not for the hot path):
+    ``mn`` and ``mx`` float32 [3] (the targets' box), ``inv_h`` and ``h_lo`` float32, ``dim`` int32 [3], ``ncells``.  A coordinate x falls
+    into cell ``int((clamp(x, mn, mx) - mn) * inv_h)`` of its axis, every operation in float32 (include/dvmvs_hip.h)."""
+    words = workspace[:48].cpu().numpy()
+    floats, ints = words.view(np.float32), words.view(np.int32)
+    return {"mn": floats[0:3].copy(), "mx": floats[3:6].copy(), "inv_h": floats[6], "h_lo": floats[7], "dim": ints[8:11].copy(), "ncells": int(ints[11])}
+
+
+def nearest_query(query: Tensor, target: Tensor, workspace: Tensor, return_index: bool = False):
+    """Distances from ``query`` (float32 [N,3]) to the nearest point of ``target``, whose grid ``workspace`` holds (``nearest_build`` of the
+    SAME target tensor contents): float32 [N], and with ``return_index`` also int32 [N], the smallest index of a nearest target.  The
+    queries are binned in a per-device scratch buffer that every call reuses: like the grid workspace it assumes that the calls of a
+    process are ordered with respect to each other (one stream, or streams that wait for each other)."""
+    query, target = _points("nearest_query", "query", query), _points("nearest_query", "target", target)
+    N, M = int(query.shape[0]), int(target.shape[0])
+    if M < 1:
+        raise ValueError("dvmvs::nearest_query: the target cloud is empty")
+    if query.device != target.device or not torch.is_tensor(workspace) or workspace.device != target.device:
+        raise ValueError(f"dvmvs::nearest_query: query, target and workspace must be on one device, got {query.device}, {target.device}")
+    dist = torch.empty(N, dtype=torch.float32, device=query.device)
+    index = torch.empty(N, dtype=torch.int32, device=query.device) if return_index else None
+    if N > 0:
+        dev_index = query.device.index if query.device.index is not None else torch.cuda.current_device()
+        scratch = _grown_workspace(("query", dev_index), query.device, _capi.lib().dvmvs_nearest_query_workspace_bytes(N, M))
+        with torch.cuda.device(query.device):
+            rc = _capi.lib().dvmvs_nearest_distance_fwd(_ptr(query), N, _ptr(target), M, _ptr(workspace), _ptr(scratch), scratch.numel(),
+                                                        _ptr(dist), None if index is None else _ptr(index), _stream(query))
+        _capi.check(rc, "dvmvs_nearest_distance_fwd")
+    return (dist, index) if return_index else dist
+
+
+def nearest_distance(query: Tensor, target: Tensor, return_index: bool = False):
+    """For every point of ``query`` (float32 [N,3] on the GPU) the exact distance to the nearest point of ``target`` (float32 [M,3], M >= 1):
+    float32 [N]; with ``return_index`` also int32 [N], the smallest index of a nearest target.  ``dist[i] = sqrt(min_j (dx*dx + dy*dy) +
+    dz*dz)`` with every operation rounded to float32 and no FMA: bit-identical to a brute force over all pairs, run to run, whatever the
+    grid prunes (include/dvmvs_hip.h).  Coordinates must be finite (not checked).  One build and one query on the current stream, no
+    synchronisation, no allocation once the per-device workspaces have grown to the sizes in use."""
+    return nearest_query(query, target, nearest_build(target), return_index)
+
+
+def distance_metrics(dist_pred: Tensor, dist_gt: Tensor, threshold: float = 0.05, out: Optional[Tensor] = None,
+                     counts: Optional[Tensor] = None) -> Tensor:
+    """The row (acc, comp, chamfer, precision, recall, fscore) of ``dvmvs.errors.compute_reconstruction_errors`` from the two distance
+    arrays: ``dist_pred`` float32 [Na] prediction -> ground truth, ``dist_gt`` float32 [Nb] ground truth -> prediction, both non-empty and
+    on the GPU.  Sums in float64 in a fixed order (one workgroup); float32 [6] device tensor (``out`` when given).  ``counts``: a
+    contiguous int64 [2] device tensor that receives the numbers of distances below ``threshold``."""
+    for label, t in (("dist_pred", dist_pred), ("dist_gt", dist_gt)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"dvmvs::distance_metrics: {label} must be a tensor, got {type(t).__name__}")
+        if t.device.type != "cuda":
+            _no_cpu("distance_metrics")
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() < 1:
+            raise ValueError(f"dvmvs::distance_metrics: {label} must be a non-empty float32 [n] tensor, got {t.dtype} {tuple(t.shape)}")
+    dev = dist_pred.device
+    threshold = float(threshold)
+    if dist_gt.device != dev or threshold != threshold:
+        raise ValueError(f"dvmvs::distance_metrics: both arrays must be on one device and the threshold not NaN, got {dev}, {dist_gt.device}, "
+                         f"{threshold}")
+    dist_pred, dist_gt = dist_pred.contiguous(), dist_gt.contiguous()
+    if out is None:
+        out = torch.empty(6, dtype=torch.float32, device=dev)
+    elif out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != (6,) or not out.is_contiguous():
+        raise ValueError(f"dvmvs::distance_metrics: out must be a contiguous float32 [6] tensor on {dev}")
+    if counts is not None and (counts.device != dev or counts.dtype != torch.int64 or tuple(counts.shape) != (2,) or not counts.is_contiguous()):
+        raise ValueError(f"dvmvs::distance_metrics: counts must be a contiguous int64 [2] tensor on {dev}")
+    with torch.cuda.device(dev):
+        rc = _capi.lib().dvmvs_distance_metrics_fwd(_ptr(dist_pred), dist_pred.numel(), _ptr(dist_gt), dist_gt.numel(), threshold, _ptr(out),
+                                                    None if counts is None else _ptr(counts), _stream(dist_pred))
+    _capi.check(rc, "dvmvs_distance_metrics_fwd")
+    return out

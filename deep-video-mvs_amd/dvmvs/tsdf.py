@@ -233,6 +233,33 @@ class TSDFVolume:
         verts, _, _, colors = self.get_mesh()
         return np.hstack([verts, colors])
 
+    def vertices(self):
+        """The vertices of the zero iso-surface (``get_mesh()[0]``) as a float32 [V,3] DEVICE tensor: nothing but ``marching_cubes``'
+        two counts is read by the host."""
+        return marching_cubes(self._tsdf, 0.0, None, self._vol_origin, self._voxel_size)[0]
+
+    def score_against(self, reference, threshold=0.05, return_sizes=False):
+        """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
+        DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
+        ``dvmvs.errors.compute_reconstruction_errors_device`` without a download.  ``reference``: another ``TSDFVolume``, or [M,3] points as
+        a tensor or a numpy array (uploaded).  The point sets are the VERTICES of the zero iso-surface, taken on the device from
+        ``marching_cubes``: one vertex per crossed grid edge, so their spacing is about one voxel, and a distance is measured to the nearest
+        vertex, not to the nearest point of a face.  Faces are not sampled and the clouds are not voxel down-sampled.  Raises
+        ``ValueError`` when either surface has no vertex.  ``return_sizes``: also return ``(vertices of this volume, reference points)``,
+        two numbers the host has anyway (tensor shapes)."""
+        from dvmvs.errors import compute_reconstruction_errors_device
+        if isinstance(reference, TSDFVolume):
+            gt = reference.vertices().to(self.device)
+        else:
+            gt = torch.as_tensor(reference, dtype=torch.float32, device=self.device)
+            if gt.dim() != 2 or gt.shape[1] != 3:
+                raise ValueError(f"score_against: reference points must be [M,3], got {tuple(gt.shape)}")
+        pred = self.vertices()
+        if pred.shape[0] == 0 or gt.shape[0] == 0:
+            raise ValueError(f"score_against: a surface without a vertex cannot be scored ({pred.shape[0]} predicted, {gt.shape[0]} reference)")
+        row = compute_reconstruction_errors_device(pred, gt.contiguous(), threshold)
+        return (row, (int(pred.shape[0]), int(gt.shape[0]))) if return_sizes else row
+
 
 class TSDFFusion:
     """Host-side helpers of the reference class of the same name."""
@@ -432,7 +459,8 @@ def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dat
 
 
 def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, scene_name, system_name, voxel_size, max_depth,
-        use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False):
+        use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False,
+        evaluate_3d=False, threshold_3d=0.05):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -443,7 +471,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     ``render_keyframes``: after fusion, ray-cast the volume from every fused keyframe's own view at the prediction size (one launch,
     ``TSDFVolume.render``) and save the fused depth maps next to the meshes as ``keyframe_<dataset>_<system>+tsdf_predictions_<scene>.npz``,
     the layout of the network's predictions; if the scene has ground-truth depth, also their error metrics (``..._errors_<scene>.npz``),
-    evaluated on the device over the pixels where a surface was hit.  Without the flag nothing else is written or changed."""
+    evaluated on the device over the pixels where a surface was hit.  Without the flag nothing else is written or changed.
+
+    ``evaluate_3d``: also fuse the ground-truth depth maps (as ``save_groundtruth`` does; its mesh file is written only with that flag),
+    keep that surface's vertices on the device, score the system's surface against them (``TSDFVolume.score_against`` with
+    ``threshold_3d`` metres), print the six metrics on one line and save them as ``<mesh name of the system>_errors3d.npz``: ``arr_0``
+    float32 [6], ``names``, ``counts`` int64 [2] (vertices of the prediction and of the ground truth) and ``threshold``.  Without the flag
+    the program writes what it writes without it, byte for byte."""
     from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, load_image_u8, resize_nearest
     if device_preprocess:
         load_image = load_image_u8       # resize_nearest only selects pixels: the uint8 values are those of the float path's astype
@@ -491,7 +525,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         keyframe_images.append(image.astype(np.uint8))
 
     groundtruths = None
-    if use_groundtruth_to_anchor or save_groundtruth:
+    if use_groundtruth_to_anchor or save_groundtruth or evaluate_3d:
         groundtruths = []
         for filename in sorted(glob.glob(os.path.join(scene_folder, "depth", "*.png"))):
             depth = load_depth_png(filename)
@@ -504,20 +538,39 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     volume_bounds *= 1.05      # margin for errors in the bounds
 
     os.makedirs(reconstruction_folder, exist_ok=True)
-    if save_groundtruth:
+    groundtruth_vertices = None
+    if save_groundtruth or evaluate_3d:
         volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
         images = [load_image(f).astype(np.uint8) for f in all_image_filenames]
-        TSDFFusion.integrate(volume, images, groundtruths, all_poses, original_K,
-                             _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, "GROUNDTRUTH",
-                                        dataset_name, scene_name), save_progressive=False)
+        if save_groundtruth:
+            TSDFFusion.integrate(volume, images, groundtruths, all_poses, original_K,
+                                 _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, "GROUNDTRUTH",
+                                            dataset_name, scene_name), save_progressive=False)
+        else:      # the same fusion, without its mesh file
+            for image, depth, pose in zip(images, groundtruths, all_poses):
+                volume.integrate(image, depth, original_K, pose, obs_weight=1.0)
+        if evaluate_3d:
+            groundtruth_vertices = volume.vertices()      # stay on the device when the volume goes
         del volume
     volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
-    TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K,
-                         _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name,
-                                    dataset_name, scene_name), save_progressive)
+    system_mesh_name = _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name, dataset_name, scene_name)
+    TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K, system_mesh_name, save_progressive)
+    if evaluate_3d:
+        _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name)
     if render_keyframes:
         _render_keyframes(volume, keyframe_poses, keyframe_image_filenames, scaled_K, preprocessor, prediction_height, prediction_width,
                           scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
+
+
+def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name):
+    """Scores the fused surface against the ground-truth vertices on the device; one row comes down, is printed and saved."""
+    from dvmvs.errors import RECONSTRUCTION_METRICS
+    row, sizes = volume.score_against(groundtruth_vertices, threshold, return_sizes=True)
+    row = row.cpu().numpy()
+    print("3-D metrics at {} m over {} predicted and {} ground-truth vertices: {}".format(
+        threshold, sizes[0], sizes[1], ", ".join(f"{n} {v:.4f}" for n, v in zip(RECONSTRUCTION_METRICS, row))))
+    np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
+                        counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold))
 
 
 def _render_keyframes(volume, poses, image_filenames, K, preprocessor, height, width, scene_folder, system_name, scene_name, save_folder):
@@ -561,6 +614,10 @@ def main(argv=None):
                         help="load the colour images as 8-bit (no float32 round trip); same meshes")
     parser.add_argument("--render_keyframes", action="store_true",
                         help="also ray-cast the fused volume from every keyframe's view and save the fused depth maps (<system>+tsdf)")
+    parser.add_argument("--evaluate_3d", action="store_true",
+                        help="also fuse the ground-truth depth maps and score the system's mesh against that surface in 3-D on the device "
+                             "(accuracy, completeness, chamfer, precision, recall, F-score; saved as <mesh name>_errors3d.npz)")
+    parser.add_argument("--threshold_3d", default=0.05, type=float, help="distance threshold of precision / recall / F-score, metres")
     args = parser.parse_args(argv)
     run(**vars(args))
 

@@ -51,7 +51,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_tsdf_raycast_* (ray-casting a fused TSDF volume from camera views); no earlier signature changed, the
  * number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_tsdf_integrate_frames* (fusing a batch of frames into a TSDF volume in one launch); no earlier signature
- * changed, the number stays 11 by the same rule. */
+ * changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_nearest_* and dvmvs_distance_metrics_fwd (exact nearest-point distances between point clouds and the 3-D
+ * reconstruction metrics); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -678,6 +680,45 @@ int dvmvs_tsdf_integrate_frames(float* tsdf_vol, float* weight_vol, float* color
                                 const unsigned char* rgb_u8, const float* folded, const float* depth, int n_frames, int im_h, int im_w,
                                 float trunc_margin, const float* obs_weight_host, float max_depth, void* workspace, long long* tile_stats,
                                 dvmvs_stream_t stream);
+
+/*
+ * Nearest-point distances between point clouds and the 3-D reconstruction metrics (ABI 11, later addition).  The reference project has
+ * nothing for this: the definitions are this project's own (the metrics are those of the Atlas / NeuralRecon / SimpleRecon evaluations).
+ *   target [M,3], query [N,3]   fp32, contiguous, 4-byte aligned, FINITE (a precondition; not checked on the device)
+ *   workspace         dvmvs_nearest_workspace_bytes(M) bytes on the device, 16-byte aligned: written by dvmvs_nearest_build, read by
+ *                     dvmvs_nearest_distance_fwd.  It holds a header (the targets' bounding box, the cell edge and the dimensions of a
+ *                     uniform grid over the box, all computed on the device), the cells' end offsets and a copy of the targets sorted by
+ *                     cell with their original indices.  The host sizes it from M alone and never reads it.  Header, for tests and tools:
+ *                     float mn[3], mx[3], inv_h, h_lo; int dim[3], ncells (48 bytes); cell_a(x) = int((clamp(x, mn_a, mx_a) - mn_a) * inv_h).
+ *   query_workspace   dvmvs_nearest_query_workspace_bytes(N, M) bytes on the device, 16-byte aligned, scratch of one query call (the
+ *                     queries binned by the same grid, so that a wave works on neighbouring cells).  Calls that share it must be ordered.
+ *   dist [N] fp32 out; index [N] int32 out or NULL
+ * Arithmetic contract.  d2(q, t) = (dx dx + dy dy) + dz dz with dx = q.x - t.x, dy, dz likewise; every operation rounded to fp32, no FMA
+ * contraction.  dist[i] = sqrt(min over j of d2(query_i, target_j)), the square root correctly rounded; index[i] = the SMALLEST j that
+ * attains the minimum.  The minimum does not depend on the order of evaluation, so dist and index are bit-identical to a brute force over
+ * all j, run to run, on any stream.  The search visits the cells around the query's cell (for a query outside the box: the cell of its
+ * clamp onto the box) in growing Chebyshev rings and stops only, and never before ring 1, when the best d2 is provably smaller than that of every unvisited
+ * target (bound and its fp32 margins: csrc/nearest_points.hip); otherwise it goes on until it has visited the whole grid.  Degenerate
+ * target sets (one point, coincident, collinear, coplanar) are legal.  The float32 result is within 4 * 2^-24 * d of the exact distance.
+ * dvmvs_nearest_distance_fwd with N == 0 enqueues nothing and returns 0.
+ * dvmvs_distance_metrics_fwd: dist_a [Na] (prediction -> ground truth), dist_b [Nb] (ground truth -> prediction), fp32 threshold ->
+ *   row fp32 [6]: acc = mean(dist_a), comp = mean(dist_b), chamfer = (acc + comp) / 2, precision = count(dist_a < threshold) / Na,
+ *   recall = count(dist_b < threshold) / Nb, fscore = 2 P R / (P + R) (0 when P + R == 0);  counts long long [2] out or NULL: the two
+ *   counts.  The sums run in fp64 in ONE workgroup in an order that is a function of (Na, Nb) alone; the means, shares, chamfer and
+ *   fscore are formed in fp64 from them and rounded to fp32 once each.
+ * The two *_workspace_bytes: host only, no HIP call; 0 for M <= 0 (N <= 0) or above 2^28 points; non-decreasing in M (and N).
+ * Returns DVMVS_EINVAL for a null target / workspace (with N > 0: query / query_workspace / dist), M < 1, N < 0, workspace_bytes or
+ * query_workspace_bytes too small,
+ * a misaligned pointer; metrics: a null dist_a / dist_b / row, Na or Nb < 1, a NaN threshold, counts not 8-byte aligned;
+ * DVMVS_EUNSUPPORTED above 2^28 points.  Nothing is enqueued in either case.
+ */
+size_t dvmvs_nearest_workspace_bytes(long long M);
+size_t dvmvs_nearest_query_workspace_bytes(long long N, long long M);
+int dvmvs_nearest_build(const float* target, long long M, void* workspace, size_t workspace_bytes, dvmvs_stream_t stream);
+int dvmvs_nearest_distance_fwd(const float* query, long long N, const float* target, long long M, const void* workspace,
+                               void* query_workspace, size_t query_workspace_bytes, float* dist, int* index, dvmvs_stream_t stream);
+int dvmvs_distance_metrics_fwd(const float* dist_a, long long Na, const float* dist_b, long long Nb, float threshold, float* row,
+                               long long* counts, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
