@@ -33,6 +33,7 @@ import copy
 import time
 import os
 from collections import OrderedDict
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -72,12 +73,24 @@ _STAGING_SLOTS = int(os.environ.get("DVMVS_STAGING_SLOTS", "1"))
 # instantiated (kept, never launched): all frame graphs end up on the same queue.  DESIGN.md section 5; 0 = the runtime's own order.
 _GRAPH_QUEUE_FILLERS = int(os.environ.get("DVMVS_GRAPH_QUEUE_FILLERS", "1"))
 # experiments: "1" = a frame's sweep runs before the side-stream fork instead of next to the side stream's kernels (see _frame_body_direct)
-_FORK_AFTER = int(os.environ.get("DVMVS_FORK_AFTER", "1"))      # see _frame_body_direct (measured: -1 / 0 / 1 / 2 / 3 / 4 = 1 355 / 1 371 / 1 382 / 1 377 / 1 319 / 1 239 frames/s)
+def _fork_point(value):
+    """A DVMVS_FORK_AFTER value as the fork level of _frame_body_direct: -1 ... 4.  Anything else raises -- behind a level the encoder does not have
+    the fork would never happen, and the next frame would read features nobody computed."""
+    try:
+        level = int(value)
+    except (TypeError, ValueError):
+        level = None
+    if level not in (-1, 0, 1, 2, 3, 4):
+        raise ValueError(f"DVMVS_FORK_AFTER must be an integer from -1 to 4, got {value!r}")
+    return level
+
+
+_FORK_AFTER = _fork_point(os.environ.get("DVMVS_FORK_AFTER", "1"))      # see _frame_body_direct (measured: -1 / 0 / 1 / 2 / 3 / 4 = 1 355 / 1 371 / 1 382 / 1 377 / 1 319 / 1 239 frames/s)
 _PAIRED_UPSAMPLING = os.environ.get("DVMVS_PAIRED_UPSAMPLING", "1") != "0"      # a decoder level's two up-samplings in one launch
 _UP2X_IN_CONV = os.environ.get("DVMVS_UP2X_IN_CONV", "1") != "0"      # the decoder's first up-sampling inside its convolution's staging
 _UPLOAD_IN_COPY_BATCH = os.environ.get("DVMVS_UPLOAD_IN_COPY_BATCH", "1") != "0"
 _AUX_STREAM = os.environ.get("DVMVS_AUX_STREAM", "0")      # "0" off, "warp" / "heads" one of the two uses, "1" both (see DepthEngine._aux_stream)
-# a step's input copies as one launch (see DepthEngine._copy); "0" = one runtime copy each
+# a step's input copies as one launch (see CopyQueue); "0" = one runtime copy each
 _BATCH_COPIES = os.environ.get("DVMVS_BATCH_COPIES", "1") != "0"
 
 
@@ -533,8 +546,151 @@ def accelerate(*modules, direct_convs=True, bottleneck_convs=True, pointwise_con
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# frame engine
+# frame engine: its host-side parts (no device needed: tests/test_engine_host_logic.py), then the engine
 # ----------------------------------------------------------------------------------------------------------------------
+class FrameBody(NamedTuple):
+    """What one call of the frame body computes (DepthEngine._frame_body's arguments): ``have`` = how much of the frame the previous step
+    prepared, ``give`` = how much of the next frame this one computes (0 nothing, 1 reference features, 2 also sweep + encoder)."""
+    n_meas: int
+    has_previous: bool
+    sweep_variant: int
+    parity: int
+    have: int
+    give: int
+    n_meas_next: int
+    next_variant: int
+
+    def key(self):
+        """The body as the key of its captured graph: stages that do not run in this graph do not tell graphs apart."""
+        own, ahead = self.have < 2, self.give == 2
+        return self._replace(n_meas=self.n_meas if own else 0, sweep_variant=self.sweep_variant if own else 0,
+                             n_meas_next=self.n_meas_next if ahead else 0, next_variant=self.next_variant if ahead else 0)
+
+
+def _store_measurement_map(dst, src):
+    """``dst`` = ``src``; an NCHW map into a channels-last buffer through the transposing kernel (torch's strided copy writes 4 bytes per
+    128-byte line)."""
+    if src.stride() == dst.stride() or not (src.is_contiguous() and dst.is_contiguous(memory_format=torch.channels_last) and src.shape[1] % 4 == 0 and src.shape[1] <= 64):
+        dst.copy_(src)      # (the frame path: channels-last into channels-last)
+    else:
+        _ops.nchw_to_nhwc_into(src, dst)
+
+
+class CopyQueue:
+    """A step's flat input copies -- this keyframe's features into the feature cache, the measurement maps into the sweep's buffers, the images
+    into their homes: four runtime copies of 0.6 - 1 MB in front of every frame graph, 5 us each on the device and as much again on the host --
+    collected while the queue is open and issued as ONE launch (dvmvs_copy_batch) before the frame's parameters go up.  Closed (outside
+    ``step``), or for a copy the batch entry does not take, ``add`` copies at once."""
+
+    def __init__(self):
+        self.pending = None      # None: closed; a list of (dst, src) while open
+
+    def open(self):
+        self.pending = []
+
+    def close(self):
+        """Closes the queue and hands over what is still queued (``issue`` it, alone or with the parameter block)."""
+        pending, self.pending = self.pending, None
+        return pending
+
+    def add(self, dst, src):
+        """``dst`` = ``src`` (see _store_measurement_map).  A copy that touches a range a queued copy writes (or writes one a queued copy
+        reads) flushes the queue first; so does the eighth copy (what one launch takes)."""
+        queue = self.pending
+        if queue is None or not _BATCH_COPIES or not _ops.batchable(dst, src):
+            self.flush()
+            _store_measurement_map(dst, src)
+            return
+        nbytes = 4 * dst.numel()
+        d0, s0 = dst.data_ptr(), src.data_ptr()
+        for qd, qs in queue:
+            q0, r0, qn = qd.data_ptr(), qs.data_ptr(), 4 * qd.numel()
+            if (d0 < q0 + qn and q0 < d0 + nbytes) or (s0 < q0 + qn and q0 < s0 + nbytes) or (d0 < r0 + qn and r0 < d0 + nbytes):
+                self.flush()
+                break
+        queue.append((dst, src))
+        if len(queue) == 8:
+            self.flush()
+
+    def flush(self):
+        self.issue(self.pending)
+
+    @staticmethod
+    def issue(pairs):
+        """Executes and forgets the copies of ``pairs`` (a list, or None): one plain copy, or one batched launch."""
+        if pairs:
+            if len(pairs) == 1:
+                pairs[0][0].copy_(pairs[0][1])
+            else:
+                _ops.copy_batch(pairs)
+            pairs.clear()
+
+
+class FeatureCache:
+    """frame id -> a keyframe's half-resolution features, least recently used first.  The entries live in a pool of ``cache_size + 1`` buffers
+    allocated once per entry shape: a ``clone()`` per keyframe made the first ``cache_size`` frames of every run pay a device allocation each
+    (hipMalloc synchronises: a 20-step run measured 1.7 ms per frame where 100 steps measured 1.39).  ``channels_last_entries``: the pool's
+    buffers are channels-last (what the MFMA sweep reads); without it a non-contiguous entry is kept as it is, outside the pool."""
+
+    def __init__(self, cache_size, device, channels_last_entries):
+        self.cache_size, self.device, self.channels_last_entries = cache_size, device, channels_last_entries
+        self.entries = OrderedDict()      # frame id -> features (a buffer of the pool)
+        self.pool, self.free, self.slot = None, [], {}      # [cache_size + 1, *entry shape]; free pool indices; frame id -> pool index
+
+    def __contains__(self, frame_id):
+        return frame_id in self.entries
+
+    def __getitem__(self, frame_id):
+        return self.entries[frame_id]
+
+    def lookup(self, frame_id):
+        """The entry, now the most recently used one."""
+        self.entries.move_to_end(frame_id)
+        return self.entries[frame_id]
+
+    def clear(self):
+        self.entries.clear()
+        if self.pool is not None:
+            self.free = list(range(self.pool.shape[0] - 1, -1, -1))
+        self.slot = {}
+
+    def remember(self, frame_id, half, copy):
+        """Caches ``half`` under ``frame_id``: into the id's own slot if it has one, else into a free one (the least recently used entry gives
+        its slot back first); the values go there through ``copy(dst, src)``.  An entry of another shape rebuilds the pool and empties the cache."""
+        if not half.is_contiguous() and not self.channels_last_entries:      # (channels-last engines keep their maps as they are: the sweep reads them as NHWC)
+            self.entries[frame_id] = half
+            while len(self.entries) > self.cache_size:
+                self.slot.pop(self.entries.popitem(last=False)[0], None)
+            return
+        if self.pool is None or tuple(self.pool.shape[1:]) != tuple(half.shape):
+            if self.channels_last_entries and half.dim() == 4:      # channels-last entries (what the sweep reads): [n, S, H, W, C] storage, [n, S, C, H, W] view
+                S_, C_, H_, W_ = half.shape
+                self.pool = torch.empty((self.cache_size + 1, S_, H_, W_, C_), device=self.device, dtype=torch.float32).permute(0, 1, 4, 2, 3)
+            else:
+                self.pool = torch.empty((self.cache_size + 1,) + tuple(half.shape), device=self.device, dtype=torch.float32)
+            self.clear()
+        if frame_id in self.entries:
+            buffer = self.entries.pop(frame_id)
+        else:
+            while len(self.entries) >= self.cache_size:      # least recently used entry out, its buffer back to the pool
+                self.free.append(self.slot.pop(self.entries.popitem(last=False)[0]))
+            buffer = self.pool[self.free[-1]]
+            self.slot[frame_id] = self.free.pop()
+        if buffer.data_ptr() != half.data_ptr():
+            copy(buffer, half)
+        self.entries[frame_id] = buffer
+
+
+# (environment variable, constructor argument, FusedConv2d attribute, engine attribute) of the kernel families an engine can switch off ("0":
+# MIOpen + epilogue launch instead); each needs the fused epilogues and contiguous maps
+_KERNEL_SWITCHES = (
+    ("DVMVS_CONV_PLANS", "conv_plans", "plan_epilogue", "conv_plans"),      # epilogues inside MIOpen's Winograd kernels where that is measurably faster (FusedConv2d.plans)
+    ("DVMVS_BOTTLENECK_CONVS", "bottleneck_convs", "bottleneck", "bottleneck_convs"),      # 3x3 layers on the 8x10 / 16x20 maps, ConvLSTM convolution: csrc/bottleneck_conv.hip
+    ("DVMVS_DIRECT_CONVS", "direct_convs", "direct_conv", "direct_convs"),      # dense 3x3 / 5x5 layers of the 1/8 ... full-resolution maps, depth heads: csrc/direct_conv.hip
+    ("DVMVS_POINTWISE_CONVS", "pointwise_convs", "pointwise_conv", "pointwise_convs"),      # 1x1 layers (feature extractor, FPN lateral layers): csrc/pointwise_conv.hip
+)
+
+
 class DepthEngine:
     """Sequential keyframe processor for one video sequence (batch 1: the reference's case) or ``sequences`` = S independent
     sequences advancing in lockstep (batch S: one cost-volume launch, one convolution per layer for all of them), pairnet
@@ -565,41 +721,15 @@ class DepthEngine:
         if channels_last:
             mods = [None if m is None else m.to(memory_format=torch.channels_last) for m in mods]
         self.fe, self.fs, self.enc, self.lstm, self.dec = mods
-        # epilogues inside MIOpen's Winograd kernels where that is measurably faster (FusedConv2d.plans; DVMVS_CONV_PLANS=0 disables)
-        if conv_plans is None:
-            conv_plans = os.environ.get("DVMVS_CONV_PLANS", "1") != "0"
-        self.conv_plans = bool(conv_plans and fuse and not channels_last)
+        requested = dict(conv_plans=conv_plans, bottleneck_convs=bottleneck_convs, direct_convs=direct_convs, pointwise_convs=pointwise_convs)
+        for variable, argument, _, engine_attribute in _KERNEL_SWITCHES:
+            wanted = requested[argument] if requested[argument] is not None else os.environ.get(variable, "1") != "0"
+            setattr(self, engine_attribute, bool(wanted and fuse and not channels_last))
         for m in mods:
             for sub in ([] if m is None else m.modules()):
                 if isinstance(sub, FusedConv2d):
-                    sub.plan_epilogue = self.conv_plans
-        # the 3x3 layers on the 8x10 / 16x20 maps and the ConvLSTM convolution through the deterministic MFMA kernel
-        # (csrc/bottleneck_conv.hip; DVMVS_BOTTLENECK_CONVS=0: MIOpen)
-        if bottleneck_convs is None:
-            bottleneck_convs = os.environ.get("DVMVS_BOTTLENECK_CONVS", "1") != "0"
-        self.bottleneck_convs = bool(bottleneck_convs and fuse and not channels_last)
-        for m in mods:
-            for sub in ([] if m is None else m.modules()):
-                if isinstance(sub, FusedConv2d):
-                    sub.bottleneck = self.bottleneck_convs
-        # the dense 3x3 / 5x5 layers of the 1/8 ... full-resolution maps and the depth heads through the direct MFMA convolution
-        # (csrc/direct_conv.hip; DVMVS_DIRECT_CONVS=0: MIOpen + epilogue launch as in rounds 1-3)
-        if direct_convs is None:
-            direct_convs = os.environ.get("DVMVS_DIRECT_CONVS", "1") != "0"
-        self.direct_convs = bool(direct_convs and fuse and not channels_last)
-        for m in mods:
-            for sub in ([] if m is None else m.modules()):
-                if isinstance(sub, FusedConv2d):
-                    sub.direct_conv = self.direct_convs
-        # the 1x1 layers (feature extractor, FPN lateral layers) through the MFMA GEMM with bias + ReLU + residual in its store path
-        # (csrc/pointwise_conv.hip; DVMVS_POINTWISE_CONVS=0: library GEMM + epilogue launch as in rounds 1-5)
-        if pointwise_convs is None:
-            pointwise_convs = os.environ.get("DVMVS_POINTWISE_CONVS", "1") != "0"
-        self.pointwise_convs = bool(pointwise_convs and fuse and not channels_last)
-        for m in mods:
-            for sub in ([] if m is None else m.modules()):
-                if isinstance(sub, FusedConv2d):
-                    sub.pointwise_conv = self.pointwise_convs
+                    for _, _, layer_attribute, engine_attribute in _KERNEL_SWITCHES:
+                        setattr(sub, layer_attribute, getattr(self, engine_attribute))
         self._lstm_packed, self._lstm_partials, self._lstm_combined = None, None, None
         if lstm_channels_last and self.lstm is not None and not channels_last:
             # the ConvLSTM convolution (1024 -> 2048 channels on an 8x10 map, 75 MB of weights) is weight-bandwidth bound;
@@ -624,8 +754,6 @@ class DepthEngine:
         self._prev_pose_host = torch.eye(4).repeat(self.sequences, 1, 1)
         self._no_previous = torch.ones(self.sequences, dtype=torch.bool)   # sequences whose next frame has no previous frame
         self._ring, self._ring_pos = None, 0
-        self._feature_cache = OrderedDict()      # frame id -> features (a buffer of the pool below), least recently used first
-        self._feature_pool, self._feature_free, self._feature_slot = None, [], {}
         self._graphs = {}
         self._static = None
         self._direct_buffers = {}
@@ -644,7 +772,7 @@ class DepthEngine:
         self.lookahead_rejected = 0      # announced frames whose prepared stages were not taken because the image came as another tensor
         self._switch_interval_before = None
         self._filler_buffers, self._filler_graphs = None, []
-        self._copy_queue = None      # a list while step() collects its input copies (see _copy)
+        self._copies = CopyQueue()      # open while step() collects its input copies
         self._staging_seen = {}      # staging slot address -> whether the device may read it in place (see _staging_visible)
         self.warm_captured_graphs = os.environ.get("DVMVS_WARM_GRAPHS", "1") != "0"
         # launches of every newly captured graph on throw-away results: the runtime finishes setting a graph up over its first launches (a
@@ -675,6 +803,7 @@ class DepthEngine:
                                and (self.height // 2) * (self.width // 2) >= 64 * 64)
         # (round 6: dvmvs_sweep_plan6 returns 6 for every single-sequence frame -- one sweep configuration, one frame graph per buffer set and pattern)
         self._tiled_variants = (6,) if self.sweep_mfma else (2, 3, 4, 5)
+        self._feature_cache = FeatureCache(self.cache_size, self.device, self.sweep_mfma)
         self.reset()
 
     def conv_plan_report(self):
@@ -732,9 +861,6 @@ class DepthEngine:
 
     def clear_feature_cache(self):
         self._feature_cache.clear()
-        if self._feature_pool is not None:
-            self._feature_free = list(range(self._feature_pool.shape[0] - 1, -1, -1))
-        self._feature_slot = {}
 
     def new_sequence(self):
         """Start of another video sequence on the same engine: forget the recurrent state AND the cached keyframe features
@@ -749,82 +875,21 @@ class DepthEngine:
             image = image.contiguous(memory_format=torch.channels_last)
         return self.fs(*self.fe(image))
 
+    def has_features(self, frame_id):
+        """Whether the features of keyframe ``frame_id`` are cached (``step`` then needs no image for it as a measurement frame)."""
+        return self.cache_features and frame_id is not None and frame_id in self._feature_cache
+
     def _half_features(self, frame_id, image):
-        if self.cache_features and frame_id is not None and frame_id in self._feature_cache:
-            self._feature_cache.move_to_end(frame_id)
-            return self._feature_cache[frame_id]
+        if self.has_features(frame_id):
+            return self._feature_cache.lookup(frame_id)
         half = self._features(image)[0].contiguous()
         self._remember(frame_id, half)
         return half
 
     def _remember(self, frame_id, half):
-        """Caches a keyframe's half-resolution features.  The entries live in a pool of ``cache_size`` buffers allocated once: a
-        ``clone()`` per keyframe made the first ``cache_size`` frames of every run pay a device allocation each (hipMalloc synchronises:
-        a 20-step run measured 1.7 ms per frame where 100 steps measured 1.39)."""
+        """Caches a keyframe's half-resolution features (the copy into the cache's buffer rides in the step's copy queue)."""
         if self.cache_features and frame_id is not None:
-            if not half.is_contiguous() and not self.sweep_mfma:      # (channels-last engines keep their maps as they are: the sweep reads them as NHWC)
-                self._feature_cache[frame_id] = half
-                while len(self._feature_cache) > self.cache_size:
-                    self._feature_slot.pop(self._feature_cache.popitem(last=False)[0], None)
-                return
-            if self._feature_pool is None or tuple(self._feature_pool.shape[1:]) != tuple(half.shape):
-                if self.sweep_mfma and half.dim() == 4:      # channels-last entries (what the sweep reads): [n, S, H, W, C] storage, [n, S, C, H, W] view
-                    S_, C_, H_, W_ = half.shape
-                    self._feature_pool = torch.empty((self.cache_size + 1, S_, H_, W_, C_), device=self.device, dtype=torch.float32).permute(0, 1, 4, 2, 3)
-                else:
-                    self._feature_pool = torch.empty((self.cache_size + 1,) + tuple(half.shape), device=self.device, dtype=torch.float32)
-                self._feature_free = list(range(self.cache_size, -1, -1))
-                self._feature_cache.clear()
-                self._feature_slot = {}
-            if frame_id in self._feature_cache:
-                slot = self._feature_cache.pop(frame_id)
-            else:
-                while len(self._feature_cache) >= self.cache_size:      # least recently used entry out, its buffer back to the pool
-                    self._feature_free.append(self._feature_slot.pop(self._feature_cache.popitem(last=False)[0]))
-                slot = self._feature_pool[self._feature_free[-1]]
-                self._feature_slot[frame_id] = self._feature_free.pop()
-            if slot.data_ptr() != half.data_ptr():
-                self._copy(slot, half)
-            self._feature_cache[frame_id] = slot
-
-    @staticmethod
-    def _store_measurement_map(dst, src):
-        """``dst`` = ``src``; an NCHW map into a channels-last buffer through the transposing kernel (torch's strided copy writes 4 bytes per
-        128-byte line)."""
-        if src.stride() == dst.stride() or not (src.is_contiguous() and dst.is_contiguous(memory_format=torch.channels_last) and src.shape[1] % 4 == 0 and src.shape[1] <= 64):
-            dst.copy_(src)      # (the frame path: channels-last into channels-last)
-        else:
-            _ops.nchw_to_nhwc_into(src, dst)
-
-    def _copy(self, dst, src):
-        """``dst`` = ``src`` (see _store_measurement_map).  Inside ``step`` the flat copies -- this keyframe's features into the feature cache,
-        the measurement maps into the sweep's buffers, the images into their homes: four runtime copies of 0.6 - 1 MB in front of every frame graph,
-        5 us each on the device and as much again on the host -- are collected and issued as ONE launch (dvmvs_copy_batch) before the
-        frame's parameters go up.  A copy that touches a range a queued copy writes (or writes one a queued copy reads) flushes the queue first."""
-        queue = self._copy_queue
-        if queue is None or not _BATCH_COPIES or not _ops.batchable(dst, src):
-            self._flush_copies()
-            self._store_measurement_map(dst, src)
-            return
-        nbytes = 4 * dst.numel()
-        d0, s0 = dst.data_ptr(), src.data_ptr()
-        for qd, qs in queue:
-            q0, r0, qn = qd.data_ptr(), qs.data_ptr(), 4 * qd.numel()
-            if (d0 < q0 + qn and q0 < d0 + nbytes) or (s0 < q0 + qn and q0 < s0 + nbytes) or (d0 < r0 + qn and r0 < d0 + nbytes):
-                self._flush_copies()
-                break
-        queue.append((dst, src))
-        if len(queue) == 8:
-            self._flush_copies()
-
-    def _flush_copies(self):
-        queue = self._copy_queue
-        if queue:
-            if len(queue) == 1:
-                queue[0][0].copy_(queue[0][1])
-            else:
-                _ops.copy_batch(queue)
-            queue.clear()
+            self._feature_cache.remember(frame_id, half, self._copies.add)
 
     def _allocate_static(self, n_meas):
         d, H, W, S = self.device, self.height, self.width, self.sequences
@@ -933,12 +998,7 @@ class DepthEngine:
                 result = self._evaluate_frame_parameters(self._param_host, n_meas, pose, measurement_poses, full_K, self._prev_pose_host,
                                                          self._no_previous, index, own_sweep, next_frame)
         except BaseException:
-            if pending_copies:      # (they belong to cache entries that are already registered: written before the error leaves)
-                self._copy_queue = pending_copies
-                try:
-                    self._flush_copies()
-                finally:
-                    self._copy_queue = None
+            CopyQueue.issue(pending_copies)      # (they belong to cache entries that are already registered: written before the error leaves)
             raise
         mirror = self._param_host
         staging, event = self._ring[self._ring_pos]
@@ -955,12 +1015,7 @@ class DepthEngine:
                 # launch more per frame
                 _ops.copy_batch(pending_copies + [(params, staging)])
             else:
-                if pending_copies:
-                    self._copy_queue = pending_copies
-                    try:
-                        self._flush_copies()
-                    finally:
-                        self._copy_queue = None
+                CopyQueue.issue(pending_copies)
                 params.copy_(staging, non_blocking=True)
             event.record(torch.cuda.current_stream(self.device))
         return result
@@ -1211,8 +1266,10 @@ class DepthEngine:
             ahead()
         else:
             main = torch.cuda.current_stream(self.device)
+            forked = []
 
             def fork():
+                forked.append(True)
                 self._side_stream.wait_stream(main)
                 with torch.cuda.stream(self._side_stream):
                     ahead()
@@ -1230,6 +1287,8 @@ class DepthEngine:
                 if level == 0:
                     fork()
                 own(sweep_done=True, after_level=(level - 1, fork) if level > 0 else None)
+            if not forked:      # (a fork level the encoder does not have: the next frame would read features nobody computed)
+                raise RuntimeError(f"the look-ahead was never forked off (fork level {level})")
             main.wait_stream(self._side_stream)
 
     def _reference_features_direct(self, buffers):
@@ -1416,89 +1475,24 @@ class DepthEngine:
         if tuple(reference_image.shape) != (self.sequences, 3, self.height, self.width):
             raise ValueError(f"image must be [{self.sequences},3,{self.height},{self.width}], got {tuple(reference_image.shape)}")
         parity = self._parity if self.direct else 0
-        sets = self._direct_buffers.get("sets")
-        cur = sets[parity] if self.direct else None
-        self._copy_queue = []      # (closed at "inputs copied"; an exception on the way flushes what was queued: see the except clause there)
+        cur = self._direct_buffers["sets"][parity] if self.direct else None
+        announced = dict(image=next_reference_image, frame_id=next_frame_id, pose=next_reference_pose, measurement_poses=next_measurement_poses,
+                         measurement_ids=next_measurement_ids)
+        self._copies.open()      # (closed at "inputs copied"; an exception on the way issues what was queued: see the except clause there)
         try:
             if self.direct:
                 self._direct_buffers["estimate"] = cur["estimate"]      # (diagnostics: the 8x10 depth estimate of the frame this call computes)
-
-            # ---- what the previous call prepared for this frame: 0 nothing, 1 its reference features, 2 also its sweep + encoder ----
-            have, ready = 0, self._prefetched
-            if self.direct and ready is not None and frame_id is not None and ready["frame_id"] == frame_id and ready["parity"] == parity and not (
-                    ready["image"].data_ptr() == reference_image.data_ptr() and ready["image_version"] == reference_image._version and
-                    ready["image"].device == reference_image.device and tuple(ready["image"].stride()) == tuple(reference_image.stride())):
-                # the announced frame came as ANOTHER tensor (re-materialised, modified): its prepared stages are not taken (say so)
-                self.lookahead_rejected += 1
-                if self.lookahead_rejected == 1:
-                    import warnings
-                    warnings.warn("DepthEngine.step: the frame announced by next_reference_image arrived as a different (or modified) tensor; its "
-                                  "prepared features are recomputed.  Hand step() the very tensor that was announced to keep the look-ahead.", RuntimeWarning)
-            # (a frame id alone does not identify an image: the prepared features are taken only for the very tensor that was announced --
-            # same storage, unmodified since; the engine keeps the announced tensor alive, so the address cannot have been reused)
-            if self.direct and frame_id is not None and ready is not None and ready["frame_id"] == frame_id and ready["parity"] == parity and \
-                    ready["image"].data_ptr() == reference_image.data_ptr() and ready["image_version"] == reference_image._version and \
-                    ready["image"].device == reference_image.device and tuple(ready["image"].stride()) == tuple(reference_image.stride()):
-                have = 1
-                if ready["level"] == 2 and ready["measurement_ids"] == list(measurement_ids) and len(ready["measurement_poses"]) == n_meas and \
-                        torch.equal(ready["full_K"], _pose_algebra.to_host(full_K).reshape(-1, 3, 3)) and \
-                        torch.equal(ready["pose"], _pose_algebra.to_host(reference_pose).reshape(-1, 4, 4)) and \
-                        all(torch.equal(a, _pose_algebra.to_host(b).reshape(-1, 4, 4)) for a, b in zip(ready["measurement_poses"], measurement_poses)):
-                    have = 2
+            have = self._prepared_level(frame_id, parity, reference_image, reference_pose, measurement_ids, measurement_poses, full_K)
             if have >= 1 and self.cache_features:
                 self._remember(frame_id, cur["ref_half_nhwc"] if self.sweep_mfma else cur["enc_cat"][0][:, :32])     # (the next frame may use this one as a measurement frame)
-
-            # ---- this frame's measurement features (not needed when its sweep already ran) ----
-            if have < 2:
-                # resolve every measurement frame BEFORE anything is inserted into the cache: an insertion may evict the least
-                # recently used entry, which could be a frame this very call still needs
-                fresh, target = [], (cur["meas_feat"] if self.direct else s["meas_feat"])
-                for i in range(n_meas):
-                    img = measurement_images[i] if measurement_images is not None else None
-                    mid = measurement_ids[i]
-                    if self.cache_features and mid is not None and mid in self._feature_cache:
-                        self._feature_cache.move_to_end(mid)
-                        half = self._feature_cache[mid]
-                    elif img is None:
-                        raise ValueError(f"measurement frame {mid} is not cached and no image was given")
-                    else:
-                        half = self._features(img)[0].contiguous()
-                        fresh.append((mid, half))
-                    self._copy(target[i], half)
-                for mid, half in fresh:
-                    self._remember(mid, half)
-
-            # ---- how much of the next frame this call computes ----
-            give, next_frame, n_meas_next = 0, None, 0
-            if self.direct and next_reference_image is not None and self.max_lookahead >= 1:
-                if tuple(next_reference_image.shape) != tuple(reference_image.shape):
-                    raise ValueError("next_reference_image must have the reference image's shape")
-                give = 1
-                if self.max_lookahead >= 2 and next_reference_pose is not None and next_measurement_poses is not None and next_measurement_ids is not None and \
-                        next_frame_id is not None and self.pose_algebra == "reference" and self.cache_features and \
-                        1 <= len(next_measurement_poses) <= _MAX_MEAS and len(next_measurement_ids) == len(next_measurement_poses) and \
-                        all(m is not None and (m in self._feature_cache or (m == frame_id and have >= 1)) for m in next_measurement_ids):
-                    give, n_meas_next = 2, len(next_measurement_poses)
-                    self._allocate_static(n_meas_next)
-                    next_frame = (next_reference_pose, list(next_measurement_poses))
-                    for i, mid in enumerate(next_measurement_ids):
-                        self._copy(sets[1 - parity]["meas_feat"][i], self._feature_cache[mid])
-            if self.direct:
-                if have < 1:
-                    self._copy(cur["full_in"][:, 33:36], reference_image)
-                if give >= 1:
-                    self._copy(sets[1 - parity]["full_in"][:, 33:36], next_reference_image)
-                s["image"], s["ref_half"] = cur["full_in"][:, 33:36], cur["enc_cat"][0][:, :32]
-            else:
-                self._copy(s["image"], reference_image)
+            if have < 2:      # (its measurement features are not needed when its sweep already ran)
+                self._queue_measurement_features(cur["meas_feat"] if self.direct else s["meas_feat"], n_meas, measurement_images, measurement_ids)
+            give, next_frame = self._plan_next_frame(announced, reference_image, frame_id, parity, have)
+            self._queue_images(cur, parity, have, give, reference_image, next_reference_image)
         except BaseException:
-            try:      # (what was queued belongs to cache entries that are already registered: write it before the error leaves)
-                self._flush_copies()
-            finally:
-                self._copy_queue = None
+            CopyQueue.issue(self._copies.close())      # (what was queued belongs to cache entries that are already registered: write it before the error leaves)
             raise
-        pending = self._copy_queue      # (launched together with the parameter block: _upload_frame_parameters)
-        self._copy_queue = None
+        pending = self._copies.close()      # (launched together with the parameter block: _upload_frame_parameters)
         mark("inputs copied")
         committed_pose, sweep_variant, next_variant = self._upload_frame_parameters(n_meas, reference_pose, measurement_poses, full_K, index=parity,
                                                                                     own_sweep=have < 2, next_frame=next_frame, pending_copies=pending)
@@ -1508,18 +1502,99 @@ class DepthEngine:
             # the announced next frame's parameter block, evaluated on the planning thread while this thread launches the frame
             self.plan_ahead(len(next_measurement_poses), next_reference_pose, list(next_measurement_poses), full_K, committed_pose, 1 - parity)
         if have == 2:
-            sweep_variant = ready["sweep_variant"]
+            sweep_variant = self._prefetched["sweep_variant"]
         self.sweep_variant_counts[sweep_variant] = self.sweep_variant_counts.get(sweep_variant, 0) + 1
-
         # S > 1: always the previous-state path (see the class docstring); S == 1: the reference's two frame kinds
-        kind = (n_meas, (self.has_previous or self.sequences > 1) and self.is_fusionnet)
+        body = FrameBody(n_meas, (self.has_previous or self.sequences > 1) and self.is_fusionnet, sweep_variant, parity, have, give,
+                         len(next_frame[1]) if next_frame else 0, next_variant or 0)
+        self._launch(body, cur)
+        mark("frame launched")
+        self._commit(committed_pose, frame_id, cur, parity, have, give, next_variant, announced, full_K)
+        mark("done")
+        return s["depth"]
 
-        def graph_key(par, hv, gv, variant, variant_next):
-            # (stages that do not run in this graph do not tell graphs apart)
-            return (n_meas if hv < 2 else 0, kind[1], variant if hv < 2 else 0, par, hv, gv, n_meas_next if gv == 2 else 0, variant_next if gv == 2 else 0)
+    # ---- the parts of a step, in its order ---------------------------------------------------------------------------------
+    @staticmethod
+    def _is_announced_tensor(ready, image):
+        """Whether ``image`` is the very tensor that ``ready`` (a ``_prefetched`` record) was prepared from: same storage, unmodified since (its
+        ``_version``), same device, same strides.  A frame id alone does not identify an image; the engine keeps the announced tensor alive, so
+        the address cannot have been reused."""
+        return (ready["image"].data_ptr() == image.data_ptr() and ready["image_version"] == image._version and
+                ready["image"].device == image.device and tuple(ready["image"].stride()) == tuple(image.stride()))
 
-        key = graph_key(parity, have, give, sweep_variant, next_variant)
-        body = (n_meas, kind[1], sweep_variant, parity, have, give, n_meas_next, next_variant or 0)
+    def _prepared_level(self, frame_id, parity, reference_image, reference_pose, measurement_ids, measurement_poses, full_K):
+        """What the previous call prepared for this frame: 0 nothing, 1 its reference features, 2 also its sweep + encoder."""
+        ready = self._prefetched
+        if not self.direct or ready is None or frame_id is None or ready["frame_id"] != frame_id or ready["parity"] != parity:
+            return 0
+        if not self._is_announced_tensor(ready, reference_image):
+            # the announced frame came as ANOTHER tensor (re-materialised, modified): its prepared stages are not taken (ADVICE r5: say so)
+            self.lookahead_rejected += 1
+            if self.lookahead_rejected == 1:
+                import warnings
+                warnings.warn("DepthEngine.step: the frame announced by next_reference_image arrived as a different (or modified) tensor; its "
+                              "prepared features are recomputed.  Hand step() the very tensor that was announced to keep the look-ahead.", RuntimeWarning)
+            return 0
+        to_host = _pose_algebra.to_host
+        if ready["level"] == 2 and ready["measurement_ids"] == list(measurement_ids) and len(ready["measurement_poses"]) == len(measurement_poses) and \
+                torch.equal(ready["full_K"], to_host(full_K).reshape(-1, 3, 3)) and torch.equal(ready["pose"], to_host(reference_pose).reshape(-1, 4, 4)) and \
+                all(torch.equal(a, to_host(b).reshape(-1, 4, 4)) for a, b in zip(ready["measurement_poses"], measurement_poses)):
+            return 2
+        return 1
+
+    def _queue_measurement_features(self, target, n_meas, measurement_images, measurement_ids):
+        """This frame's measurement features, out of the cache or computed, into the sweep's buffers ``target``."""
+        # resolve every measurement frame BEFORE anything is inserted into the cache: an insertion may evict the least
+        # recently used entry, which could be a frame this very call still needs
+        fresh = []
+        for i in range(n_meas):
+            img = measurement_images[i] if measurement_images is not None else None
+            mid = measurement_ids[i]
+            if self.has_features(mid):
+                half = self._feature_cache.lookup(mid)
+            elif img is None:
+                raise ValueError(f"measurement frame {mid} is not cached and no image was given")
+            else:
+                half = self._features(img)[0].contiguous()
+                fresh.append((mid, half))
+            self._copies.add(target[i], half)
+        for mid, half in fresh:
+            self._remember(mid, half)
+
+    def _plan_next_frame(self, announced, reference_image, frame_id, parity, have):
+        """How much of the announced next frame this call computes: (0 nothing / 1 its features / 2 also its sweep + encoder, (pose, measurement
+        poses) of a frame whose sweep runs now -- its measurement features are queued into the other buffer set -- or None)."""
+        if not self.direct or announced["image"] is None or self.max_lookahead < 1:
+            return 0, None
+        if tuple(announced["image"].shape) != tuple(reference_image.shape):
+            raise ValueError("next_reference_image must have the reference image's shape")
+        poses, ids = announced["measurement_poses"], announced["measurement_ids"]
+        if not (self.max_lookahead >= 2 and announced["pose"] is not None and poses is not None and ids is not None and
+                announced["frame_id"] is not None and self.pose_algebra == "reference" and self.cache_features and
+                1 <= len(poses) <= _MAX_MEAS and len(ids) == len(poses) and
+                all(m is not None and (m in self._feature_cache or (m == frame_id and have >= 1)) for m in ids)):
+            return 1, None
+        self._allocate_static(len(poses))
+        for i, mid in enumerate(ids):
+            self._copies.add(self._direct_buffers["sets"][1 - parity]["meas_feat"][i], self._feature_cache[mid])
+        return 2, (announced["pose"], list(poses))
+
+    def _queue_images(self, cur, parity, have, give, reference_image, next_reference_image):
+        """The images into their homes (the decoder's last concatenation buffer ends with the image)."""
+        s = self._static
+        if self.direct:
+            if have < 1:
+                self._copies.add(cur["full_in"][:, 33:36], reference_image)
+            if give >= 1:
+                self._copies.add(self._direct_buffers["sets"][1 - parity]["full_in"][:, 33:36], next_reference_image)
+            s["image"], s["ref_half"] = cur["full_in"][:, 33:36], cur["enc_cat"][0][:, :32]
+        else:
+            self._copies.add(s["image"], reference_image)
+
+    def _launch(self, body, cur):
+        """Runs the frame ``body``: eagerly (no graphs, or the first frame of its kind), else by replaying its graph -- with everything this kind of
+        frame will need later captured and warmed first when the graph is new."""
+        kind = (body.n_meas, body.has_previous)
         if not self.use_graphs:
             self._frame_body(*body)
         elif kind not in self._warm:
@@ -1531,99 +1606,90 @@ class DepthEngine:
             torch.cuda.synchronize(self.device)
             self.warmup_seconds["eager_first_frames"] += time.perf_counter() - t_eager
         else:
-            known = set(self._graphs)
+            key, known = body.key(), len(self._graphs)
             if key not in self._graphs:
-                # Capture records launches, it executes nothing -- so what this kind of frame will need later is captured now, while the
-                # caller is still warming up: with look-ahead the steady-state pattern (this frame's share prefetched, the next frame's
-                # being prefetched) for both buffer sets and both sweep configurations, without it both configurations.  A later frame
-                # whose geometry asks for the other configuration finds its graph ready instead of paying ~0.1 s of capture mid-run.
-                t_capture = time.perf_counter()
-                self._graphs[key] = self._capture(body)
-                if give:
-                    tiled = self._tiled_variants      # the sweep's configurations x (two passes, one pass) [+ the MFMA sweep]: whichever a later geometry asks for
-                    choices = tiled if next_variant in tiled or sweep_variant in tiled else (sweep_variant,)
-                    for par in (0, 1):
-                        for v in (choices if give < 2 else (0,)):
-                            for vn in (choices if give == 2 else (0,)):
-                                k = graph_key(par, give, give, v, vn)
-                                if k not in self._graphs:
-                                    self._graphs[k] = self._capture((n_meas, kind[1], v, par, give, give, n_meas_next, vn))
-                elif sweep_variant in self._tiled_variants and have < 2:
-                    for par in ((0, 1) if self.direct else (0,)):
-                        for v in self._tiled_variants:
-                            k = graph_key(par, have, 0, v, 0)
-                            if k not in self._graphs:
-                                self._graphs[k] = self._capture((n_meas, kind[1], v, par, have, 0, 0, 0))
-                self.warmup_seconds["graph_capture"] += time.perf_counter() - t_capture
-            # (the graph of THIS frame, when it is new, is warmed like the ones captured ahead: its throw-away launches are undone the same way)
-            fresh = [k for k in self._graphs if k not in known]
-            if fresh and self.warm_captured_graphs:
-                # A graph's FIRST launch stalls the device for ~5 ms (its kernel arguments and code are set up then, not at capture):
-                # once per pre-captured graph, i.e. a few steps into every run, whenever a geometry first asks for another sweep
-                # configuration or buffer set.  So every graph captured ahead is launched once now, during warm-up, on throw-away
-                # results: the recurrent state is put back afterwards, and everything else the launch writes is rewritten by the real
-                # frame below (same image, same features) before anybody reads it.
-                # One exception: a frame whose sweep + encoder ran a frame ahead (have == 2) does NOT recompute them, and a fresh graph of the
-                # other parity runs ITS look-ahead stage -- other measurement count, other sweep configuration, the work list of another
-                # geometry -- on this frame's buffer set.  Those buffers are saved and put back as well.
-                t_warm = time.perf_counter()
-                keep = [s[k].clone() for k in ("h", "c", "prev_depth")] if self.is_fusionnet else []
-                keep_set = self._snapshot(cur) if (self.direct and have == 2) else None
-                for k in fresh:      # back to back per graph: a graph's next launch is queued while its previous one still runs, as in the steady
-                    for _ in range(self.warm_graph_launches):      # state, where the host is up to two frames ahead of the device
-                        self._graphs[k].replay()
-                for name, saved in zip(("h", "c", "prev_depth"), keep):
-                    s[name].copy_(saved)
-                if keep_set is not None:
-                    self._restore(cur, keep_set)
-                if self.direct:      # (the splat's invariant: a frame finds its estimate buffer all-zero; the throw-away launches wrote into both)
-                    for buffer_set in sets:
-                        buffer_set["estimate"].zero_()
-                torch.cuda.synchronize(self.device)
-                self.warmup_seconds["graph_first_launches"] += time.perf_counter() - t_warm
-                self.warmup_graphs_launched += len(fresh)
+                self._capture_ahead(body)
+                if self.warm_captured_graphs:      # (the graph of THIS frame is warmed like the ones captured ahead: its throw-away launches are undone the same way)
+                    self._warm_graphs(list(self._graphs)[known:], cur, body.have)      # (a dict keeps the order of insertion: the new ones)
             self._graphs[key].replay()
-        mark("frame launched")
+
+    def _capture_ahead(self, body):
+        """Captures the graph of ``body`` and, behind it, those this kind of frame will need later.  Capture records launches, it executes nothing
+        -- so they are captured now, while the caller is still warming up: with look-ahead the steady-state pattern (this frame's share
+        prefetched, the next frame's being prefetched) for both buffer sets and both sweep configurations, without it both configurations.  A
+        later frame whose geometry asks for the other configuration finds its graph ready instead of paying ~0.1 s of capture mid-run."""
+        def capture(b):
+            if b.key() not in self._graphs:
+                self._graphs[b.key()] = self._capture(b)
+
+        t_capture = time.perf_counter()
+        capture(body)
+        give, tiled = body.give, self._tiled_variants
+        if give:
+            # the sweep's configurations x (two passes, one pass) [+ the MFMA sweep]: whichever a later geometry asks for
+            choices = tiled if body.next_variant in tiled or body.sweep_variant in tiled else (body.sweep_variant,)
+            for par in (0, 1):
+                for v in (choices if give < 2 else (0,)):
+                    for vn in (choices if give == 2 else (0,)):
+                        capture(body._replace(sweep_variant=v, parity=par, have=give, next_variant=vn))
+        elif body.sweep_variant in tiled and body.have < 2:
+            for par in ((0, 1) if self.direct else (0,)):
+                for v in tiled:
+                    capture(body._replace(sweep_variant=v, parity=par))
+        self.warmup_seconds["graph_capture"] += time.perf_counter() - t_capture
+
+    def _warm_graphs(self, fresh, cur, have):
+        """Launches the newly captured graphs ``fresh`` on throw-away results and puts the state back.  A graph's FIRST launch stalls the device
+        for ~5 ms (its kernel arguments and code are set up then, not at capture): once per pre-captured graph, i.e. a few steps into every
+        run, whenever a geometry first asks for another sweep configuration or buffer set.  So every graph captured ahead is launched now,
+        during warm-up: the recurrent state is put back afterwards, and everything else the launch writes is rewritten by the real frame
+        (same image, same features) before anybody reads it.
+        One exception: a frame whose sweep + encoder ran a frame ahead (have == 2) does NOT recompute them, and a fresh graph of the other
+        parity runs ITS look-ahead stage -- other measurement count, other sweep configuration, the work list of another geometry -- on this
+        frame's buffer set ``cur``.  Those buffers are saved and put back as well."""
+        t_warm = time.perf_counter()
+        s = self._static
+        keep = [(s[k], s[k].clone()) for k in ("h", "c", "prev_depth")] if self.is_fusionnet else []
+        keep += [(t, t.clone()) for t in self._tensors(cur)] if (self.direct and have == 2) else []
+        for k in fresh:      # back to back per graph: a graph's next launch is queued while its previous one still runs, as in the steady
+            for _ in range(self.warm_graph_launches):      # state, where the host is up to two frames ahead of the device
+                self._graphs[k].replay()
+        for tensor, saved in keep:
+            tensor.copy_(saved)
+        if self.direct:      # (the splat's invariant: a frame finds its estimate buffer all-zero; the throw-away launches wrote into both)
+            for buffer_set in self._direct_buffers["sets"]:
+                buffer_set["estimate"].zero_()
+        torch.cuda.synchronize(self.device)
+        self.warmup_seconds["graph_first_launches"] += time.perf_counter() - t_warm
+        self.warmup_graphs_launched += len(fresh)
+
+    def _commit(self, committed_pose, frame_id, cur, parity, have, give, next_variant, announced, full_K):
+        """The launched frame becomes "the previous frame" (only now: a frame that raised has left the state that of one frame), what was
+        announced and computed ahead is recorded for the next call, and the frame's features go into the cache."""
         self._prev_pose_host = committed_pose
         self._no_previous[:] = False
         self.has_previous = True
         if self.direct:
             self._prefetched = None
-            if give >= 1 and next_frame_id is not None:
-                self._prefetched = dict(frame_id=next_frame_id, parity=1 - parity, level=give, sweep_variant=next_variant,
-                                        image=next_reference_image, image_version=next_reference_image._version)
+            if give >= 1 and announced["frame_id"] is not None:
+                self._prefetched = dict(frame_id=announced["frame_id"], parity=1 - parity, level=give, sweep_variant=next_variant,
+                                        image=announced["image"], image_version=announced["image"]._version)
                 if give == 2:
                     to_host = _pose_algebra.to_host
-                    self._prefetched.update(pose=to_host(next_reference_pose).reshape(-1, 4, 4).clone(), measurement_ids=list(next_measurement_ids),
+                    self._prefetched.update(pose=to_host(announced["pose"]).reshape(-1, 4, 4).clone(), measurement_ids=list(announced["measurement_ids"]),
                                             full_K=to_host(full_K).reshape(-1, 3, 3).clone(),      # (the sweep ahead used THIS call's intrinsics)
-                                            measurement_poses=[to_host(p).reshape(-1, 4, 4).clone() for p in next_measurement_poses])
+                                            measurement_poses=[to_host(p).reshape(-1, 4, 4).clone() for p in announced["measurement_poses"]])
             self._parity = 1 - parity
         if self.cache_features and frame_id is not None and have < 1:
-            self._remember(frame_id, cur["ref_half_nhwc"] if (self.direct and self.sweep_mfma) else s["ref_half"])
-        mark("done")
-        return s["depth"]
+            self._remember(frame_id, cur["ref_half_nhwc"] if (self.direct and self.sweep_mfma) else self._static["ref_half"])
 
     @staticmethod
-    def _snapshot(tree):
-        """Clones every tensor of a (nested dict / list of) buffer set."""
+    def _tensors(tree):
+        """Every tensor of a (nested dict / list of) buffer set, in a fixed order."""
         if isinstance(tree, torch.Tensor):
-            return tree.clone()
-        if isinstance(tree, dict):
-            return {k: DepthEngine._snapshot(v) for k, v in tree.items()}
-        if isinstance(tree, (list, tuple)):
-            return [DepthEngine._snapshot(v) for v in tree]
-        return None
-
-    @staticmethod
-    def _restore(tree, saved):
-        if isinstance(tree, torch.Tensor):
-            tree.copy_(saved)
-        elif isinstance(tree, dict):
-            for k, v in tree.items():
-                DepthEngine._restore(v, saved[k])
-        elif isinstance(tree, (list, tuple)):
-            for v, w in zip(tree, saved):
-                DepthEngine._restore(v, w)
+            return [tree]
+        values = tree.values() if isinstance(tree, dict) else tree if isinstance(tree, (list, tuple)) else ()
+        return [t for v in values for t in DepthEngine._tensors(v)]
 
     def graph_memory_report(self):
         """Captured frame graphs and the device memory of their private pools (bytes; None where the runtime does not say)."""
@@ -1651,16 +1717,16 @@ class DepthEngine:
         if self._lstm_packed is not None:
             self._lstm_packed.copy_(_ops.bottleneck_conv_pack(self.lstm.lstm_cell.conv.weight.detach()))
 
-    def _capture(self, key):
-        """Captures the frame body for ``key`` into a hipGraph.  Capture only records the launches (nothing executes, no
+    def _capture(self, body):
+        """Captures the frame body ``body`` (a FrameBody) into a hipGraph.  Capture only records the launches (nothing executes, no
         state buffer changes); the caller replays the graph to actually run the frame."""
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
         if getattr(self, "graph_debug", False):     # bench.py counts the kernel nodes of the frame graph from its dot dump
             graph.enable_debug_mode()
         with torch.cuda.graph(graph):
-            self._frame_body(*key)
-        if self.direct and key[5] and key[4] >= key[5]:      # a body with a second branch (see _frame_body_direct)
+            self._frame_body(*body)
+        if self.direct and body.give and body.have >= body.give:      # a body with a second branch (see _frame_body_direct)
             for _ in range(_GRAPH_QUEUE_FILLERS):
                 self._capture_queue_filler()
         return graph

@@ -258,7 +258,7 @@ def _run_frame(engine, frames, results, timer, indices, upcoming=None):
     ref_pose, full_K = scene.pose(reference_index), FrameInput.intrinsics(pre)
     meas_images, meas_poses = [], []
     for m in measurement_indices:
-        if engine.cache_features and m in engine._feature_cache:
+        if engine.cache_features and engine.has_features(m):
             meas_images.append(None)     # features of this keyframe are cached: no need to load / pre-process the image again
         else:
             meas_images.append(frames.image(pre, m))

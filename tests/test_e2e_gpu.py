@@ -432,6 +432,48 @@ def test_lookahead_is_bit_identical(hip_device):
     assert deep.sweep_variant_counts == plain.sweep_variant_counts
 
 
+def test_graph_capture_order_of_the_lookahead_schedule(hip_device):
+    """WHICH graphs an engine captures, and in which order, is part of its speed: the queue-filler graphs (dvmvs/engine.py, _GRAPH_QUEUE_FILLERS)
+    put every frame graph's second branch on the same hardware queue only while the order of instantiations stays what it is.  The start of
+    test_lookahead_is_bit_identical's schedule (six frames, a tracking loss, frame 117; every announcement right) through engines at look-ahead
+    levels 1 and 2: the graph keys in capture order, the filler graphs, the graphs warmed and the frames per sweep configuration equal what
+    the engine gave before its step() was split into parts (recorded on an MI355X from that commit)."""
+    dev = hip_device
+    _, shallow = build(dev, fusion=True, fold_bn=True, cache_features=True, use_graphs=True, max_lookahead=1)
+    _, deep = build(dev, fusion=True, fold_bn=True, cache_features=True, use_graphs=True, max_lookahead=2)
+    fullK = syn.full_K()
+    lines = syn.keyframe_index_lines(2)
+    schedule = [(0, True), (1, True), (2, True), (3, True), (4, False), (5, True), (None, None), (117, True)]
+    frames = [(None if i is None else lines[i], flag) for i, flag in schedule]
+    held = {}
+    image = lambda i: held.setdefault(i, syn.e2e_image(i).to(dev))
+    for n, (item, announce) in enumerate(frames):
+        if item is None:
+            shallow.reset()
+            deep.reset()
+            continue
+        r, ms = item
+        args = (image(r), syn.pose(r), [syn.e2e_image(i).to(dev) for i in ms], [syn.pose(i) for i in ms], fullK)
+        upcoming = next((f[0] for f in frames[n + 1:] if f[0] is not None), None)
+        kw1, kw2 = {}, {}
+        if announce and upcoming is not None:
+            nr, nms = upcoming
+            kw1 = dict(next_reference_image=image(nr), next_frame_id=nr)
+            kw2 = dict(kw1, next_reference_pose=syn.pose(nr), next_measurement_poses=[syn.pose(i) for i in nms], next_measurement_ids=list(nms))
+        shallow.step(*args, frame_id=r, measurement_ids=list(ms), **kw1)
+        deep.step(*args, frame_id=r, measurement_ids=list(ms), **kw2)
+    torch.cuda.synchronize()
+    for name, e in (("level 1", shallow), ("level 2", deep)):
+        print(f"{name}: graphs {list(e._graphs)}; fillers {len(e._filler_graphs)}; warmed {e.warmup_graphs_launched}; frames per sweep {e.sweep_variant_counts}")
+    # (n_meas, has_previous, sweep_variant, parity, have, give, n_meas_next, next_variant)
+    assert list(shallow._graphs) == [(2, True, 6, 0, 1, 1, 0, 0), (2, True, 6, 1, 1, 1, 0, 0), (2, True, 6, 0, 1, 0, 0, 0), (2, True, 6, 1, 1, 0, 0, 0),
+                                     (2, True, 6, 1, 0, 1, 0, 0), (2, False, 6, 0, 1, 0, 0, 0), (2, False, 6, 1, 1, 0, 0, 0)]
+    assert len(shallow._filler_graphs) == 2 and shallow.warmup_graphs_launched == 7 and shallow.sweep_variant_counts == {6: 7}
+    assert list(deep._graphs) == [(0, True, 0, 0, 2, 2, 2, 6), (0, True, 0, 1, 2, 2, 2, 6), (0, True, 0, 0, 2, 0, 0, 0), (2, True, 6, 1, 0, 1, 0, 0),
+                                  (2, True, 6, 0, 1, 1, 0, 0), (2, True, 6, 1, 1, 1, 0, 0), (2, False, 6, 0, 1, 0, 0, 0), (2, False, 6, 1, 1, 0, 0, 0)]
+    assert len(deep._filler_graphs) == 4 and deep.warmup_graphs_launched == 8 and deep.sweep_variant_counts == {6: 7}
+
+
 @pytest.mark.parametrize("seed", [11, 12])
 def test_lookahead_random_schedules_are_bit_identical(hip_device, seed):
     """Property test: random schedules of keyframes with correct / wrong / missing announcements, an announced frame id
