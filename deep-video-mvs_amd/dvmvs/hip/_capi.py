@@ -126,6 +126,9 @@ SIGNATURES = {
     "dvmvs_nearest_distance_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_size_t, _c_fp, _c_fp,
                                             _c_stream]),
     "dvmvs_distance_metrics_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, ctypes.c_float, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_consistency_matrices": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_stream]),
+    "dvmvs_depth_consistency_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int,
+                                             ctypes.c_float, ctypes.c_float, _c_int, _c_int, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -140,6 +143,8 @@ ADDED_WITHIN_ABI_TSDF_FUSE = ("dvmvs_tsdf_integrate_frames_workspace_bytes", "dv
 # ... and the fifth (nearest-point distances between point clouds and the 3-D reconstruction metrics)
 ADDED_WITHIN_ABI_NEAREST = ("dvmvs_nearest_workspace_bytes", "dvmvs_nearest_query_workspace_bytes", "dvmvs_nearest_build",
                             "dvmvs_nearest_distance_fwd", "dvmvs_distance_metrics_fwd")
+# ... and the sixth (filtering depth maps by multi-view geometric consistency)
+ADDED_WITHIN_ABI_CONSISTENCY = ("dvmvs_consistency_matrices", "dvmvs_depth_consistency_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -159,7 +164,7 @@ def lib():
                 f"(or __graft_entry__.build()). The plane-sweep ops have no CPU / eager fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
-                 + ADDED_WITHIN_ABI_NEAREST)
+                 + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

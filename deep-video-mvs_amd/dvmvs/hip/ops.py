@@ -18,7 +18,7 @@ from dvmvs.hip import _capi
 __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lstm_gates", "depth_reproject", "depth_reproject_lowres",
            "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress", "preprocess_rgb",
            "preprocess_depth", "depth_errors", "tsdf_raycast", "tsdf_raycast_mask", "tsdf_integrate_frames", "nearest_distance", "nearest_build",
-           "nearest_query", "distance_metrics"]
+           "nearest_query", "distance_metrics", "consistency_matrices", "depth_consistency"]
 
 
 # two-pass tiled sweep (spill list in the workspace): see dvmvs_cost_volume_workspace_bytes_two_pass in the header
@@ -1673,3 +1673,105 @@ def distance_metrics(dist_pred: Tensor, dist_gt: Tensor, threshold: float = 0.05
                                                     None if counts is None else _ptr(counts), _stream(dist_pred))
     _capi.check(rc, "dvmvs_distance_metrics_fwd")
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# filtering depth maps by multi-view geometric consistency (inference only)
+# ----------------------------------------------------------------------------------------------------------------------
+CONSISTENCY_MAX_SOURCES = 16
+
+
+def _consistency_cameras(name, K, poses, sources):
+    """Checks types and shapes of the camera tensors of the two consistency ops; returns (N, S)."""
+    for label, t in (("K", K), ("poses", poses), ("sources", sources)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"dvmvs::{name}: {label} must be a tensor, got {type(t).__name__}")
+    if K.dtype != torch.float32 or K.dim() != 3 or tuple(K.shape[1:]) != (3, 3) or K.shape[0] < 1:
+        raise ValueError(f"dvmvs::{name}: K must be float32 [N,3,3], got {K.dtype} {tuple(K.shape)}")
+    N = int(K.shape[0])
+    if poses.dtype != torch.float32 or tuple(poses.shape) != (N, 4, 4):
+        raise ValueError(f"dvmvs::{name}: poses must be float32 [{N},4,4] camera-to-world, got {poses.dtype} {tuple(poses.shape)}")
+    if sources.dtype != torch.int32 or sources.dim() != 2 or sources.shape[0] != N or sources.shape[1] > CONSISTENCY_MAX_SOURCES:
+        raise ValueError(f"dvmvs::{name}: sources must be int32 [{N},S] with S <= {CONSISTENCY_MAX_SOURCES}, got {sources.dtype} "
+                         f"{tuple(sources.shape)}")
+    if N > 65535:
+        raise ValueError(f"dvmvs::{name}: at most 65535 frames per call, got {N}")
+    return N, int(sources.shape[1])
+
+
+def _consistency_devices(name, **tensors):
+    """Every tensor on the GPU, and on the same one."""
+    first = None
+    for label, t in tensors.items():
+        if t.device.type != "cuda":
+            _no_cpu(name)
+        first = t.device if first is None else first
+        if t.device != first:
+            raise ValueError(f"dvmvs::{name}: {label} is on {t.device}, not on {first} like the other tensors")
+
+
+def consistency_matrices(K: Tensor, poses: Tensor, sources: Tensor) -> Tensor:
+    """Step A of the consistency filter (``dvmvs_consistency_matrices``; definition in include/dvmvs_hip.h): for every (frame r, slot j) the
+    float32 (A, b) that take a pixel of r and its depth into source ``sources[r][j]``, and (A', b') for the way back, from float64
+    arithmetic on the device.  ``K`` float32 [N,3,3], camera-to-world ``poses`` float32 [N,4,4], ``sources`` int32 [N,S] (S <= 16), all on
+    the GPU -> float32 [N,S,2,12]; a skipped slot (negative, >= N or the frame itself) holds zeros.  One tiny launch on the current stream."""
+    N, S = _consistency_cameras("consistency_matrices", K, poses, sources)
+    _consistency_devices("consistency_matrices", K=K, poses=poses, sources=sources)
+    K, poses, sources = K.contiguous(), poses.contiguous(), sources.contiguous()
+    out = torch.empty((N, S, 2, 12), dtype=torch.float32, device=K.device)
+    if S == 0:
+        return out
+    with torch.cuda.device(K.device):
+        rc = _capi.lib().dvmvs_consistency_matrices(_ptr(K), _ptr(poses), _ptr(sources), _ptr(out), N, S, _stream(K))
+    _capi.check(rc, "dvmvs_consistency_matrices")
+    return out
+
+
+def depth_consistency(depths: Tensor, K: Tensor, poses: Tensor, sources: Tensor, pixel_threshold: float = 1.0,
+                      relative_threshold: float = 0.01, min_views: int = 2, average: bool = True, with_count: bool = True,
+                      with_points: bool = False, matrices: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """Filters N depth maps by multi-view geometric consistency in one launch (csrc/depth_consistency.hip; definition in
+    include/dvmvs_hip.h): a pixel of frame r is projected into each source ``sources[r][j]``, that map is sampled there, the sample is
+    projected back, and the source agrees when the pixel returns within ``pixel_threshold`` pixels and ``relative_threshold`` of its depth.
+    ``depths`` float32 [N,H,W], ``K`` float32 [N,3,3], camera-to-world ``poses`` float32 [N,4,4], ``sources`` int32 [N,S], all on one GPU.
+    Returns ``(depth, count or None, points or None)``: ``depth`` float32 [N,H,W], 0 where fewer than ``min_views`` sources agree and the
+    pixel's own depth (``average=False``) or the mean of it and the agreeing re-projections elsewhere; ``count`` uint8 [N,H,W];
+    ``points`` float32 [N,H,W,3], the kept pixels in world space (zeros elsewhere).  ``matrices``: ``consistency_matrices(K, poses,
+    sources)`` when the caller already has it (saves that launch); ``out``: a contiguous float32 [N,H,W] tensor for ``depth``, e.g. a
+    view that starts anywhere inside a larger buffer (must not overlap ``depths``).  Runs on the current stream; no host read and
+    no synchronisation."""
+    name = "depth_consistency"
+    if not torch.is_tensor(depths):
+        raise TypeError(f"dvmvs::{name}: depths must be a tensor, got {type(depths).__name__}")
+    N, S = _consistency_cameras(name, K, poses, sources)
+    if depths.dtype != torch.float32 or depths.dim() != 3 or depths.shape[0] != N or depths.shape[1] < 1 or depths.shape[2] < 1:
+        raise ValueError(f"dvmvs::{name}: depths must be non-empty float32 [{N},H,W] like K, got {depths.dtype} {tuple(depths.shape)}")
+    H, W = int(depths.shape[1]), int(depths.shape[2])
+    if 3 * H * W >= 2 ** 31:
+        raise ValueError(f"dvmvs::{name}: a {H}x{W} map is too large (3 H W must stay below 2^31)")
+    pixel_threshold, relative_threshold, min_views = float(pixel_threshold), float(relative_threshold), int(min_views)
+    if pixel_threshold != pixel_threshold or relative_threshold != relative_threshold:
+        raise ValueError(f"dvmvs::{name}: a threshold is NaN")
+    if min_views < 0:
+        raise ValueError(f"dvmvs::{name}: min_views must not be negative, got {min_views}")
+    _consistency_devices(name, depths=depths, K=K, poses=poses, sources=sources)
+    if matrices is None:
+        matrices = consistency_matrices(K, poses, sources)
+    elif (not torch.is_tensor(matrices) or matrices.device != depths.device or matrices.dtype != torch.float32
+          or tuple(matrices.shape) != (N, S, 2, 12) or not matrices.is_contiguous()):
+        raise ValueError(f"dvmvs::{name}: matrices must be the contiguous float32 [{N},{S},2,12] tensor of consistency_matrices on {depths.device}")
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.float32, device=depths.device)
+    elif (not torch.is_tensor(out) or out.device != depths.device or out.dtype != torch.float32 or tuple(out.shape) != (N, H, W)
+          or not out.is_contiguous()):
+        raise ValueError(f"dvmvs::{name}: out must be a contiguous float32 [{N},{H},{W}] tensor on {depths.device}")
+    depths, K, poses, sources = depths.contiguous(), K.contiguous(), poses.contiguous(), sources.contiguous()
+    count = torch.empty((N, H, W), dtype=torch.uint8, device=depths.device) if with_count else None
+    points = torch.empty((N, H, W, 3), dtype=torch.float32, device=depths.device) if with_points else None
+    with torch.cuda.device(depths.device):
+        rc = _capi.lib().dvmvs_depth_consistency_fwd(
+            _ptr(depths), _ptr(K), _ptr(poses), _ptr(sources), _ptr(matrices), _ptr(out), None if count is None else _ptr(count),
+            None if points is None else _ptr(points), N, S, H, W, pixel_threshold, relative_threshold, min_views, 1 if average else 0,
+            _stream(depths))
+    _capi.check(rc, "dvmvs_depth_consistency_fwd")
+    return out, count, points

@@ -378,12 +378,28 @@ class LiveFusion:
     calls earlier.  So the host runs at most 8 frames ahead of the device's copy queue, and no further.  (That wait is on an event, which
     torch's synchronisation detector does not see.)
     ASSUMPTION: every call (``add``, ``flush``, ``volume`` and whatever uses the volume) is issued on ONE stream.  Everything is then in
-    stream order -- a ring slot is rewritten only by copies enqueued after the launch that read it -- so no event guards the rings."""
+    stream order -- a ring slot is rewritten only by copies enqueued after the launch that read it -- so no event guards the rings.
 
-    def __init__(self, vol_bnds, voxel_size=0.025, max_depth=5.0, batch=8, device="cuda"):
+    ``min_consistent_views`` > 0 filters every batch by multi-view geometric consistency before it is fused (``dvmvs.consistency``, one more
+    launch pair per flush): the pending frames are checked against each other, frame i against the ``consistency_sources`` frames nearest
+    to it in the batch (``nearest_sources``), and a pixel is fused, with its own depth (``average=False``), only where at least that many of
+    them agree within ``pixel_threshold`` pixels and ``relative_threshold`` of the depth.  The source tables of every batch size up to
+    ``batch`` go up once, in the constructor, so ``add`` and ``flush`` stay free of blocking copies and host reads.  CONSEQUENCE: a flush of
+    a single pending frame (the tail of a scene, or ``batch=1``) has no neighbour to agree with and fuses nothing.  With the default 0
+    nothing is allocated or launched for the filter and the volume's bits are those of the unfiltered fusion."""
+
+    def __init__(self, vol_bnds, voxel_size=0.025, max_depth=5.0, batch=8, device="cuda", min_consistent_views=0, consistency_sources=4,
+                 pixel_threshold=1.0, relative_threshold=0.01):
         batch = int(batch)
         if batch < 1:
             raise ValueError(f"LiveFusion: batch must be at least 1, got {batch}")
+        min_consistent_views, consistency_sources = int(min_consistent_views), int(consistency_sources)
+        if min_consistent_views < 0:
+            raise ValueError(f"LiveFusion: min_consistent_views must not be negative, got {min_consistent_views}")
+        if not 0 <= consistency_sources <= 16:
+            raise ValueError(f"LiveFusion: consistency_sources must be between 0 and 16, got {consistency_sources}")
+        if float(pixel_threshold) != float(pixel_threshold) or float(relative_threshold) != float(relative_threshold):
+            raise ValueError("LiveFusion: a consistency threshold is NaN")
         if not float(voxel_size) > 0.0:
             raise ValueError(f"LiveFusion: voxel_size must be positive, got {voxel_size}")
         if float(max_depth) != float(max_depth):
@@ -395,6 +411,14 @@ class LiveFusion:
         self._uploader = FrameUploader(self.device, slots=8)
         self._depth = self._rgb = self._K = self._P = None
         self._weights, self._pending, self.frames = [], 0, 0
+        self.min_consistent_views, self.pixel_threshold, self.relative_threshold = min_consistent_views, float(pixel_threshold), float(relative_threshold)
+        self._filtered = self._source_tables = None
+        if min_consistent_views > 0:
+            from dvmvs.consistency import nearest_sources
+            tables = np.full((batch, batch, consistency_sources), -1, dtype=np.int32)     # [n - 1, :n] = the table of a flush of n frames
+            for n in range(1, batch + 1):
+                tables[n - 1, :n] = nearest_sources(n, consistency_sources)
+            self._source_tables = torch.as_tensor(tables, device=self.device)
 
     def _rings(self, h, w):
         if self._depth is None:
@@ -403,6 +427,8 @@ class LiveFusion:
             self._rgb = torch.empty((self.batch, h, w, 3), dtype=torch.uint8, device=dev)
             self._K = torch.empty((self.batch, 3, 3), dtype=torch.float32, device=dev)
             self._P = torch.empty((self.batch, 4, 4), dtype=torch.float32, device=dev)
+            if self.min_consistent_views > 0:
+                self._filtered = torch.empty((self.batch, h, w), dtype=torch.float32, device=dev)
         elif tuple(self._depth.shape[1:]) != (h, w):
             raise ValueError(f"LiveFusion: a {h}x{w} frame in a run of {self._depth.shape[1]}x{self._depth.shape[2]} frames")
 
@@ -443,8 +469,13 @@ class LiveFusion:
         n = self._pending
         if n == 0:
             return
-        self._volume.integrate_frames(self._rgb[:n], self._depth[:n], self._K[:n], self._P[:n], obs_weight=self._weights,
-                                      max_depth=self.max_depth)
+        depth = self._depth[:n]
+        if self.min_consistent_views > 0:
+            from dvmvs.hip import ops
+            depth, _, _ = ops.depth_consistency(depth, self._K[:n], self._P[:n], self._source_tables[n - 1, :n], self.pixel_threshold,
+                                                self.relative_threshold, self.min_consistent_views, average=False, with_count=False,
+                                                out=self._filtered[:n])
+        self._volume.integrate_frames(self._rgb[:n], depth, self._K[:n], self._P[:n], obs_weight=self._weights, max_depth=self.max_depth)
         self._weights, self._pending = [], 0
 
     @property
@@ -460,7 +491,8 @@ def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dat
 
 def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, scene_name, system_name, voxel_size, max_depth,
         use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False,
-        evaluate_3d=False, threshold_3d=0.05):
+        evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
+        consistency_relative=0.01, save_point_cloud=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -477,7 +509,19 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     keep that surface's vertices on the device, score the system's surface against them (``TSDFVolume.score_against`` with
     ``threshold_3d`` metres), print the six metrics on one line and save them as ``<mesh name of the system>_errors3d.npz``: ``arr_0``
     float32 [6], ``names``, ``counts`` int64 [2] (vertices of the prediction and of the ground truth) and ``threshold``.  Without the flag
-    the program writes what it writes without it, byte for byte."""
+    the program writes what it writes without it, byte for byte.
+
+    ``filter_consistency``: after the masks above, the keyframe predictions go up once and are filtered by multi-view geometric consistency
+    in one launch (``dvmvs.consistency.filter_depths``): a pixel is kept, with its own depth, where at least ``consistency_views`` of the
+    ``consistency_sources`` keyframes nearest to it in keyframe order (never across a "TRACKING LOST" line) agree within
+    ``consistency_pixel`` pixels and ``consistency_relative`` of the depth.  The filtered predictions come down and are fused as before; the
+    volume bounds are still those of the UNFILTERED predictions, so the meshes with and without the filter share a grid.  The system's mesh
+    and the files of ``evaluate_3d`` and ``render_keyframes`` are written under ``<system_name>+consistent``; the kept share of the valid
+    pixels is printed.  ``save_point_cloud`` (needs ``filter_consistency``): also writes ``<mesh name>_pointcloud.ply``, the kept pixels of
+    a second call that averages the agreeing depths, as coloured world-space points.  Without these flags the program writes what it
+    writes without them, byte for byte."""
+    if save_point_cloud and not filter_consistency:
+        raise ValueError("save_point_cloud needs filter_consistency: the point cloud is made of the pixels the filter keeps")
     from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, load_image_u8, resize_nearest
     if device_preprocess:
         load_image = load_image_u8       # resize_nearest only selects pixels: the uint8 values are those of the float path's astype
@@ -496,10 +540,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     nmeas = system_name.split("_")[2]
     with open(os.path.join(data_folder, "indices", f"keyframe+{dataset_name}+{scene_name}+nmeas+{nmeas}")) as f:
         keyframe_lines = [line.rstrip("\n") for line in f if line.strip()]
-    keyframe_poses, keyframe_image_filenames = [], []
+    keyframe_poses, keyframe_image_filenames, keyframe_segments = [], [], []
+    segment = 0
     for line in keyframe_lines:
         if line == "TRACKING LOST":
+            segment += 1
             continue
+        keyframe_segments.append(segment)
         image_filename = os.path.join(scene_folder, "images", line.split(" ")[0])
         keyframe_poses.append(all_poses[all_image_filenames.index(image_filename)])
         keyframe_image_filenames.append(image_filename)
@@ -537,6 +584,14 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         volume_bounds = TSDFFusion.calculate_volume_bounds(keyframe_predictions, keyframe_poses, scaled_K)
     volume_bounds *= 1.05      # margin for errors in the bounds
 
+    point_cloud = None
+    if filter_consistency:
+        system_name = f"{system_name}+consistent"
+        if keyframe_predictions:
+            keyframe_predictions, point_cloud = _filter_keyframes(
+                keyframe_predictions, keyframe_images if save_point_cloud else None, keyframe_poses, scaled_K, keyframe_segments,
+                consistency_views, consistency_sources, consistency_pixel, consistency_relative, device)
+
     os.makedirs(reconstruction_folder, exist_ok=True)
     groundtruth_vertices = None
     if save_groundtruth or evaluate_3d:
@@ -555,11 +610,33 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
     system_mesh_name = _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name, dataset_name, scene_name)
     TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K, system_mesh_name, save_progressive)
+    if save_point_cloud:
+        print("Saving point cloud to", system_mesh_name + "_pointcloud.ply")
+        TSDFFusion.pcwrite(system_mesh_name + "_pointcloud.ply", point_cloud if point_cloud is not None else np.zeros((0, 6), np.float32))
     if evaluate_3d:
         _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name)
     if render_keyframes:
         _render_keyframes(volume, keyframe_poses, keyframe_image_filenames, scaled_K, preprocessor, prediction_height, prediction_width,
                           scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
+
+
+def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sources, pixel_threshold, relative_threshold, device):
+    """The keyframe predictions filtered by consistency (a list of host arrays, as they came) and, with ``images``, the fused point cloud
+    [P,6] xyzrgb on the host."""
+    from dvmvs.consistency import filter_depths, fused_point_cloud, nearest_sources
+    depths = torch.as_tensor(np.stack(predictions).astype(np.float32), device=device)
+    cameras = torch.as_tensor(np.stack(poses).astype(np.float32), device=device)
+    sources = torch.as_tensor(nearest_sources(len(predictions), n_sources, segments), device=device)
+    thresholds = dict(pixel_threshold=pixel_threshold, relative_threshold=relative_threshold, min_views=min_views)
+    kept, _, _ = filter_depths(depths, K, cameras, sources, average=False, with_count=False, **thresholds)
+    valid = torch.isfinite(depths) & (depths > 0)
+    print("Consistency filter: kept {:.1f} % of the valid pixels of {} keyframes".format(
+        100.0 * float((kept > 0).sum()) / max(int(valid.sum()), 1), len(predictions)))
+    cloud = None
+    if images is not None:
+        averaged, _, points = filter_depths(depths, K, cameras, sources, average=True, with_count=False, with_points=True, **thresholds)
+        cloud = fused_point_cloud(averaged, points, np.stack(images)).cpu().numpy()
+    return list(kept.cpu().numpy()), cloud
 
 
 def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name):
@@ -596,7 +673,7 @@ def _render_keyframes(volume, poses, image_filenames, K, preprocessor, height, w
         save_predictions(rendered, system_name, scene_name, save_folder)
 
 
-def main(argv=None):
+def build_parser():
     parser = ArgumentParser(description="TSDF reconstruction of a scene from saved keyframe depth predictions (writes .ply meshes)")
     parser.add_argument("--reconstruction_folder", default="./reconstructions", type=str)
     parser.add_argument("--prediction_folder", default="./predictions", type=str)
@@ -618,7 +695,20 @@ def main(argv=None):
                         help="also fuse the ground-truth depth maps and score the system's mesh against that surface in 3-D on the device "
                              "(accuracy, completeness, chamfer, precision, recall, F-score; saved as <mesh name>_errors3d.npz)")
     parser.add_argument("--threshold_3d", default=0.05, type=float, help="distance threshold of precision / recall / F-score, metres")
-    args = parser.parse_args(argv)
+    parser.add_argument("--filter_consistency", action="store_true",
+                        help="fuse only the pixels that neighbouring keyframes agree on (multi-view geometric consistency, on the device); "
+                             "files are written under <system>+consistent")
+    parser.add_argument("--consistency_views", default=2, type=int, help="neighbouring keyframes that must agree for a pixel to be kept")
+    parser.add_argument("--consistency_sources", default=4, type=int, help="neighbouring keyframes each keyframe is checked against (at most 16)")
+    parser.add_argument("--consistency_pixel", default=1.0, type=float, help="largest re-projection error of an agreeing view, pixels")
+    parser.add_argument("--consistency_relative", default=0.01, type=float, help="largest relative depth difference of an agreeing view")
+    parser.add_argument("--save_point_cloud", action="store_true",
+                        help="with --filter_consistency: also write the kept pixels as a coloured point cloud (<mesh name>_pointcloud.ply)")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     run(**vars(args))
 
 

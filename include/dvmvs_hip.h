@@ -53,7 +53,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_tsdf_integrate_frames* (fusing a batch of frames into a TSDF volume in one launch); no earlier signature
  * changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_nearest_* and dvmvs_distance_metrics_fwd (exact nearest-point distances between point clouds and the 3-D
- * reconstruction metrics); no earlier signature changed, the number stays 11 by the same rule. */
+ * reconstruction metrics); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_consistency_matrices and dvmvs_depth_consistency_fwd (filtering depth maps by multi-view geometric
+ * consistency); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -719,6 +721,58 @@ int dvmvs_nearest_distance_fwd(const float* query, long long N, const float* tar
                                void* query_workspace, size_t query_workspace_bytes, float* dist, int* index, dvmvs_stream_t stream);
 int dvmvs_distance_metrics_fwd(const float* dist_a, long long Na, const float* dist_b, long long Nb, float threshold, float* row,
                                long long* counts, dvmvs_stream_t stream);
+
+/*
+ * Depth-map consistency (ABI 11, later addition): keeps the pixels of N depth maps that enough neighbouring views agree on.  The reference
+ * project has nothing for this: the definition is this project's own (the geometric check of the MVSNet family's fusion step).
+ *   depth   [N,H,W] fp32, dense.  A pixel is VALID iff it is finite and > 0
+ *   K       [N,3,3] fp32; only fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2] are read
+ *   pose    [N,4,4] fp32, camera-to-world, rigid (only the top three rows are read)
+ *   sources [N,S] int32 device table, 0 <= S <= 16: slot j of frame r names a source frame s = sources[r][j] of the same batch.  A slot with
+ *           s < 0, s >= N or s == r is SKIPPED, on the device (no host read).  A frame named twice counts twice.  May be NULL when S == 0
+ *   pixel_threshold, relative_threshold   fp32 (usual values 1.0 and 0.01); min_views >= 0; average 0 / 1
+ *
+ * Step A, dvmvs_consistency_matrices: one thread per (r, j), float64 from the float32 inputs, no FMA contraction, each result rounded once
+ * to fp32.  With pose = [R|t] and a -> b meaning "from frame a's pixels to frame b's":
+ *   Rab[i][j] = (Rb[0][i] Ra[0][j] + Rb[1][i] Ra[1][j]) + Rb[2][i] Ra[2][j]                       (inv_rigid(pose_b) pose_a, rotation)
+ *   ti[i]     = -((Rb[0][i] tb[0] + Rb[1][i] tb[1]) + Rb[2][i] tb[2])                              (inv_rigid = (R^T, -R^T t))
+ *   tab[i]    = ((Rb[0][i] ta[0] + Rb[1][i] ta[1]) + Rb[2][i] ta[2]) + ti[i]
+ *   M = K_b Rab:  M[0][j] = fx_b Rab[0][j] + cx_b Rab[2][j],  M[1][j] = fy_b Rab[1][j] + cy_b Rab[2][j],  M[2][j] = Rab[2][j]
+ *   A = M K_a^-1: A[i][0] = M[i][0] (1 / fx_a),  A[i][1] = M[i][1] (1 / fy_a),
+ *                 A[i][2] = (M[i][0] (-(cx_a / fx_a)) + M[i][1] (-(cy_a / fy_a))) + M[i][2]
+ *   b = K_b tab:  b[0] = fx_b tab[0] + cx_b tab[2],  b[1] = fy_b tab[1] + cy_b tab[2],  b[2] = tab[2]
+ *   matrices [N,S,2,12] fp32 out: [r][j][0] = (A row-major, b) for a = r, b = s;  [r][j][1] = (A', b') for a = s, b = r.  A skipped slot is
+ *   written as 24 zeros.  S == 0 writes nothing.
+ *
+ * Step B, dvmvs_depth_consistency_fwd: one launch for all N frames; fp32 throughout, every operation rounded (no FMA contraction), divisions
+ * correctly rounded, in exactly this order for pixel (u, v) of frame r with valid d and each non-skipped slot j (u, v as fp32):
+ *   1. p[i] = d * ((A[i][0] u + A[i][1] v) + A[i][2]) + b[i];  require p.z > 0;  us = p.x / p.z, vs = p.y / p.z;
+ *      require 0 <= us <= W - 1 and 0 <= vs <= H - 1
+ *   2. x0 = min(floor(us), W - 2), y0 = min(floor(vs), H - 2), wx = us - x0, wy = vs - y0;  the four taps t00 = depth[s][y0][x0],
+ *      t01 = [y0][x0 + 1], t10 = [y0 + 1][x0], t11 = [y0 + 1][x0 + 1] must all be valid;
+ *      top = t00 + wx (t01 - t00), bot = t10 + wx (t11 - t10), ds = top + wy (bot - top)
+ *   3. q[i] = ds * ((A'[i][0] us + A'[i][1] vs) + A'[i][2]) + b'[i];  require q.z > 0;  du = q.x / q.z - u, dv = q.y / q.z - v
+ *   4. the slot is CONSISTENT iff du du + dv dv < pixel_threshold^2 (squared once, in fp32; no square root anywhere) and
+ *      |q.z - d| / d < relative_threshold
+ *   5. count = number of consistent slots;  fused = (d + sum of q.z over the consistent slots, in slot order) / fp32(count + 1)
+ *   6. out_depth [N,H,W] fp32 = count >= min_views ? (average ? fused : d) : 0;  0 for an invalid d
+ *      count     [N,H,W] uint8 or NULL: the count; 0 for an invalid d
+ *      points    [N,H,W,3] fp32 or NULL: world position of the pixel at z = out_depth: xn = (u - cx) / fx, yn = (v - cy) / fy,
+ *                X = z xn, Y = z yn, Z = z, world[i] = ((P[i][0] X + P[i][1] Y) + P[i][2] Z) + P[i][3] with K_r, P = pose_r;
+ *                zeros where out_depth is 0
+ *   A map with H < 2 or W < 2 has no tap cell: every slot is inconsistent.
+ * matrices: step A's output for the same K, pose and sources.  out_depth must not overlap depth.
+ * Every output element has one writer and no value crosses threads: the results depend on nothing but the inputs -- a frame filtered alone
+ * with its sources gives the bits it has inside a larger batch with re-indexed sources, and two calls give the same bits.
+ * Both return DVMVS_EINVAL for a null K / pose / matrices (with S > 0: sources; pixels: depth / out_depth), N < 1, S outside [0,16],
+ * H or W < 1, a NaN threshold, min_views < 0, average not 0 / 1, a pointer to 32-bit words that is not 4-byte aligned; DVMVS_EUNSUPPORTED
+ * for N > 65535 or 3 H W >= 2^31 (offsets inside a frame are 32-bit).  Nothing is enqueued in either case.
+ */
+int dvmvs_consistency_matrices(const float* K, const float* pose, const int* sources, float* matrices, int N, int S,
+                               dvmvs_stream_t stream);
+int dvmvs_depth_consistency_fwd(const float* depth, const float* K, const float* pose, const int* sources, const float* matrices,
+                                float* out_depth, unsigned char* count, float* points, int N, int S, int H, int W,
+                                float pixel_threshold, float relative_threshold, int min_views, int average, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
