@@ -121,8 +121,8 @@ def test_gate_backward_upstream_gradient_forms(ops, dev, H, W):
     # whichever form autograd hands over for the unused output, None and zeros give the same gradients, bit for bit
     ctx = types.SimpleNamespace(saved_tensors=(cc.to(dev), c.to(dev)))
     gh, gc = wh.to(dev), wc.to(dev)
-    for none_form, zero_form in ((ops._lstm_gates_backward(ctx, gh, None), ops._lstm_gates_backward(ctx, gh, torch.zeros_like(gc))),
-                                 (ops._lstm_gates_backward(ctx, None, gc), ops._lstm_gates_backward(ctx, torch.zeros_like(gh), gc))):
+    for none_form, zero_form in ((ops.frame._lstm_gates_backward(ctx, gh, None), ops.frame._lstm_gates_backward(ctx, gh, torch.zeros_like(gc))),
+                                 (ops.frame._lstm_gates_backward(ctx, None, gc), ops.frame._lstm_gates_backward(ctx, torch.zeros_like(gh), gc))):
         assert all(torch.equal(x, y) for x, y in zip(none_form, zero_form))
 
 
@@ -182,7 +182,7 @@ def test_gate_planes_above_1024_elements_are_refused(ops, dev):
     with pytest.raises(RuntimeError, match="dvmvs_lstm_gates_fwd"):
         ops.lstm_gates(cc, c)
     with pytest.raises(RuntimeError, match="dvmvs_lstm_gates_bwd"):
-        ops._lstm_gates_backward(types.SimpleNamespace(saved_tensors=(cc, c)), torch.ones_like(c), torch.ones_like(c))
+        ops.frame._lstm_gates_backward(types.SimpleNamespace(saved_tensors=(cc, c)), torch.ones_like(c), torch.ones_like(c))
     c_state, h_state = c.clone(), torch.zeros_like(c)
     with pytest.raises(RuntimeError, match="dvmvs_lstm_gates_fwd"):
         ops.lstm_gates_into(cc, c_state, h_state)

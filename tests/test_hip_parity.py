@@ -232,12 +232,12 @@ def test_cost_volume_two_pass_is_bit_reproducible(ops, dev):
                 one = [hipcall.cost_volume(ops, f1, f2s, p1, p2s, K, 0.25, 20.0, 64, True, variant).clone() for _ in range(2)]
                 assert torch.equal(one[0], one[1]), (r, layout, variant)
                 assert maxerr(one[0], runs[0]) < (2e-6 if variant == 6 else 1e-6), (r, layout, variant)   # (6: another order of the channel sum)
-            saved = ops.COST_VOLUME_TWO_PASS
-            ops.COST_VOLUME_TWO_PASS = False
+            saved = ops.sweep.COST_VOLUME_TWO_PASS
+            ops.sweep.COST_VOLUME_TWO_PASS = False
             try:
                 single = hipcall.cost_volume(ops, f1, f2s, p1, p2s, K, 0.25, 20.0, 64, True, 2)
             finally:
-                ops.COST_VOLUME_TWO_PASS = saved
+                ops.sweep.COST_VOLUME_TWO_PASS = saved
             assert maxerr(single, runs[0]) < 1e-6, (r, layout)
             generic = hipcall.cost_volume(ops, f1, [t.contiguous() for t in f2s], p1, p2s, K, 0.25, 20.0, 64, True, 1)
             assert maxerr(generic, runs[0]) < 3e-5, (r, layout)   # different (reference-order) arithmetic, same volume
