@@ -176,4 +176,32 @@ __device__ inline int block_exclusive_scan(int v, int* lds, int& total) {
   return prefix + incl - v;
 }
 
+// The same for 64-bit values (sums wrap like the 32-bit ones): `lds` holds kBlock / 64 long longs.
+__device__ inline long long wave_inclusive_scan(long long x) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const long long y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  return x;
+}
+
+template <int kBlock = 256>
+__device__ inline long long block_exclusive_scan(long long v, long long* lds, long long& total) {
+  const long long incl = wave_inclusive_scan(v);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 63) lds[wave] = incl;
+  __syncthreads();
+  long long prefix = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < kBlock / 64; ++w) {
+    const long long t = lds[w];
+    if (w < wave) prefix += t;
+    total += t;
+  }
+  return prefix + incl - v;
+}
+
 }  // namespace dvmvs

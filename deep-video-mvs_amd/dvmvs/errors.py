@@ -75,30 +75,197 @@ def reconstruction_metrics_from_distances(dist_pred, dist_gt, threshold=0.05):
     return np.array([acc, comp, (acc + comp) / 2.0, precision, recall, fscore], dtype=np.float32), counts
 
 
-def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05):
+# ----------------------------------------------------------------------------------------------------------------------
+# point sets for the 3-D metrics: area-weighted samples of a triangle mesh, one point per occupied voxel
+# ----------------------------------------------------------------------------------------------------------------------
+SAMPLE_MAX_POINTS = 1 << 28
+_AREA_SCALE = 4294967296.0          # areas are counted in units of 2^-32 square metres
+_AREA_LIMIT = 1 << 63               # the total must stay below this (2^31 square metres)
+VOXEL_MAX_CELLS = 1 << 21           # cells per axis of voxel_down_sample
+
+
+def _lowbias32(x):
+    x = np.uint32(x)
+    with np.errstate(over="ignore"):
+        x ^= x >> np.uint32(16)
+        x *= np.uint32(0x7feb352d)
+        x ^= x >> np.uint32(15)
+        x *= np.uint32(0x846ca68b)
+        x ^= x >> np.uint32(16)
+    return x
+
+
+def quantised_face_areas(verts, faces):
+    """``A_f = int64(rint(|e1 x e2| / 2 * 2^32))`` of every face, in float64 with every operation rounded: e1 = b - a, e2 = c - a,
+    cx = e1.y e2.z - e1.z e2.y (cy, cz by the same pattern), n2 = (cx cx + cy cy) + cz cz.  A face with an index outside [0, V) has
+    area 0.  Raises ``ValueError`` when an area is not finite or does not fit."""
+    verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    valid = np.all((faces >= 0) & (faces < len(verts)), axis=1)
+    safe = np.where(valid[:, None], faces, 0) if len(verts) else np.zeros_like(faces)
+    if len(verts) == 0:
+        return np.zeros(len(faces), dtype=np.int64), valid
+    a, b, c = (verts[safe[:, j]].astype(np.float64) for j in range(3))
+    e1, e2 = b - a, c - a
+    with np.errstate(all="ignore"):
+        cx = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+        cy = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+        cz = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        n2 = (cx * cx + cy * cy) + cz * cz
+        area = np.sqrt(n2) * 0.5 * _AREA_SCALE
+    area = np.where(valid, area, 0.0)
+    if not np.all(area < 2.0 ** 63):       # NaN, infinite or beyond int64
+        raise ValueError("sample_surface: a face's area is not finite or the mesh is larger than 2^31 square metres")
+    return np.rint(area).astype(np.int64), valid
+
+
+def sample_surface(verts, faces, density, seed=0, return_face=False):
+    """Points on the triangle mesh ``verts`` float32 [V,3], ``faces`` int32 [F,3], about ``density`` per square metre, spread over the
+    faces in proportion to their areas: float32 [N,3], with ``return_face`` also int32 [N], the face of each point.  The host definition
+    that ``dvmvs.hip.ops.surface_sample`` reproduces bit for bit (include/dvmvs_hip.h restates it):
+      1. ``quantised_face_areas`` and their inclusive sum ``cum`` (exact in int64; the total must stay below 2^63);
+      2. D = max(int64(rint(2^32 / density)), 1); sample k sits at t_k = k D + (D >> 1) of the summed area and belongs to the face f with
+         cum[f-1] <= t_k < cum[f]; N = the number of t_k below cum[F-1].  A face gets A_f / D samples to within one, a face without area
+         (or with an index outside [0, V)) none;
+      3. inside the face, the R2 sequence in integers: r0 = lowbias32(seed), r1 = lowbias32(seed + 1), h1 = uint32(k) 0xC13FA9A9 + r0,
+         h2 = uint32(k) 0x91E10DA5 + r1, u = float32(h1 >> 8) 2^-24, v likewise; if u + v > 1 (float32): u = 1 - u, v = 1 - v;
+         p = (a + u (b - a)) + v (c - a) per component in float32, every operation rounded.
+    Point k depends on k and the mesh alone.  Raises ``ValueError`` for a density that is not positive and for N above 2^28."""
+    verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    density = float(density)
+    if not density > 0.0 or density == np.inf:
+        raise ValueError(f"sample_surface: density must be positive and finite, got {density}")
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError(f"sample_surface: seed must fit 32 unsigned bits, got {seed}")
+    areas, _ = quantised_face_areas(verts, faces)
+    total = (int((areas >> 32).sum()) << 32) + int((areas & 0xffffffff).sum())
+    if total >= _AREA_LIMIT:
+        raise ValueError("sample_surface: the mesh is larger than 2^31 square metres")
+    cum = np.cumsum(areas, dtype=np.int64)
+    D = max(int(np.rint(_AREA_SCALE / density)), 1)
+    half = D >> 1
+    N = 0 if total <= half else (total - half - 1) // D + 1
+    if N > SAMPLE_MAX_POINTS:
+        raise ValueError(f"sample_surface: {N} samples are more than 2^28; lower the density")
+    k = np.arange(N, dtype=np.int64)
+    face = np.searchsorted(cum, k * D + half, side="right").astype(np.int32)
+    with np.errstate(over="ignore"):
+        k32 = k.astype(np.uint32)
+        h1 = k32 * np.uint32(0xC13FA9A9) + _lowbias32(seed)
+        h2 = k32 * np.uint32(0x91E10DA5) + _lowbias32((seed + 1) & 0xffffffff)
+    scale, one = np.float32(2.0 ** -24), np.float32(1.0)
+    u = (h1 >> np.uint32(8)).astype(np.float32) * scale
+    v = (h2 >> np.uint32(8)).astype(np.float32) * scale
+    fold = u + v > one
+    u, v = np.where(fold, one - u, u), np.where(fold, one - v, v)
+    tri = faces[face]
+    a, b, c = verts[tri[:, 0]], verts[tri[:, 1]], verts[tri[:, 2]]
+    points = (a + u[:, None] * (b - a)) + v[:, None] * (c - a)
+    return (points, face) if return_face else points
+
+
+def voxel_keys(points, voxel):
+    """The voxel of every point of ``voxel_down_sample``: ``(keys int64 [N], cells int32 [N,3], mn float32 [3])``."""
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    voxel = float(voxel)
+    if len(points) == 0:
+        raise ValueError("voxel_down_sample: the cloud is empty")
+    if not voxel > 0.0 or voxel == np.inf:
+        raise ValueError(f"voxel_down_sample: voxel must be positive and finite, got {voxel}")
+    mn = points.min(axis=0)
+    inv = np.float32(1.0 / voxel)
+    with np.errstate(all="ignore"):
+        scaled = (points - mn) * inv
+    if not np.all(scaled < np.float32(VOXEL_MAX_CELLS)):
+        raise ValueError("voxel_down_sample: the cloud spans 2^21 voxels or more on an axis (or holds a coordinate that is not finite)")
+    cells = scaled.astype(np.int32)
+    c = cells.astype(np.int64)
+    return (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2], cells, mn
+
+
+def voxel_down_sample(points, voxel, return_counts=False):
+    """One point per occupied voxel of edge ``voxel``, the mean of the voxel's points: float32 [M,3], with ``return_counts`` also int32
+    [M], the points per voxel.  ``points`` float32 [N,3], finite, N >= 1.  The host definition that ``dvmvs.hip.ops.voxel_downsample``
+    reproduces bit for bit: mn = the per-axis minimum; inv = float32(1 / float64(voxel)); cell c_a = int32((x_a - mn_a) inv), a float32
+    subtraction and a float32 multiplication, then truncation; key = (c_x << 42) | (c_y << 21) | c_z; the voxels come in ascending key
+    order; a voxel's point is float32(sum of float64(x_i) / n) per axis, the sum in float64 over the voxel's points in ascending index i
+    starting from 0.0, the division in float64.  Raises ``ValueError`` when a cell index reaches 2^21."""
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    keys, _, _ = voxel_keys(points, voxel)
+    order = np.argsort(keys, kind="stable")
+    sorted_keys = keys[order]
+    starts = np.flatnonzero(np.concatenate([[True], sorted_keys[1:] != sorted_keys[:-1]]))
+    counts = np.diff(np.concatenate([starts, [len(points)]]))
+    sorted_points = points[order].astype(np.float64)
+    # the r-th point of every voxel that has one is added in step r: each voxel's sum runs in ascending index, vectorised over the voxels
+    by_count = np.argsort(-counts, kind="stable")
+    descending = -counts[by_count]
+    sums = np.zeros((len(starts), 3), dtype=np.float64)
+    for r in range(int(counts.max())):
+        active = by_count[:np.searchsorted(descending, -r, side="left")]
+        sums[active] += sorted_points[starts[active] + r]
+    out = (sums / counts[:, None].astype(np.float64)).astype(np.float32)
+    return (out, counts.astype(np.int32)) if return_counts else out
+
+
+def prepare_points(verts, faces=None, sample_density=None, voxel=None, seed=0):
+    """The point set the 3-D metrics take from a surface: ``verts`` themselves, or, with ``faces`` and ``sample_density``,
+    ``sample_surface(verts, faces, sample_density, seed)``; then, with ``voxel``, ``voxel_down_sample`` of that.  A side without faces (a
+    point cloud) is not sampled, only down-sampled.  float32 [N,3]."""
+    points = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+    if sample_density is not None and faces is not None:
+        points = sample_surface(points, faces, sample_density, seed)
+    if voxel is not None and len(points):
+        points = voxel_down_sample(points, voxel)
+    return points
+
+
+def prepare_points_device(verts, faces=None, sample_density=None, voxel=None, seed=0):
+    """``prepare_points`` for device tensors (``dvmvs.hip.ops.surface_sample`` / ``voxel_downsample``): the same bits, on the GPU."""
+    from dvmvs.hip import ops
+    points = verts
+    if sample_density is not None and faces is not None:
+        points = ops.surface_sample(points, faces, sample_density, seed)
+    if voxel is not None and points.shape[0]:
+        points = ops.voxel_downsample(points, voxel)
+    return points
+
+
+def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05, pred_faces=None, gt_faces=None, sample_density=None, voxel=None):
     """The 3-D reconstruction metrics of the Atlas / NeuralRecon / SimpleRecon evaluations between a predicted point set [N,3] and a
     ground-truth point set [M,3], float32 [6] in the order of ``RECONSTRUCTION_METRICS``:
       acc = mean distance from a predicted point to its nearest ground-truth point; comp = the same from ground truth to prediction;
       chamfer = (acc + comp) / 2; precision = share of predicted points closer than ``threshold`` (strictly) to the ground truth;
       recall = share of ground-truth points closer than ``threshold`` to the prediction; fscore = 2PR / (P + R), 0 when P + R = 0.
     The host definition: numpy, exact nearest neighbours by chunked brute force (``nearest_distances``), for a few tens of thousands of
-    points.  In this package the point sets are MESH VERTICES (``TSDFVolume.score_against``): one per crossed grid edge, so their spacing
-    is about one voxel and the distances are point-to-point, not point-to-surface; sampling the faces or voxel down-sampling, as some
-    evaluations do, is not done here.  Raises ``ValueError`` when either set is empty."""
-    pred_points = np.asarray(pred_points, dtype=np.float32).reshape(-1, 3)
-    gt_points = np.asarray(gt_points, dtype=np.float32).reshape(-1, 3)
+    points.  The distances are point-to-point.  With every keyword at None the point sets are taken as they come; in this package they
+    are then MESH VERTICES (``TSDFVolume.score_against``), one per crossed grid edge, which compares two marching-cubes meshes of one
+    voxel size soundly and nothing else.  The usual protocol is the keywords: ``pred_faces`` / ``gt_faces`` (int32 [F,3]) with
+    ``sample_density`` (points per square metre) replace a side's vertices by ``sample_surface`` of its mesh, and ``voxel`` (metres)
+    replaces each side by its ``voxel_down_sample``, so that both clouds have a common resolution (``prepare_points``).  Raises
+    ``ValueError`` when either set is, or becomes, empty."""
+    pred_points = prepare_points(pred_points, pred_faces, sample_density, voxel)
+    gt_points = prepare_points(gt_points, gt_faces, sample_density, voxel)
     if len(pred_points) == 0 or len(gt_points) == 0:
         raise ValueError("compute_reconstruction_errors: both point clouds must hold at least one point")
     return reconstruction_metrics_from_distances(nearest_distances(pred_points, gt_points), nearest_distances(gt_points, pred_points),
                                                  threshold)[0]
 
 
-def compute_reconstruction_errors_device(pred_points, gt_points, threshold=0.05, counts=None):
+def compute_reconstruction_errors_device(pred_points, gt_points, threshold=0.05, counts=None, pred_faces=None, gt_faces=None,
+                                         sample_density=None, voxel=None):
     """``compute_reconstruction_errors`` for point sets that live on the GPU (float32 [N,3] and [M,3] device tensors, both non-empty):
     a float32 device tensor [6].  Two grid builds, two nearest-point queries (csrc/nearest_points.hip: the distances are the host
-    function's, bit for bit) and one reduction in float64, all on the current stream; nothing is copied to the host.  ``counts``: an
-    int64 [2] device tensor that receives the numbers of distances below the threshold."""
+    function's, bit for bit) and one reduction in float64, all on the current stream; with every keyword at None nothing is copied to
+    the host.  ``counts``: an int64 [2] device tensor that receives the numbers of distances below the threshold.  ``pred_faces`` /
+    ``gt_faces`` (int32 [F,3] device tensors), ``sample_density`` and ``voxel`` as in the host function, on the device
+    (csrc/surface_sample.hip: the host definitions' bits; each sampling and each down-sampling reads its output's size once)."""
     from dvmvs.hip import ops      # (imported here: this module stays importable, and the host functions usable, without a GPU)
+    if pred_faces is not None or gt_faces is not None or sample_density is not None or voxel is not None:
+        pred_points = prepare_points_device(pred_points, pred_faces, sample_density, voxel)
+        gt_points = prepare_points_device(gt_points, gt_faces, sample_density, voxel)
     for label, t in (("pred_points", pred_points), ("gt_points", gt_points)):
         if hasattr(t, "shape") and len(t.shape) == 2 and t.shape[0] == 0:
             raise ValueError(f"compute_reconstruction_errors_device: {label} is empty")

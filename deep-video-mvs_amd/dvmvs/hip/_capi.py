@@ -129,6 +129,14 @@ SIGNATURES = {
     "dvmvs_consistency_matrices": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_stream]),
     "dvmvs_depth_consistency_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int,
                                              ctypes.c_float, ctypes.c_float, _c_int, _c_int, _c_stream]),
+    "dvmvs_surface_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "dvmvs_surface_sample_count": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_dbl, _c_fp, ctypes.c_size_t, _c_fp, _c_stream]),
+    "dvmvs_surface_sample_emit": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_dbl, ctypes.c_uint, _c_fp, ctypes.c_longlong,
+                                           _c_fp, _c_fp, _c_stream]),
+    "dvmvs_voxel_downsample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong]),
+    "dvmvs_voxel_keys": (_c_int, [_c_fp, ctypes.c_longlong, ctypes.c_float, _c_fp, ctypes.c_size_t, _c_fp, _c_stream]),
+    "dvmvs_voxel_downsample_count": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, ctypes.c_size_t, _c_fp, _c_stream]),
+    "dvmvs_voxel_downsample_emit": (_c_int, [ctypes.c_longlong, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -145,6 +153,10 @@ ADDED_WITHIN_ABI_NEAREST = ("dvmvs_nearest_workspace_bytes", "dvmvs_nearest_quer
                             "dvmvs_nearest_distance_fwd", "dvmvs_distance_metrics_fwd")
 # ... and the sixth (filtering depth maps by multi-view geometric consistency)
 ADDED_WITHIN_ABI_CONSISTENCY = ("dvmvs_consistency_matrices", "dvmvs_depth_consistency_fwd")
+# ... and the seventh (point sets for the 3-D metrics: surface sampling and voxel down-sampling)
+ADDED_WITHIN_ABI_SURFACE_SAMPLE = ("dvmvs_surface_sample_workspace_bytes", "dvmvs_surface_sample_count", "dvmvs_surface_sample_emit",
+                                   "dvmvs_voxel_downsample_workspace_bytes", "dvmvs_voxel_keys", "dvmvs_voxel_downsample_count",
+                                   "dvmvs_voxel_downsample_emit")
 
 _lib = None
 _lock = threading.Lock()
@@ -164,7 +176,7 @@ def lib():
                 f"(or __graft_entry__.build()). The plane-sweep ops have no CPU / eager fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
-                 + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY)
+                 + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

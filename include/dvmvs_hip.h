@@ -55,7 +55,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_nearest_* and dvmvs_distance_metrics_fwd (exact nearest-point distances between point clouds and the 3-D
  * reconstruction metrics); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_consistency_matrices and dvmvs_depth_consistency_fwd (filtering depth maps by multi-view geometric
- * consistency); no earlier signature changed, the number stays 11 by the same rule. */
+ * consistency); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_surface_sample_* and dvmvs_voxel_* (point sets for the 3-D metrics: area-weighted samples of a triangle
+ * mesh, one point per occupied voxel of a cloud); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -773,6 +775,55 @@ int dvmvs_consistency_matrices(const float* K, const float* pose, const int* sou
 int dvmvs_depth_consistency_fwd(const float* depth, const float* K, const float* pose, const int* sources, const float* matrices,
                                 float* out_depth, unsigned char* count, float* points, int N, int S, int H, int W,
                                 float pixel_threshold, float relative_threshold, int min_views, int average, dvmvs_stream_t stream);
+
+/*
+ * Point sets for the 3-D reconstruction metrics (ABI 11, later addition): samples of a triangle mesh in proportion to its faces' areas, and
+ * the voxel down-sampling of a point cloud.  The reference project has nothing for this: the definitions are this project's own (the
+ * protocol is that of the Atlas / NeuralRecon / TransformerFusion / SimpleRecon evaluations); dvmvs/errors.py restates them in numpy
+ * (sample_surface, voxel_down_sample) and the device reproduces those bit for bit.  No float atomics; no FMA contraction; every entry
+ * runs on `stream`; the host reads `counts` once between a *_count and its *_emit, to size the output.
+ *
+ * Surface sampling.  verts [V,3] fp32, faces [F,3] int32, density > 0 (points per square metre), seed (32 bits).
+ *   1. A_f = int64(rint(sqrt(n2) * 0.5 * 2^32)) with, in fp64 from the fp32 corners a, b, c of face f: e1 = b - a, e2 = c - a,
+ *      cx = e1.y e2.z - e1.z e2.y, cy = e1.z e2.x - e1.x e2.z, cz = e1.x e2.y - e1.y e2.x, n2 = (cx cx + cy cy) + cz cz; every operation
+ *      rounded.  A face with an index outside [0, V) has A_f = 0 and no vertex is read for it.  cum_f = A_0 + ... + A_f, exact.  An A_f that
+ *      is not below 2^63 (or not a number), or a total of 2^63 and more (2^31 square metres), is an error: counts[1] = 1, N = 0.
+ *   2. D = max(int64(rint(2^32 / density)), 1); t_k = k D + (D >> 1); N = 0 if cum_{F-1} <= D >> 1, else (cum_{F-1} - (D >> 1) - 1) / D + 1;
+ *      sample k belongs to the face f with cum_{f-1} <= t_k < cum_f (found by binary search, one thread per sample).
+ *   3. lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32).  r0 = lowbias32(seed),
+ *      r1 = lowbias32(seed + 1); h1 = uint32(k) 0xC13FA9A9 + r0, h2 = uint32(k) 0x91E10DA5 + r1; u = fp32(h1 >> 8) 2^-24, v likewise from h2;
+ *      if u + v > 1 (fp32): u = 1 - u, v = 1 - v;  p = (a + u (b - a)) + v (c - a) per component in fp32, every operation rounded.
+ *   workspace   dvmvs_surface_sample_workspace_bytes(F) bytes on the device, 8-byte aligned: written by _count (it holds cum), read by _emit
+ *   counts      long long [3] on the device, out of _count: N, the status (0, or 1 = the error of step 1) and cum_{F-1}
+ *   points [N,3] fp32 out, in ascending k;  face [N] int32 out or NULL: the face of each sample
+ * dvmvs_surface_sample_emit takes the N that _count of the same mesh and density produced; N == 0 enqueues nothing and returns 0.
+ *
+ * Voxel down-sampling.  points [N,3] fp32, FINITE, N >= 1; inv_voxel = fp32(1 / fp64(voxel)), computed by the host.
+ *   mn = the per-axis minimum of the cloud (exact); cell c_a = int32((x_a - mn_a) inv_voxel): one fp32 subtraction, one fp32 product, each
+ *   rounded, then truncation; a c_a of 2^21 or more (or a coordinate that is not finite) is an error: status 1, and that cell counts as 0.
+ *   key = (c_x << 42) | (c_y << 21) | c_z.  dvmvs_voxel_keys writes key [N] int64 (and mn into the workspace).  The CALLER sorts the keys
+ *   stably with their indices 0 .. N-1 (both int64).  dvmvs_voxel_downsample_count takes the sorted arrays: counts long long [2] on the
+ *   device receives M, the number of distinct keys, and the status of dvmvs_voxel_keys for the same workspace.  dvmvs_voxel_downsample_emit
+ *   writes out [M,3] fp32, the voxels in ascending key order: out[m][a] = fp32((0.0 + x_i0 + x_i1 + ...) / n), the sum in fp64 over the
+ *   voxel's points in ascending index, the division in fp64, one rounding;  count [M] int32 out or NULL: n.  One thread per voxel walks a
+ *   copy of the points in sorted order: linear in N.
+ *   workspace   dvmvs_voxel_downsample_workspace_bytes(N) bytes on the device, 16-byte aligned, shared by the three calls of one cloud
+ * The two *_workspace_bytes: host only, no HIP call; 0 for F (N) <= 0 or above 2^28; non-decreasing.
+ * Every entry returns DVMVS_EINVAL for a null or misaligned pointer (verts may be null when V == 0), F < 1, N < 1 (surface emit: N < 0),
+ * V < 0, a density or inv_voxel that is not positive and finite, M outside [1, N], a workspace that is too small, an N for which t_k does
+ * not fit 63 bits; DVMVS_EUNSUPPORTED for F, N above 2^28 or V above 2^31 - 1.  Nothing is enqueued in either case.
+ */
+size_t dvmvs_surface_sample_workspace_bytes(long long F);
+int dvmvs_surface_sample_count(const float* verts, long long V, const int* faces, long long F, double density, void* workspace,
+                               size_t workspace_bytes, long long* counts, dvmvs_stream_t stream);
+int dvmvs_surface_sample_emit(const float* verts, long long V, const int* faces, long long F, double density, unsigned int seed,
+                              const void* workspace, long long N, float* points, int* face, dvmvs_stream_t stream);
+size_t dvmvs_voxel_downsample_workspace_bytes(long long N);
+int dvmvs_voxel_keys(const float* points, long long N, float inv_voxel, void* workspace, size_t workspace_bytes, long long* keys,
+                     dvmvs_stream_t stream);
+int dvmvs_voxel_downsample_count(const float* points, long long N, const long long* sorted_keys, const long long* sorted_index,
+                                 void* workspace, size_t workspace_bytes, long long* counts, dvmvs_stream_t stream);
+int dvmvs_voxel_downsample_emit(long long N, long long M, const void* workspace, float* out, int* count, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
