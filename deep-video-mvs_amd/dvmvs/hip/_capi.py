@@ -137,6 +137,12 @@ SIGNATURES = {
     "dvmvs_voxel_keys": (_c_int, [_c_fp, ctypes.c_longlong, ctypes.c_float, _c_fp, ctypes.c_size_t, _c_fp, _c_stream]),
     "dvmvs_voxel_downsample_count": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, ctypes.c_size_t, _c_fp, _c_stream]),
     "dvmvs_voxel_downsample_emit": (_c_int, [ctypes.c_longlong, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_mesh_raster_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong] * 4),
+    "dvmvs_mesh_raster_cameras": (_c_int, [_c_fp, _c_fp, _c_int, _c_stream]),
+    "dvmvs_mesh_raster_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float,
+                                       ctypes.c_float, _c_int, _c_int, _c_fp, ctypes.c_size_t, _c_fp, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_mesh_visibility_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_float, _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -157,6 +163,9 @@ ADDED_WITHIN_ABI_CONSISTENCY = ("dvmvs_consistency_matrices", "dvmvs_depth_consi
 ADDED_WITHIN_ABI_SURFACE_SAMPLE = ("dvmvs_surface_sample_workspace_bytes", "dvmvs_surface_sample_count", "dvmvs_surface_sample_emit",
                                    "dvmvs_voxel_downsample_workspace_bytes", "dvmvs_voxel_keys", "dvmvs_voxel_downsample_count",
                                    "dvmvs_voxel_downsample_emit")
+# ... and the eighth (rasterising a triangle mesh to depth maps; vertex visibility)
+ADDED_WITHIN_ABI_MESH_RASTER = ("dvmvs_mesh_raster_workspace_bytes", "dvmvs_mesh_raster_cameras", "dvmvs_mesh_raster_fwd",
+                                "dvmvs_mesh_visibility_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -176,7 +185,7 @@ def lib():
                 f"(or __graft_entry__.build()). The plane-sweep ops have no CPU / eager fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
-                 + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE)
+                 + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

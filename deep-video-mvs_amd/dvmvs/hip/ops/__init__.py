@@ -46,7 +46,8 @@ __all__ = ["cost_volume", "sweep_matrices", "hidden_warp", "relative_pose", "lst
 # The listing of this package (``dir``, ``__all__``) is recorded in tests/golden/ops_surface.json and held fixed.  Ops added after that
 # record are defined and listed in their family module and are served from here by name, so ``ops.surface_sample(...)`` and
 # ``from dvmvs.hip.ops import voxel_downsample`` work like every other op.
-_LATER_OPS = {"surface_sample": reconstruction, "voxel_downsample": reconstruction}
+_LATER_OPS = {"surface_sample": reconstruction, "voxel_downsample": reconstruction, "mesh_raster": reconstruction,
+              "mesh_raster_workspace": reconstruction, "mesh_visibility": reconstruction}
 
 
 def __getattr__(name):

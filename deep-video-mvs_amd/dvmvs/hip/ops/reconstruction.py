@@ -488,6 +488,131 @@ def voxel_downsample(points: Tensor, voxel: float, return_counts: bool = False):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# rasterising a triangle mesh to depth maps, and the vertices that depth maps show
+# ----------------------------------------------------------------------------------------------------------------------
+# a clipped triangle whose box of candidate pixels holds more pixels than this goes to the device work list (one pixel per lane) instead
+# of being rasterised by the thread of its (view, face): DVMVS_MESH_RASTER_LARGE_BOX in include/dvmvs_hip.h.  It cannot change a result.
+MESH_RASTER_LARGE_BOX = 64
+MESH_RASTER_TILE = 16             # the edge of a list entry's tile of the image grid (kMrTile in csrc/mesh_raster.hip)
+
+
+def mesh_raster_cameras(cam_poses: Tensor) -> Tensor:
+    """World-to-camera matrices [N,3,4] float32 of camera-to-world poses float32 [N,4,4] on the GPU, as ``mesh_raster`` and
+    ``mesh_visibility`` use them: the inverse in float64 on the device, rounded once (``dvmvs_mesh_raster_cameras``: one tiny launch;
+    the same as a chain of small torch operations took 0.07 ms, more than the rest of a
+    ``mesh_raster`` call on a 190 000-face mesh).  No host read, no synchronisation."""
+    check_tensors("mesh_raster_cameras", cam_poses, label="cam_poses", shape=(None, 4, 4))
+    N = int(cam_poses.shape[0])
+    w2c = torch.empty((N, 3, 4), dtype=torch.float32, device=cam_poses.device)
+    if N > 0:
+        launch("dvmvs_mesh_raster_cameras", cam_poses.device, ptr(cam_poses.contiguous()), ptr(w2c), N)
+    return w2c
+
+
+def _mesh_cameras(name, cam_intr, cam_poses, dev):
+    check_tensors(name, cam_intr, label="cam_intr", shape=(None, 3, 3), device=dev)
+    check_tensors(name, cam_poses, label="cam_poses", shape=(None, 4, 4), device=dev)
+    N = int(cam_poses.shape[0])
+    if N < 1 or N > 65535 or cam_intr.shape[0] != N:
+        raise ValueError(f"dvmvs::{name}: expected 1 .. 65535 poses and as many intrinsics, got {tuple(cam_poses.shape)} and {tuple(cam_intr.shape)}")
+    return N, cam_intr.contiguous(), mesh_raster_cameras(cam_poses)
+
+
+def _mesh_near(name, near):
+    near = float(near)
+    if not 0.0 < near < float("inf"):
+        raise ValueError(f"dvmvs::{name}: near must be positive and finite, got {near}")
+    return near
+
+
+def mesh_raster_workspace_bytes(n_views, n_faces, height, width):
+    """Bytes of workspace ``mesh_raster`` needs for the shape (host arithmetic); raises ``ValueError`` for a shape the kernels refuse."""
+    nbytes = _capi.lib().dvmvs_mesh_raster_workspace_bytes(int(n_views), int(n_faces), int(height), int(width))
+    if nbytes == 0:
+        raise ValueError(f"dvmvs::mesh_raster: {n_views} views of {height}x{width} pixels of {n_faces} faces are outside what the kernels take "
+                         f"(1 .. 65535 views, 1 .. 2^28 faces, sides up to 16384, fewer than 2^31 pixels in all)")
+    return nbytes
+
+
+def mesh_raster_workspace(device, n_views, n_faces, height, width):
+    """Persistent workspace of ``mesh_raster`` per device: grown to the largest shape seen; every call writes what it reads first (the
+    z-buffer keys, the work list's length), so it needs no initialisation.  Calls that share it must be ordered (one stream per process)."""
+    return _workspace.grown("mesh_raster", device, mesh_raster_workspace_bytes(n_views, n_faces, height, width), torch.int64)
+
+
+def mesh_raster(verts: Tensor, faces: Tensor, cam_intr: Tensor, cam_poses: Tensor, height: int, width: int, near: float = 0.05,
+                far: float = float("inf"), cull_backfaces: bool = False, workspace: Optional[Tensor] = None, return_overflow: bool = False,
+                large_box: Optional[int] = None):
+    """Rasterises the triangle mesh ``verts`` float32 [V,3] (world space), ``faces`` int32 [F,3] from N views in one call
+    (csrc/mesh_raster.hip; definition in include/dvmvs_hip.h): ``cam_intr`` float32 [N,3,3], camera-to-world ``cam_poses`` float32 [N,4,4],
+    all on one GPU.  Returns ``(depth [N,height,width] float32, face [N,height,width] int32)``: the camera depth of the nearest face at
+    every pixel (0 where there is none between ``near`` and ``far``) and that face's index (-1); with ``return_overflow`` also int32 [N],
+    the clipped triangles per view that were left out because a corner projects beyond 2^21 pixels.  Pixels are sampled at their integer
+    coordinates, as ``tsdf_raycast`` does.  A face that crosses ``z = near`` is clipped; at equal depths the lowest face index wins; the
+    result does not depend on the order of the faces or on ``large_box`` (the tuning constant ``MESH_RASTER_LARGE_BOX``).  ``workspace``:
+    an int64 device tensor of at least ``mesh_raster_workspace_bytes(N, F, height, width)`` bytes, of any contents, instead of the
+    per-device one.  An empty mesh gives empty maps.  Runs on the current stream: no host read and no synchronisation."""
+    name = "mesh_raster"
+    check_tensors(name, verts, label="verts", shape=(None, 3))
+    dev = verts.device
+    check_tensors(name, faces, dtype=torch.int32, label="faces", shape=(None, 3), device=dev)
+    N, K, w2c = _mesh_cameras(name, cam_intr, cam_poses, dev)
+    height, width, near, far = int(height), int(width), _mesh_near(name, near), float(far)
+    if height < 1 or width < 1 or far != far:
+        raise ValueError(f"dvmvs::{name}: expected a positive image size and a far that is a number, got {height}x{width}, {far}")
+    large_box = MESH_RASTER_LARGE_BOX if large_box is None else int(large_box)
+    if large_box < 1:
+        raise ValueError(f"dvmvs::{name}: large_box must be at least 1, got {large_box}")
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    nbytes = mesh_raster_workspace_bytes(N, max(F, 1), height, width)
+    if workspace is not None:
+        check_tensors(name, workspace, dtype=torch.int64, label="workspace", shape=(None,), device=dev, contiguous=True)
+        if workspace.numel() * 8 < nbytes:
+            raise ValueError(f"dvmvs::{name}: workspace must have at least {nbytes} bytes, got {workspace.numel() * 8}")
+    if V == 0 or F == 0:
+        depth = torch.zeros((N, height, width), dtype=torch.float32, device=dev)
+        face = torch.full((N, height, width), -1, dtype=torch.int32, device=dev)
+        overflow = torch.zeros(N, dtype=torch.int32, device=dev)
+        return (depth, face, overflow) if return_overflow else (depth, face)
+    if workspace is None:
+        workspace = mesh_raster_workspace(dev, N, F, height, width)
+    verts, faces = verts.contiguous(), faces.contiguous()
+    depth = torch.empty((N, height, width), dtype=torch.float32, device=dev)
+    face = torch.empty((N, height, width), dtype=torch.int32, device=dev)
+    overflow = torch.empty(N, dtype=torch.int32, device=dev)
+    launch("dvmvs_mesh_raster_fwd", dev, ptr(verts), V, ptr(faces), F, ptr(K), ptr(w2c), N, height, width, near, far, 1 if cull_backfaces else 0,
+           large_box, ptr(workspace), workspace.numel() * 8, ptr(depth), ptr(face), ptr(overflow))
+    return (depth, face, overflow) if return_overflow else (depth, face)
+
+
+def mesh_visibility(verts: Tensor, depth: Tensor, cam_intr: Tensor, cam_poses: Tensor, near: float = 0.05, relative: float = 0.01,
+                    absolute: float = 0.0) -> Tensor:
+    """For every vertex of ``verts`` float32 [V,3] the number of views that see it, int32 [V] (definition in include/dvmvs_hip.h): view r
+    sees a vertex whose camera depth z is at least ``near``, whose projection lies inside the image, and with
+    ``z <= D (1 + relative) + absolute`` for the largest positive ``D`` among the up to four pixels of ``depth[r]`` around the projection.
+    ``depth`` float32 [N,H,W] (normally ``mesh_raster``'s), ``cam_intr`` [N,3,3], camera-to-world ``cam_poses`` [N,4,4], all on one GPU.
+    One launch on the current stream: no host read and no synchronisation."""
+    name = "mesh_visibility"
+    check_tensors(name, verts, label="verts", shape=(None, 3))
+    dev = verts.device
+    check_tensors(name, depth, label="depth", shape=(None, None, None), device=dev)
+    N, K, w2c = _mesh_cameras(name, cam_intr, cam_poses, dev)
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    near, relative, absolute = _mesh_near(name, near), float(relative), float(absolute)
+    if depth.shape[0] != N or H < 1 or W < 1:
+        raise ValueError(f"dvmvs::{name}: expected {N} non-empty depth maps, got {tuple(depth.shape)}")
+    if relative != relative or absolute != absolute:
+        raise ValueError(f"dvmvs::{name}: a threshold is NaN")
+    mesh_raster_workspace_bytes(N, 1, H, W)          # the shape limits of the family
+    V = int(verts.shape[0])
+    count = torch.empty(V, dtype=torch.int32, device=dev)
+    if V > 0:
+        launch("dvmvs_mesh_visibility_fwd", dev, ptr(verts.contiguous()), V, ptr(depth.contiguous()), ptr(K), ptr(w2c), N, H, W, near, relative,
+               absolute, ptr(count))
+    return count
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # filtering depth maps by multi-view geometric consistency
 # ----------------------------------------------------------------------------------------------------------------------
 CONSISTENCY_MAX_SOURCES = 16

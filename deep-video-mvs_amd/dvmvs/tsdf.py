@@ -83,6 +83,84 @@ def marching_cubes(volume, level=0.0, color=None, origin=(0.0, 0.0, 0.0), voxel_
     return verts, faces, normals, colors
 
 
+def _mesh_and_cameras(verts, faces, cam_intr, cam_poses, device=None):
+    """Device tensors (verts float32 [V,3], faces int32 [F,3], K float32 [N,3,3], poses float32 [N,4,4]) of a mesh and its views, given as
+    arrays or tensors, the cameras as one matrix or a batch.  ``device``: where arrays go (default: where the vertices are, else "cuda")."""
+    if device is None:
+        device = verts.device if torch.is_tensor(verts) and verts.device.type == "cuda" else torch.device("cuda")
+
+    def as_dev(a, dtype):
+        if torch.is_tensor(a):
+            return a.to(device, dtype)
+        return torch.as_tensor(np.asarray(a, dtype={torch.float32: np.float32, torch.int32: np.int32}[dtype]), device=device)
+
+    def cameras(a, tail):
+        t = as_dev(a, torch.float32)
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3 or tuple(t.shape[1:]) != tail:
+            raise ValueError(f"expected [{tail[0]},{tail[1]}] or [N,{tail[0]},{tail[1]}], got {tuple(t.shape)}")
+        return t
+
+    verts, faces = as_dev(verts, torch.float32), as_dev(faces, torch.int32)
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"expected vertices [V,3] and faces [F,3], got {tuple(verts.shape)} and {tuple(faces.shape)}")
+    P, K = cameras(cam_poses, (4, 4)), cameras(cam_intr, (3, 3))
+    if K.shape[0] == 1 and P.shape[0] > 1:
+        K = K.expand(P.shape[0], 3, 3)
+    if K.shape[0] != P.shape[0]:
+        raise ValueError(f"{K.shape[0]} intrinsics for {P.shape[0]} poses")
+    return verts.contiguous(), faces.contiguous(), K.contiguous(), P.contiguous()
+
+
+def render_mesh(verts, faces, cam_intr, cam_poses, height, width, near=0.05, far=float("inf"), cull_backfaces=False):
+    """Rasterises a triangle mesh from N views in one call (``dvmvs.hip.ops.mesh_raster``, csrc/mesh_raster.hip; definition in
+    include/dvmvs_hip.h): ``verts`` [V,3] world space and ``faces`` [F,3], ``cam_poses`` camera-to-world [N,4,4] or one [4,4], ``cam_intr``
+    [N,3,3] or one [3,3] for all views; numpy arrays or tensors, as ``TSDFVolume.render`` takes them.  Returns DEVICE tensors ``(depth
+    [N,height,width] float32, face [N,height,width] int32)``: the camera depth of the nearest face at every pixel (0 where there is none)
+    and its index (-1), at the pixel positions of ``TSDFVolume.render``, so that the depth maps can go to ``compute_errors_device``.
+    Reads ONE number per view from the device (a synchronisation): the triangles left out because they project beyond 2^21 pixels, and
+    warns when there are any."""
+    import warnings
+    from dvmvs.hip import ops
+    verts, faces, K, P = _mesh_and_cameras(verts, faces, cam_intr, cam_poses)
+    depth, face, overflow = ops.mesh_raster(verts, faces, K, P, height, width, near=near, far=far, cull_backfaces=cull_backfaces,
+                                            return_overflow=True)
+    left_out = int(overflow.sum())                                  # the one host read
+    if left_out:
+        warnings.warn(f"render_mesh: {left_out} clipped triangles project beyond 2^21 pixels and were left out", RuntimeWarning, stacklevel=2)
+    return depth, face
+
+
+VISIBLE_MESH_CHUNK = 32       # views rasterised per call of visible_mesh: bounds the z-buffer keys (8 bytes per pixel and view)
+
+
+def visible_mesh(verts, faces, cam_intr, cam_poses, height, width, min_views=1, near=0.05, relative=0.01, absolute=0.0):
+    """The part of a mesh that N views observed: the mesh is rasterised from the views (``render_mesh``'s op), every vertex is tested
+    against those depth maps (``dvmvs.hip.ops.mesh_visibility``: in front of ``near``, inside the image, not deeper than the rendered
+    surface by more than ``relative`` of it plus ``absolute`` metres), and the faces whose three vertices are each seen by at least
+    ``min_views`` views are kept.  Arguments as ``render_mesh``.  Returns DEVICE tensors ``(verts, kept_faces)``: the vertices are
+    unchanged, so the face indices stay valid.  The views go through in chunks of ``VISIBLE_MESH_CHUNK``, so the memory does not grow
+    with the length of the sequence.  No host read but the size of the result (the boolean selection of the kept faces)."""
+    from dvmvs.hip import ops
+    verts, faces, K, P = _mesh_and_cameras(verts, faces, cam_intr, cam_poses)
+    min_views = int(min_views)
+    if min_views < 1:
+        raise ValueError(f"visible_mesh: min_views must be at least 1, got {min_views}")
+    count = torch.zeros(verts.shape[0], dtype=torch.int32, device=verts.device)
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        return verts, faces[:0]
+    for first in range(0, P.shape[0], VISIBLE_MESH_CHUNK):
+        k, p = K[first:first + VISIBLE_MESH_CHUNK], P[first:first + VISIBLE_MESH_CHUNK]
+        depth, _ = ops.mesh_raster(verts, faces, k, p, height, width, near=near)
+        count += ops.mesh_visibility(verts, depth, k, p, near=near, relative=relative, absolute=absolute)
+    V = verts.shape[0]
+    index = faces.long()
+    valid = ((index >= 0) & (index < V)).all(dim=1)
+    seen = (count[index.clamp(0, V - 1)] >= min_views).all(dim=1) & valid
+    return verts, faces[seen]
+
+
 class TSDFVolume:
     """Voxel volume over ``vol_bnds`` ([[x0, x1], [y0, y1], [z0, z1]] in metres) with ``voxel_size`` edges.  tsdf starts at 1,
     weight and colour at 0; truncation = 5 voxels, as in the reference."""
@@ -251,7 +329,7 @@ class TSDFVolume:
         verts, faces = self.mesh_tensors()
         return prepare_points_device(verts, faces, sample_density, voxel)
 
-    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None):
+    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None):
         """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
         DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
         ``dvmvs.errors.compute_reconstruction_errors_device`` without a download.  ``reference``: another ``TSDFVolume``, [M,3] points as a
@@ -264,9 +342,20 @@ class TSDFVolume:
         ``surface_points``-style samples of them, and ``voxel`` (metres) replaces each side by one point per occupied voxel, so that both
         clouds have the same resolution (the usual evaluation protocol; ``dvmvs.errors.prepare_points``).  Each of those steps reads its
         output's size once.  Raises ``ValueError`` when either point set is empty.  ``return_sizes``: also return the sizes of the two
-        point sets that were scored ``(prediction, reference)``, numbers the host has anyway (tensor shapes)."""
+        point sets that were scored ``(prediction, reference)``, numbers the host has anyway (tensor shapes).
+
+        ``visible_from``: a tuple ``(cam_intr, cam_poses, height, width)`` or ``(cam_intr, cam_poses, height, width, min_views)``.  The
+        reference, which must then be a mesh (a pair, or a ``TSDFVolume``), is first restricted by ``visible_mesh`` to the faces those views
+        observed, so that surface the sequence never faced does not count against completeness and recall.  It needs ``sample_density``:
+        the vertices of a culled face set would still include those that no kept face uses.  ``ValueError`` otherwise, and for a bare
+        point set.  With ``return_sizes`` a third entry ``(kept faces, all faces)`` of the reference is returned."""
         from dvmvs.errors import compute_reconstruction_errors_device, prepare_points_device
         prepare = sample_density is not None or voxel is not None
+        if visible_from is not None:
+            if sample_density is None:
+                raise ValueError("score_against: visible_from needs sample_density (the kept faces are sampled; the vertices are not culled)")
+            if len(visible_from) not in (4, 5):
+                raise ValueError("score_against: visible_from is (cam_intr, cam_poses, height, width[, min_views])")
         gt_faces = None
         if isinstance(reference, TSDFVolume):
             gt, gt_faces = reference.mesh_tensors() if prepare else (reference.vertices(), None)
@@ -277,6 +366,15 @@ class TSDFVolume:
             gt = torch.as_tensor(reference, dtype=torch.float32, device=self.device)
             if gt.dim() != 2 or gt.shape[1] != 3:
                 raise ValueError(f"score_against: reference points must be [M,3], got {tuple(gt.shape)}")
+        face_counts = None
+        if visible_from is not None:
+            if gt_faces is None:
+                raise ValueError("score_against: visible_from restricts a mesh reference; a bare point set has no faces to cull")
+            cam_intr, cam_poses, height, width = visible_from[:4]
+            all_faces = int(gt_faces.shape[0])
+            gt, gt_faces = visible_mesh(gt.contiguous(), torch.as_tensor(gt_faces, device=self.device).to(torch.int32), cam_intr, cam_poses,
+                                        height, width, min_views=visible_from[4] if len(visible_from) == 5 else 1)
+            face_counts = (int(gt_faces.shape[0]), all_faces)
         if prepare:
             if gt_faces is not None:
                 gt_faces = torch.as_tensor(gt_faces, device=self.device).to(torch.int32)
@@ -287,7 +385,10 @@ class TSDFVolume:
         if pred.shape[0] == 0 or gt.shape[0] == 0:
             raise ValueError(f"score_against: a surface without a vertex cannot be scored ({pred.shape[0]} predicted, {gt.shape[0]} reference)")
         row = compute_reconstruction_errors_device(pred, gt.contiguous(), threshold)
-        return (row, (int(pred.shape[0]), int(gt.shape[0]))) if return_sizes else row
+        if not return_sizes:
+            return row
+        sizes = (int(pred.shape[0]), int(gt.shape[0]))
+        return (row, sizes) if face_counts is None else (row, sizes, face_counts)
 
 
 class TSDFFusion:
@@ -637,7 +738,8 @@ def _mesh_name(reconstruction_folder, voxel_size, max_depth, anchor, system, dat
 def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, scene_name, system_name, voxel_size, max_depth,
         use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False,
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
-        consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None):
+        consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
+        evaluate_3d_visible=False, evaluate_3d_min_views=1):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -664,6 +766,12 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     and ``voxel`` (NaN where not given) and ``points`` int64 [2], the sizes of the two point sets that were scored; ``counts`` stays the
     vertices of the two surfaces.  Without them the file is what it is without them, byte for byte.
 
+    ``evaluate_3d_visible`` (needs ``evaluate_3d``, ``groundtruth_mesh`` and ``evaluate_3d_density``): the ground-truth mesh is first
+    restricted to what the sequence observed, the faces whose three vertices are each seen by at least ``evaluate_3d_min_views`` of the
+    fused keyframes' views at the prediction size (``visible_mesh``: the mesh is rasterised from those views on the device), so that the
+    parts of a scan that the camera never faced do not count against completeness and recall.  ``_errors3d.npz`` then also holds
+    ``visible_faces`` and ``total_faces``.
+
     ``filter_consistency``: after the masks above, the keyframe predictions go up once and are filtered by multi-view geometric consistency
     in one launch (``dvmvs.consistency.filter_depths``): a pixel is kept, with its own depth, where at least ``consistency_views`` of the
     ``consistency_sources`` keyframes nearest to it in keyframe order (never across a "TRACKING LOST" line) agree within
@@ -678,6 +786,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     protocol_3d = evaluate_3d_density is not None or evaluate_3d_voxel is not None or groundtruth_mesh is not None
     if protocol_3d and not evaluate_3d:
         raise ValueError("evaluate_3d_density, evaluate_3d_voxel and groundtruth_mesh say how evaluate_3d scores: they need evaluate_3d")
+    if evaluate_3d_visible and not (evaluate_3d and groundtruth_mesh is not None and evaluate_3d_density is not None):
+        raise ValueError("evaluate_3d_visible culls a ground-truth mesh whose kept faces are then sampled: it needs evaluate_3d, "
+                         "groundtruth_mesh and evaluate_3d_density")
+    if int(evaluate_3d_min_views) != 1 and not evaluate_3d_visible:
+        raise ValueError("evaluate_3d_min_views says how evaluate_3d_visible culls: it needs evaluate_3d_visible")
+    if int(evaluate_3d_min_views) < 1:
+        raise ValueError(f"evaluate_3d_min_views must be at least 1, got {evaluate_3d_min_views}")
     fuse_groundtruth_3d = evaluate_3d and groundtruth_mesh is None
     from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, load_image_u8, resize_nearest
     if device_preprocess:
@@ -774,7 +889,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         TSDFFusion.pcwrite(system_mesh_name + "_pointcloud.ply", point_cloud if point_cloud is not None else np.zeros((0, 6), np.float32))
     if evaluate_3d:
         if protocol_3d:
-            _evaluate_3d_protocol(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_density, evaluate_3d_voxel)
+            visible_from = None
+            if evaluate_3d_visible:
+                if not keyframe_poses:
+                    raise ValueError("evaluate_3d_visible: the scene has no keyframe to take the visibility from")
+                visible_from = (scaled_K, np.stack(keyframe_poses), prediction_height, prediction_width, int(evaluate_3d_min_views))
+            _evaluate_3d_protocol(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_density, evaluate_3d_voxel,
+                                  visible_from)
         else:
             _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name)
     if render_keyframes:
@@ -812,10 +933,18 @@ def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name):
                         counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold))
 
 
-def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample_density, voxel):
-    """``_evaluate_3d`` against a ground-truth mesh (device verts and faces), with face sampling and / or voxel down-sampling of both sides."""
+def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample_density, voxel, visible_from=None):
+    """``_evaluate_3d`` against a ground-truth mesh (device verts and faces), with face sampling and / or voxel down-sampling of both sides;
+    with ``visible_from`` (``TSDFVolume.score_against``) against the part of the mesh those views observed."""
     from dvmvs.errors import RECONSTRUCTION_METRICS
-    row, points = volume.score_against(groundtruth_mesh, threshold, return_sizes=True, sample_density=sample_density, voxel=voxel)
+    extra = {}
+    if visible_from is None:
+        row, points = volume.score_against(groundtruth_mesh, threshold, return_sizes=True, sample_density=sample_density, voxel=voxel)
+    else:
+        row, points, kept = volume.score_against(groundtruth_mesh, threshold, return_sizes=True, sample_density=sample_density, voxel=voxel,
+                                                 visible_from=visible_from)
+        print("Ground truth restricted to what {} keyframes saw: {} of {} faces".format(len(visible_from[1]), kept[0], kept[1]))
+        extra = {"visible_faces": np.int64(kept[0]), "total_faces": np.int64(kept[1])}
     row = row.cpu().numpy()
     sizes = (int(volume.vertices().shape[0]), int(groundtruth_mesh[0].shape[0]))
     print("3-D metrics at {} m over {} predicted and {} ground-truth points (density {}, voxel {}; {} and {} vertices): {}".format(
@@ -824,7 +953,7 @@ def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
                         counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold),
                         sample_density=np.float64(np.nan if sample_density is None else sample_density),
-                        voxel=np.float64(np.nan if voxel is None else voxel), points=np.array(points, dtype=np.int64))
+                        voxel=np.float64(np.nan if voxel is None else voxel), points=np.array(points, dtype=np.int64), **extra)
 
 
 def _render_keyframes(volume, poses, image_filenames, K, preprocessor, height, width, scene_folder, system_name, scene_name, save_folder):
@@ -878,6 +1007,11 @@ def build_parser():
                         help="with --evaluate_3d: down-sample both point sets to one point per voxel of this edge, metres")
     parser.add_argument("--groundtruth_mesh", default=None, type=str,
                         help="with --evaluate_3d: score against this .ply mesh (ascii or binary little endian) instead of the fused ground-truth depth maps")
+    parser.add_argument("--evaluate_3d_visible", action="store_true",
+                        help="with --evaluate_3d, --groundtruth_mesh and --evaluate_3d_density: score against the part of the ground-truth "
+                             "mesh that the fused keyframes saw (the mesh is rasterised from their views on the device)")
+    parser.add_argument("--evaluate_3d_min_views", default=1, type=int,
+                        help="with --evaluate_3d_visible: keyframes that must see each vertex of a ground-truth face for it to be kept")
     parser.add_argument("--filter_consistency", action="store_true",
                         help="fuse only the pixels that neighbouring keyframes agree on (multi-view geometric consistency, on the device); "
                              "files are written under <system>+consistent")

@@ -57,7 +57,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_consistency_matrices and dvmvs_depth_consistency_fwd (filtering depth maps by multi-view geometric
  * consistency); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_surface_sample_* and dvmvs_voxel_* (point sets for the 3-D metrics: area-weighted samples of a triangle
- * mesh, one point per occupied voxel of a cloud); no earlier signature changed, the number stays 11 by the same rule. */
+ * mesh, one point per occupied voxel of a cloud); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_mesh_raster_* and dvmvs_mesh_visibility_fwd (rasterising a triangle mesh to depth maps, and the vertices
+ * that depth maps show); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -824,6 +826,71 @@ int dvmvs_voxel_keys(const float* points, long long N, float inv_voxel, void* wo
 int dvmvs_voxel_downsample_count(const float* points, long long N, const long long* sorted_keys, const long long* sorted_index,
                                  void* workspace, size_t workspace_bytes, long long* counts, dvmvs_stream_t stream);
 int dvmvs_voxel_downsample_emit(long long N, long long M, const void* workspace, float* out, int* count, dvmvs_stream_t stream);
+
+/*
+ * Mesh rasterisation (ABI 11, later addition): the depth and the face of a triangle mesh at every pixel of n_views cameras, with a
+ * z-buffer, in ONE call; and which vertices a set of depth maps shows.  The reference project has no rasteriser: the definition is this
+ * project's own; tests/mesh_raster_reference.py restates it in numpy and the device reproduces that bit for bit.
+ *   verts [V,3] fp32 world space; faces [F,3] int32; cam_intr [n_views,3,3] (fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]);
+ *   cam_w2c [n_views,3,4] WORLD-TO-CAMERA (R | t), row-major; near > 0, finite; far (may be +inf); cull_backfaces 0 / 1;
+ *   large_box >= 1: see "work" below, it cannot change a result (DVMVS_MESH_RASTER_LARGE_BOX is the measured choice).
+ * fp32 throughout, every operation rounded (no FMA contraction), divisions correctly rounded, in exactly this order for view r, face f:
+ *   1. A face with an index outside [0, V) is skipped; no vertex is read for it.  Camera space, per corner j (a, b, c in the face's order):
+ *      p_j[i] = ((M[i][0] x + M[i][1] y) + M[i][2] z) + M[i][3].  A face with a coordinate that is not finite is skipped.
+ *   2. Plane of the UNCLIPPED triangle: e1 = b - a, e2 = c - a; nx = e1.y e2.z - e1.z e2.y, ny = e1.z e2.x - e1.x e2.z,
+ *      nz = e1.x e2.y - e1.y e2.x; na = (nx a.x + ny a.y) + nz a.z; lo = fmaxf(fminf(fminf(a.z, b.z), c.z), near),
+ *      hi = fmaxf(fmaxf(a.z, b.z), c.z).  With cull_backfaces the face is skipped unless na < 0 (it then shows the camera the side from which
+ *      its corners run counter-clockwise, the outside of a dvmvs_marching_cubes_emit mesh).
+ *   3. Near plane: corner j is BEHIND when p_j.z < near.  Three behind: the face is skipped.  None: one triangle (a, b, c).  Otherwise the
+ *      corners are rotated, keeping their cyclic order, to (v0, v1, v2) with v0 the odd one out, and the point where the edge from a corner
+ *      g behind to a corner h in front meets the plane is clip(g, h): t = (near - g.z) / (h.z - g.z), x = g.x + t (h.x - g.x), y likewise,
+ *      z = near (always from the corner behind, so two faces that share the edge compute the same point).
+ *      One behind (v0): piece 0 = (clip(v0,v1), v1, v2), piece 1 = (clip(v0,v1), v2, clip(v0,v2)).
+ *      Two behind (v1, v2): piece 0 = (v0, clip(v1,v0), clip(v2,v0)).
+ *   4. Every corner of a piece is projected and snapped to 8 sub-pixel bits: xp = (x / z) fx + cx, sx = rintf(256 xp), the same in y.  A piece
+ *      with |sx| or |sy| above 2^29 (2^21 pixels) or not a number at a corner is LEFT OUT and adds one to overflow[r]; else X = (int) sx.
+ *   5. Coverage, in int64 (no product exceeds 2^61): area = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0); a piece with area 0 is skipped; with
+ *      area < 0 its corners 1 and 2 are exchanged.  For the edges i -> j = 0 -> 1, 1 -> 2, 2 -> 0: dx = Xj - Xi, dy = Yj - Yi,
+ *      E(u, v) = dx (256 v - Yi) - dy (256 u - Xi): pixel (u, v), sampled AT its integer coordinates as the ray-caster's, is covered when
+ *      for every edge E > 0, or E == 0 and the edge is a top or left one: dy < 0, or dy == 0 and dx > 0.  Two pieces that share an edge
+ *      cover each sample on it exactly once.  Only pixels inside the image are looked at.
+ *   6. Depth of a covered pixel: dx = (u - cx) / fx, dy = (v - cy) / fy, den = (nx dx + ny dy) + nz, z = fminf(fmaxf(na / den, lo), hi).
+ *      fmaxf and fminf return their other operand for a NaN, so z is finite and near <= lo <= z <= hi whatever na / den is (a grazing
+ *      triangle).  z depends on (r, f, u, v) alone, not on the piece.  A pixel with z > far is not written.
+ *   7. Z-buffer: key = (bits of z << 32) | f, a 64-bit unsigned atomic minimum per pixel (positive floats order as their bits): the nearest
+ *      depth wins and, at equal depths, the lowest face index; the result does not depend on the order of arrival.
+ *   8. depth [n_views,im_h,im_w] fp32 out (0 = nothing), face [n_views,im_h,im_w] int32 out (-1 = nothing), overflow [n_views] int32 out.
+ * Work: a piece whose box of candidate pixels holds at most large_box pixels is rasterised by the thread of its (view, face); a larger one is
+ * appended, once per 16x16 tile of the image grid that its box meets, to a list in the workspace that resident workgroups then stride
+ * over, one pixel per lane; the length of the list is read on the device.
+ *   workspace   dvmvs_mesh_raster_workspace_bytes(n_views, F, im_h, im_w) bytes on the device, 16-byte aligned.  Every call writes what it
+ *               reads first (keys, list length): no initial state is needed, and a buffer may serve calls of different sizes in turn.
+ * dvmvs_mesh_raster_workspace_bytes: host only, no HIP call; 0 for a shape that dvmvs_mesh_raster_fwd refuses.
+ * dvmvs_mesh_raster_cameras: cam_w2c [n_views,3,4] fp32 out <- the top three rows of the inverse of cam_pose [n_views,4,4] fp32
+ * (camera-to-world), computed in fp64 by cofactors from the fp32 entries and rounded once; one thread per view.
+ *
+ * Vertex visibility: count [V] int32 out, the number of views r that SEE vertex i, which is when, with p = the camera-space point of step 1
+ * and fp32 operations in this order: p.z >= near;  xp = (p.x / p.z) fx + cx, yp likewise, 0 <= xp <= im_w - 1 and 0 <= yp <= im_h - 1;  and
+ * p.z <= D (1 + relative) + absolute, evaluated as (D * (1.0f + relative)) + absolute, for D the largest depth[r] value > 0 among the
+ * pixels (floor(xp) + {0,1}, floor(yp) + {0,1}) that are inside the image (not seen when there is none; a NaN is never the largest).
+ * depth [n_views,im_h,im_w] fp32: any depth maps, normally the rasteriser's.  One thread per vertex, the views in order.
+ *
+ * The rasteriser and the visibility return DVMVS_EINVAL for a null or misaligned pointer (4 bytes; workspace: 16), V, F, n_views, im_h or
+ * im_w < 1, large_box < 1, near
+ * not positive and finite, a NaN far / relative / absolute, cull_backfaces not 0 / 1, a workspace that is too small; DVMVS_EUNSUPPORTED for
+ * n_views > 65535, F > 2^28, V > 2^31 - 1, im_h or im_w > 16384, n_views im_h im_w >= 2^31, or 2 n_views F tiles >= 4e18 (tiles: the 16x16
+ * tiles of the image grid).  dvmvs_mesh_raster_cameras: DVMVS_EINVAL for a null or misaligned pointer or n_views < 1, DVMVS_EUNSUPPORTED for
+ * n_views > 65535.  Nothing is enqueued in either case.
+ */
+#define DVMVS_MESH_RASTER_LARGE_BOX 64
+size_t dvmvs_mesh_raster_workspace_bytes(long long n_views, long long n_faces, long long im_h, long long im_w);
+int dvmvs_mesh_raster_cameras(const float* cam_pose, float* cam_w2c, int n_views, dvmvs_stream_t stream);
+int dvmvs_mesh_raster_fwd(const float* verts, long long V, const int* faces, long long F, const float* cam_intr, const float* cam_w2c,
+                          int n_views, int im_h, int im_w, float near, float far, int cull_backfaces, int large_box, void* workspace,
+                          size_t workspace_bytes, float* depth, int* face, int* overflow, dvmvs_stream_t stream);
+int dvmvs_mesh_visibility_fwd(const float* verts, long long V, const float* depth, const float* cam_intr, const float* cam_w2c,
+                              int n_views, int im_h, int im_w, float near, float relative, float absolute, int* count,
+                              dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
