@@ -233,7 +233,205 @@ def prepare_points_device(verts, faces=None, sample_density=None, voxel=None, se
     return points
 
 
-def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05, pred_faces=None, gt_faces=None, sample_density=None, voxel=None):
+# ----------------------------------------------------------------------------------------------------------------------
+# registering the prediction to the ground truth before scoring: trimmed ICP with Horn's closed form
+# ----------------------------------------------------------------------------------------------------------------------
+REGISTRATION_STATUS = ("running", "converged", "too few correspondences", "iteration limit")
+REGISTRATION_MAX_ITERATIONS = 1024
+_ICP_BLOCK, _ICP_ROWS, _ICP_WAVE, _ICP_SWEEPS = 256, 4, 64, 16
+
+
+def transform_points(points, T):
+    """``points`` float32 [N,3] moved by the 4x4 ``T``: every entry of ``T[:3,:4]`` is rounded to float32 and
+    ``p' = ((A00 x + A01 y) + A02 z) + A03`` (likewise y, z) is evaluated in float32, each operation rounded, nothing fused."""
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    A = np.asarray(T, dtype=np.float64)[:3, :4].astype(np.float32)
+    x, y, z = points[:, 0].copy(), points[:, 1].copy(), points[:, 2].copy()
+    return np.stack([((A[r, 0] * x + A[r, 1] * y) + A[r, 2] * z) + A[r, 3] for r in range(3)], axis=1)
+
+
+def _butterfly(v):
+    """The xor butterfly over axis -2 (64 entries): every entry ends as the same sum, in the order the device's wave forms it."""
+    lanes = np.arange(_ICP_WAVE)
+    for m in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lanes ^ m, :]
+    return v
+
+
+def registration_moments(moved, target_points, dist, inlier):
+    """The 18 float64 sums of one iteration over the inliers: n | sum p' [3] | sum q [3] | sum p' q^T [9] | sum |p'|^2 | sum d^2, added in
+    the order include/dvmvs_hip.h fixes (blocks of 1024 points, 256 strided threads, wave butterfly, waves in order; then 64 strided
+    lanes over the block sums and one more butterfly).  ``target_points``: q_i, the nearest target of every moved point."""
+    p, q, d = moved.astype(np.float64), target_points.astype(np.float64), dist.astype(np.float64)
+    n = len(p)
+    terms = np.empty((n, 18), dtype=np.float64)
+    terms[:, 0] = 1.0
+    terms[:, 1:4], terms[:, 4:7] = p, q
+    terms[:, 7:16] = (p[:, :, None] * q[:, None, :]).reshape(n, 9)
+    terms[:, 16] = (p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1]) + p[:, 2] * p[:, 2]
+    terms[:, 17] = d * d
+    terms[~inlier] = 0.0                                       # a skipped point and an added +0.0 are the same bits
+    group = _ICP_BLOCK * _ICP_ROWS
+    groups = -(-n // group)
+    padded = np.zeros((groups * group, 18), dtype=np.float64)
+    padded[:n] = terms
+    padded = padded.reshape(groups, _ICP_ROWS, _ICP_BLOCK, 18)
+    threads = np.zeros((groups, _ICP_BLOCK, 18), dtype=np.float64)
+    for r in range(_ICP_ROWS):
+        threads = threads + padded[:, r]
+    waves = _butterfly(threads.reshape(groups, _ICP_BLOCK // _ICP_WAVE, _ICP_WAVE, 18))[:, :, 0]
+    partials = waves[:, 0]
+    for w in range(1, _ICP_BLOCK // _ICP_WAVE):
+        partials = partials + waves[:, w]
+    rounds = -(-groups // _ICP_WAVE)
+    padded = np.zeros((rounds * _ICP_WAVE, 18), dtype=np.float64)
+    padded[:groups] = partials
+    padded = padded.reshape(rounds, _ICP_WAVE, 18)
+    lanes = np.zeros((_ICP_WAVE, 18), dtype=np.float64)
+    for r in range(rounds):
+        lanes = lanes + padded[r]
+    return _butterfly(lanes)[0]
+
+
+def _horn_quaternion(S):
+    """(w, x, y, z), w >= 0: the eigenvector of the largest eigenvalue of Horn's symmetric 4x4 matrix of ``S`` (nine floats, row-major),
+    by cyclic Jacobi sweeps in float64 with +, -, *, / and sqrt only (Python floats: each operation correctly rounded)."""
+    Sxx, Sxy, Sxz, Syx, Syy, Syz, Szx, Szy, Szz = S
+    A = [[(Sxx + Syy) + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx],
+         [Syz - Szy, (Sxx - Syy) - Szz, Sxy + Syx, Szx + Sxz],
+         [Szx - Sxz, Sxy + Syx, (Syy - Sxx) - Szz, Syz + Szy],
+         [Sxy - Syx, Szx + Sxz, Syz + Szy, (Szz - Sxx) - Syy]]
+    V = [[1.0 if r == c else 0.0 for c in range(4)] for r in range(4)]
+    pairs = [(p, q) for p in range(3) for q in range(p + 1, 4)]
+    for _ in range(_ICP_SWEEPS):
+        if all(A[p][q] == 0.0 for p, q in pairs):
+            break
+        for p, q in pairs:
+            apq = A[p][q]
+            if apq == 0.0:
+                continue
+            theta = (A[q][q] - A[p][p]) / (2.0 * apq)
+            mag = abs(theta) + math.sqrt(theta * theta + 1.0)
+            t = -1.0 / mag if theta < 0.0 else 1.0 / mag
+            c = 1.0 / math.sqrt(t * t + 1.0)
+            s = t * c
+            for k in range(4):
+                akp, akq = A[k][p], A[k][q]
+                A[k][p], A[k][q] = c * akp - s * akq, s * akp + c * akq
+            for k in range(4):
+                apk, aqk = A[p][k], A[q][k]
+                A[p][k], A[q][k] = c * apk - s * aqk, s * apk + c * aqk
+            A[p][q] = A[q][p] = 0.0
+            for k in range(4):
+                vkp, vkq = V[k][p], V[k][q]
+                V[k][p], V[k][q] = c * vkp - s * vkq, s * vkp + c * vkq
+    best = 0
+    for k in range(1, 4):
+        if A[k][k] > A[best][best]:
+            best = k
+    w, x, y, z = (V[r][best] for r in range(4))
+    norm = math.sqrt(((w * w + x * x) + y * y) + z * z)
+    w, x, y, z = w / norm, x / norm, y / norm, z / norm
+    return (-w, -x, -y, -z) if w < 0.0 else (w, x, y, z)
+
+
+def registration_solve(moments, T, with_scale=False):
+    """The update of one iteration from its 18 sums (n >= 3): the float64 4x4 ``[sR t; 0 1] T``, or None where the scale's denominator is
+    not positive.  Every operation in float64, in the order include/dvmvs_hip.h states."""
+    v = [float(m) for m in moments]
+    with np.errstate(all="ignore"):
+        return _registration_solve(v, [[float(e) for e in row] for row in np.asarray(T, dtype=np.float64)], with_scale)
+
+
+def _registration_solve(v, T, with_scale):
+    n = v[0]
+    pbar, qbar = [v[1 + a] / n for a in range(3)], [v[4 + a] / n for a in range(3)]
+    S = [v[7 + a * 3 + b] - (v[1 + a] * v[4 + b]) / n for a in range(3) for b in range(3)]
+    w, x, y, z = _horn_quaternion(S)
+    R = [1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+         2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+         2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]
+    scale = 1.0
+    if with_scale:
+        denominator = v[16] - ((v[1] * v[1] + v[2] * v[2]) + v[3] * v[3]) / n
+        if not denominator > 0.0:
+            return None
+        trace = 0.0
+        for a in range(3):
+            for b in range(3):
+                trace += R[a * 3 + b] * S[b * 3 + a]
+        scale = trace / denominator
+    M = [scale * r for r in R]
+    shift = [qbar[a] - ((M[a * 3] * pbar[0] + M[a * 3 + 1] * pbar[1]) + M[a * 3 + 2] * pbar[2]) for a in range(3)]
+    out = [[((M[a * 3] * T[0][c] + M[a * 3 + 1] * T[1][c]) + M[a * 3 + 2] * T[2][c]) + shift[a] * T[3][c] for c in range(4)] for a in range(3)]
+    return np.array(out + [T[3]], dtype=np.float64)
+
+
+def register_points(source, target, max_distance, init=None, max_iterations=30, with_scale=False, tolerance=1e-6):
+    """Registers ``source`` [N,3] to ``target`` [M,3] by trimmed ICP: ``(T float64 [4,4], info)``, ``T`` taking source coordinates into the
+    target's frame.  The host definition that ``dvmvs.hip.registration.icp`` reproduces bit for bit (include/dvmvs_hip.h restates it).
+    Iteration k, from ``T_0 = init`` (or the identity): the source moved by ``transform_points``; its nearest targets by
+    ``nearest_distances`` (float32, smallest index); the inliers ``d <= float32(max_distance)``; their ``registration_moments``;
+    rmse_k = sqrt(sum d^2 / n) (0 without inliers) and fitness_k = n / N, which describe T_k; fewer than 3 inliers stop with status 2;
+    from k = 1 on, rmse and fitness both within ``tolerance`` (strictly) of the iteration before stop with status 1 and leave T; otherwise
+    ``registration_solve`` (Horn's quaternion by Jacobi sweeps, Umeyama's scale with ``with_scale``) gives T_{k+1}; status 3 at the limit.
+    ``info``: ``iterations``, ``status`` (an index of ``REGISTRATION_STATUS``), and per recorded iteration ``inliers`` (int64), ``fitness``,
+    ``rmse`` (float64), with ``moments``, the sums of the last one."""
+    source = np.ascontiguousarray(source, dtype=np.float32).reshape(-1, 3)
+    target = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 3)
+    max_distance, tolerance, max_iterations = np.float32(max_distance), float(tolerance), int(max_iterations)
+    if len(source) == 0 or len(target) == 0:
+        raise ValueError("register_points: both point clouds must hold at least one point")
+    if not max_distance > 0.0 or not tolerance >= 0.0:
+        raise ValueError(f"register_points: max_distance must be positive and tolerance not negative, got {max_distance}, {tolerance}")
+    if not 1 <= max_iterations <= REGISTRATION_MAX_ITERATIONS:
+        raise ValueError(f"register_points: max_iterations must be in 1 .. {REGISTRATION_MAX_ITERATIONS}, got {max_iterations}")
+    T = np.eye(4, dtype=np.float64) if init is None else np.array(init, dtype=np.float64)
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError("register_points: init must be a finite 4x4 matrix")
+    inliers, fitness, rmse = [], [], []
+    status, moments = 0, np.zeros(18, dtype=np.float64)
+    for k in range(max_iterations):
+        moved = transform_points(source, T)
+        dist, index = nearest_distances(moved, target, return_index=True)
+        moments = registration_moments(moved, target[index], dist, dist <= max_distance)
+        n = float(moments[0])
+        inliers.append(int(n))
+        fitness.append(n / float(len(source)))
+        rmse.append(math.sqrt(float(moments[17]) / n) if n > 0.0 else 0.0)
+        if n < 3.0:
+            status = 2
+            break
+        if k >= 1 and abs(rmse[k] - rmse[k - 1]) < tolerance and abs(fitness[k] - fitness[k - 1]) < tolerance:
+            status = 1
+            break
+        update = registration_solve(moments, T, with_scale)
+        if update is None:
+            status = 2
+            break
+        T = update
+        if k + 1 == max_iterations:
+            status = 3
+    info = {"iterations": len(inliers), "status": status, "inliers": np.array(inliers, dtype=np.int64),
+            "fitness": np.array(fitness, dtype=np.float64), "rmse": np.array(rmse, dtype=np.float64), "moments": moments}
+    return T, info
+
+
+def register_points_device(source, target, max_distance, init=None, max_iterations=30, with_scale=False, tolerance=1e-6, grid=None):
+    """``register_points`` for device tensors (``dvmvs.hip.registration.icp``): the same bits, ``T`` and every entry of ``info`` on the GPU,
+    nothing read by the call.  ``grid``: an existing ``ops.nearest_build`` workspace of ``target``."""
+    from dvmvs.hip import registration
+    return registration.icp(source, target, max_distance, init=init, max_iterations=max_iterations, with_scale=with_scale, tolerance=tolerance,
+                            grid=grid)
+
+
+def _check_alignment(name, align_distance, align_scale, align_init, return_transform):
+    if align_distance is None and (align_scale or align_init is not None or return_transform):
+        raise ValueError(f"{name}: align_scale, align_init and return_transform say how align_distance registers: they need align_distance")
+
+
+def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05, pred_faces=None, gt_faces=None, sample_density=None, voxel=None,
+                                  align_distance=None, align_scale=False, align_init=None, return_transform=False):
     """The 3-D reconstruction metrics of the Atlas / NeuralRecon / SimpleRecon evaluations between a predicted point set [N,3] and a
     ground-truth point set [M,3], float32 [6] in the order of ``RECONSTRUCTION_METRICS``:
       acc = mean distance from a predicted point to its nearest ground-truth point; comp = the same from ground truth to prediction;
@@ -245,30 +443,62 @@ def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05, pred_f
     voxel size soundly and nothing else.  The usual protocol is the keywords: ``pred_faces`` / ``gt_faces`` (int32 [F,3]) with
     ``sample_density`` (points per square metre) replace a side's vertices by ``sample_surface`` of its mesh, and ``voxel`` (metres)
     replaces each side by its ``voxel_down_sample``, so that both clouds have a common resolution (``prepare_points``).  Raises
-    ``ValueError`` when either set is, or becomes, empty."""
+    ``ValueError`` when either set is, or becomes, empty.
+
+    ``align_distance`` (metres): the prediction's prepared point set is first registered to the ground truth's by ``register_points`` with
+    that inlier distance (``align_scale``: a similarity instead of a rigid motion; ``align_init``: a 4x4 to start from), moved by the
+    result (``transform_points``) and then scored, as the Tanks-and-Temples evaluation does; ``return_transform``: return
+    ``(row, T float64 [4,4])``.  With ``align_distance`` at None nothing is registered and the row is what it is without the keywords."""
+    _check_alignment("compute_reconstruction_errors", align_distance, align_scale, align_init, return_transform)
     pred_points = prepare_points(pred_points, pred_faces, sample_density, voxel)
     gt_points = prepare_points(gt_points, gt_faces, sample_density, voxel)
     if len(pred_points) == 0 or len(gt_points) == 0:
         raise ValueError("compute_reconstruction_errors: both point clouds must hold at least one point")
-    return reconstruction_metrics_from_distances(nearest_distances(pred_points, gt_points), nearest_distances(gt_points, pred_points),
-                                                 threshold)[0]
+    transform = None
+    if align_distance is not None:
+        transform, _ = register_points(pred_points, gt_points, align_distance, init=align_init, with_scale=align_scale)
+        pred_points = transform_points(pred_points, transform)
+    row = reconstruction_metrics_from_distances(nearest_distances(pred_points, gt_points), nearest_distances(gt_points, pred_points),
+                                                threshold)[0]
+    return (row, transform) if return_transform else row
 
 
 def compute_reconstruction_errors_device(pred_points, gt_points, threshold=0.05, counts=None, pred_faces=None, gt_faces=None,
-                                         sample_density=None, voxel=None):
+                                         sample_density=None, voxel=None, align_distance=None, align_scale=False, align_init=None,
+                                         return_transform=False):
     """``compute_reconstruction_errors`` for point sets that live on the GPU (float32 [N,3] and [M,3] device tensors, both non-empty):
     a float32 device tensor [6].  Two grid builds, two nearest-point queries (csrc/nearest_points.hip: the distances are the host
     function's, bit for bit) and one reduction in float64, all on the current stream; with every keyword at None nothing is copied to
     the host.  ``counts``: an int64 [2] device tensor that receives the numbers of distances below the threshold.  ``pred_faces`` /
     ``gt_faces`` (int32 [F,3] device tensors), ``sample_density`` and ``voxel`` as in the host function, on the device
-    (csrc/surface_sample.hip: the host definitions' bits; each sampling and each down-sampling reads its output's size once)."""
+    (csrc/surface_sample.hip: the host definitions' bits; each sampling and each down-sampling reads its output's size once).
+    ``align_distance``, ``align_scale``, ``align_init`` (a HOST 4x4) and ``return_transform`` as in the host function: the registration
+    (``dvmvs.hip.registration.icp``: the host definition's bits, no host read) uses the ground truth's grid, which then also serves the
+    accuracy query; the transform comes back as a float64 [4,4] device tensor."""
+    _check_alignment("compute_reconstruction_errors_device", align_distance, align_scale, align_init, return_transform)
+    row, transform, _ = _score_device(pred_points, gt_points, threshold, counts, pred_faces, gt_faces, sample_density, voxel, align_distance,
+                                      align_scale, align_init)
+    return (row, transform) if return_transform else row
+
+
+def _score_device(pred_points, gt_points, threshold, counts, pred_faces, gt_faces, sample_density, voxel, align_distance, align_scale,
+                  align_init):
+    """``compute_reconstruction_errors_device``: ``(row, transform or None, the registration's info or None)``."""
     from dvmvs.hip import ops      # (imported here: this module stays importable, and the host functions usable, without a GPU)
+    transform = info = None
     if pred_faces is not None or gt_faces is not None or sample_density is not None or voxel is not None:
         pred_points = prepare_points_device(pred_points, pred_faces, sample_density, voxel)
         gt_points = prepare_points_device(gt_points, gt_faces, sample_density, voxel)
     for label, t in (("pred_points", pred_points), ("gt_points", gt_points)):
         if hasattr(t, "shape") and len(t.shape) == 2 and t.shape[0] == 0:
             raise ValueError(f"compute_reconstruction_errors_device: {label} is empty")
-    dist_pred = ops.nearest_distance(pred_points, gt_points)
+    if align_distance is None:
+        dist_pred = ops.nearest_distance(pred_points, gt_points)
+    else:       # one grid of the ground truth serves the registration's queries and the accuracy query
+        from dvmvs.hip import registration
+        grid = ops.nearest_build(gt_points)
+        transform, info = registration.icp(pred_points, gt_points, align_distance, init=align_init, with_scale=align_scale, grid=grid)
+        pred_points = registration.transform_points(pred_points, transform)
+        dist_pred = ops.nearest_query(pred_points, gt_points, grid)
     dist_gt = ops.nearest_distance(gt_points, pred_points)
-    return ops.distance_metrics(dist_pred, dist_gt, threshold, counts=counts)
+    return ops.distance_metrics(dist_pred, dist_gt, threshold, counts=counts), transform, info

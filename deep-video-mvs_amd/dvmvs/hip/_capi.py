@@ -143,6 +143,10 @@ SIGNATURES = {
                                        ctypes.c_float, _c_int, _c_int, _c_fp, ctypes.c_size_t, _c_fp, _c_fp, _c_fp, _c_stream]),
     "dvmvs_mesh_visibility_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float,
                                            ctypes.c_float, _c_fp, _c_stream]),
+    "dvmvs_icp_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, _c_int]),
+    "dvmvs_icp_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_size_t, ctypes.c_float, _c_int, _c_int,
+                               _c_dbl, ctypes.POINTER(ctypes.c_double), _c_fp, ctypes.c_size_t, _c_stream]),
+    "dvmvs_transform_points_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -166,6 +170,8 @@ ADDED_WITHIN_ABI_SURFACE_SAMPLE = ("dvmvs_surface_sample_workspace_bytes", "dvmv
 # ... and the eighth (rasterising a triangle mesh to depth maps; vertex visibility)
 ADDED_WITHIN_ABI_MESH_RASTER = ("dvmvs_mesh_raster_workspace_bytes", "dvmvs_mesh_raster_cameras", "dvmvs_mesh_raster_fwd",
                                 "dvmvs_mesh_visibility_fwd")
+# ... and the ninth (registering a point cloud to another by trimmed ICP)
+ADDED_WITHIN_ABI_REGISTRATION = ("dvmvs_icp_workspace_bytes", "dvmvs_icp_fwd", "dvmvs_transform_points_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -185,7 +191,8 @@ def lib():
                 f"(or __graft_entry__.build()). The plane-sweep ops have no CPU / eager fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
-                 + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER)
+                 + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER
+                 + ADDED_WITHIN_ABI_REGISTRATION)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

@@ -1,0 +1,111 @@
+"""Registration of a point cloud to another by trimmed ICP on the device (csrc/registration.hip; definition in include/dvmvs_hip.h):
+plain functions over the C ABI and the ops package's workspace and launch plumbing.  Inference-time geometry only: nothing here is
+registered under ``torch.ops.dvmvs`` and nothing needs autograd."""
+import ctypes
+from typing import Optional
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from dvmvs.hip import _capi
+from dvmvs.hip.ops import _workspace
+from dvmvs.hip.ops._common import check_tensors, launch, out_or_new, ptr
+
+STATUS_NAMES = ("running", "converged", "too few correspondences", "iteration limit")
+STATUS_RUNNING, STATUS_CONVERGED, STATUS_TOO_FEW, STATUS_LIMIT = range(4)
+MAX_ITERATIONS = 1024
+# the head of the state block in 8-byte words (include/dvmvs_hip.h): T | iterations | status | moments, then three arrays per iteration
+_WORD_ITERATIONS, _WORD_STATUS, _WORD_MOMENTS, _HEAD_WORDS = 16, 17, 18, 36
+
+
+def icp_workspace(device, N, max_iterations):
+    """A state block for one registration of ``N`` source points over at most ``max_iterations`` iterations: a float64 device tensor of
+    ``dvmvs_icp_workspace_bytes(N, max_iterations)`` bytes, uninitialised (the call writes what it reads).  It is a FRESH block, not a
+    per-device one: the transform and the record that ``icp`` returns are views of it."""
+    N, max_iterations = int(N), int(max_iterations)
+    nbytes = _capi.lib().dvmvs_icp_workspace_bytes(N, max_iterations)
+    if nbytes == 0:
+        raise ValueError(f"dvmvs::icp: {N} points over {max_iterations} iterations are outside what the kernels take (1 .. 2^28 points, "
+                         f"1 .. {MAX_ITERATIONS} iterations)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def _cloud(name, label, t, device=None):
+    check_tensors(name, t, label=label, shape=(None, 3), device=device)
+    if t.shape[0] < 1:
+        raise ValueError(f"dvmvs::{name}: {label} is empty")
+    return t.contiguous()
+
+
+def _host_matrix(name, init):
+    if init is None:
+        return None
+    if torch.is_tensor(init):
+        if init.device.type != "cpu":
+            raise ValueError(f"dvmvs::{name}: init is a HOST 4x4 (it is read before the call returns), got a tensor on {init.device}")
+        init = init.detach().numpy()
+    init = np.ascontiguousarray(init, dtype=np.float64)
+    if init.shape != (4, 4) or not np.isfinite(init).all():
+        raise ValueError(f"dvmvs::{name}: init must be a finite 4x4 matrix, got shape {init.shape}")
+    return init
+
+
+def icp(source: Tensor, target: Tensor, max_distance: float, init=None, max_iterations: int = 30, with_scale: bool = False,
+        tolerance: float = 1e-6, grid: Optional[Tensor] = None):
+    """Registers ``source`` (float32 [N,3]) to ``target`` (float32 [M,3], both on one GPU, finite) by trimmed ICP: returns ``(T, info)``,
+    ``T`` a float64 [4,4] DEVICE tensor that takes source coordinates into the target's frame (rigid; with ``with_scale`` a similarity),
+    ``info`` a dict of DEVICE tensors: ``iterations`` and ``status`` (int64 scalars; ``STATUS_NAMES``), ``inliers`` (int64), ``fitness``
+    and ``rmse`` (float64), each [max_iterations] with the entries below ``iterations`` written, and ``moments`` (float64 [18]: the
+    sums of the last recorded iteration).  Nothing is read by the call: ``max_iterations`` iterations are enqueued on the current stream,
+    and those after the loop has stopped find the status on the device and do nothing.  A pair is an inlier when its distance is at most
+    ``max_distance`` (``inf`` keeps all); the loop stops when RMSE and fitness both change by less than ``tolerance``, with fewer than 3
+    inliers, or at the limit.  ``init``: a HOST 4x4 (array, nested list or CPU tensor) to start from instead of the identity.  ``grid``:
+    the workspace of ``ops.nearest_build(target)`` when the caller has it (it is not changed).  The arithmetic, including the order of
+    every sum, is fixed (include/dvmvs_hip.h): ``dvmvs.errors.register_points`` gives the same bits."""
+    from dvmvs.hip.ops import reconstruction
+    source = _cloud("icp", "source", source)
+    dev = source.device
+    target = _cloud("icp", "target", target, dev)
+    N, M = int(source.shape[0]), int(target.shape[0])
+    max_distance, tolerance, max_iterations = float(max_distance), float(tolerance), int(max_iterations)
+    if not max_distance > 0.0 or not tolerance >= 0.0:
+        raise ValueError(f"dvmvs::icp: max_distance must be positive and tolerance not negative (neither NaN), got {max_distance}, {tolerance}")
+    if not 1 <= max_iterations <= MAX_ITERATIONS:
+        raise ValueError(f"dvmvs::icp: max_iterations must be in 1 .. {MAX_ITERATIONS}, got {max_iterations}")
+    init = _host_matrix("icp", init)
+    if grid is None:
+        grid = reconstruction.nearest_build(target)
+    else:
+        check_tensors("icp", grid, dtype=torch.uint8, label="grid", device=dev, contiguous=True)
+        if grid.numel() < _capi.lib().dvmvs_nearest_workspace_bytes(M):
+            raise ValueError(f"dvmvs::icp: grid is smaller than the workspace of a {M}-point target")
+    scratch = _workspace.grown("nearest_query", dev, _capi.lib().dvmvs_nearest_query_workspace_bytes(N, M), torch.uint8)
+    state = icp_workspace(dev, N, max_iterations)
+    init_ptr = None if init is None else init.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    launch("dvmvs_icp_fwd", dev, ptr(source), N, ptr(target), M, ptr(grid), ptr(scratch), scratch.numel(), max_distance, int(bool(with_scale)),
+           max_iterations, tolerance, init_ptr, ptr(state), state.numel() * 8)
+    words = state.view(torch.int64)
+    a, b, c = _HEAD_WORDS, _HEAD_WORDS + max_iterations, _HEAD_WORDS + 2 * max_iterations
+    info = {"iterations": words[_WORD_ITERATIONS], "status": words[_WORD_STATUS], "inliers": words[a:b], "fitness": state[b:c],
+            "rmse": state[c:c + max_iterations], "moments": state[_WORD_MOMENTS:_HEAD_WORDS]}
+    return state[:16].view(4, 4), info
+
+
+def transform_points(points: Tensor, T: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``points`` float32 [N,3] moved by ``T`` (float64 [4,4] on the same GPU, e.g. ``icp``'s): every entry of ``T[:3,:4]`` is rounded to
+    float32 and ``p' = ((A00 x + A01 y) + A02 z) + A03`` (and so on) is evaluated in float32 without FMA, as the registration itself
+    moves its points.  ``out``: a contiguous float32 [N,3] tensor, which may be ``points``; it is returned.  One launch, no host read."""
+    check_tensors("transform_points", points, label="points", shape=(None, 3))
+    dev = points.device
+    check_tensors("transform_points", T, dtype=torch.float64, label="T", shape=(4, 4), device=dev)
+    if out is not None and out is not points:
+        check_tensors("transform_points", out)
+    if out is points and not points.is_contiguous():
+        raise ValueError("dvmvs::transform_points: in place needs a contiguous tensor")
+    src = points.contiguous()
+    N = int(src.shape[0])
+    out = out_or_new("transform_points", out, (N, 3), torch.float32, dev)
+    if N > 0:
+        launch("dvmvs_transform_points_fwd", dev, ptr(src), N, ptr(T.contiguous()), ptr(out))
+    return out

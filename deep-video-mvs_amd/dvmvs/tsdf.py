@@ -329,7 +329,8 @@ class TSDFVolume:
         verts, faces = self.mesh_tensors()
         return prepare_points_device(verts, faces, sample_density, voxel)
 
-    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None):
+    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None,
+                      align_distance=None, align_scale=False, return_transform=False):
         """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
         DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
         ``dvmvs.errors.compute_reconstruction_errors_device`` without a download.  ``reference``: another ``TSDFVolume``, [M,3] points as a
@@ -348,8 +349,22 @@ class TSDFVolume:
         reference, which must then be a mesh (a pair, or a ``TSDFVolume``), is first restricted by ``visible_mesh`` to the faces those views
         observed, so that surface the sequence never faced does not count against completeness and recall.  It needs ``sample_density``:
         the vertices of a culled face set would still include those that no kept face uses.  ``ValueError`` otherwise, and for a bare
-        point set.  With ``return_sizes`` a third entry ``(kept faces, all faces)`` of the reference is returned."""
-        from dvmvs.errors import compute_reconstruction_errors_device, prepare_points_device
+        point set.  With ``return_sizes`` a third entry ``(kept faces, all faces)`` of the reference is returned.
+
+        ``align_distance`` (metres): before it is scored, the prediction's point set is registered to the reference's by trimmed ICP
+        with that inlier distance and moved by the result (``dvmvs.hip.registration.icp``; ``dvmvs.errors.register_points`` is the host
+        definition), so that a residual pose offset does not decide the score; ``align_scale`` lets the registration also find a scale.
+        Nothing is read by the host.  ``return_transform``: the transform, a float64 [4,4] DEVICE tensor that takes this volume's
+        coordinates into the reference's, comes back as the LAST entry of the returned tuple."""
+        return self._score_against(reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
+                                   return_transform)[0]
+
+    def _score_against(self, reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
+                       return_transform):
+        """``score_against``: ``(what it returns, the registration's record or None)``; the record is ``dvmvs.hip.registration.icp``'s
+        ``info`` (device tensors)."""
+        from dvmvs.errors import _check_alignment, _score_device, prepare_points_device
+        _check_alignment("score_against", align_distance, align_scale, None, return_transform)
         prepare = sample_density is not None or voxel is not None
         if visible_from is not None:
             if sample_density is None:
@@ -384,11 +399,13 @@ class TSDFVolume:
             pred = self.vertices()
         if pred.shape[0] == 0 or gt.shape[0] == 0:
             raise ValueError(f"score_against: a surface without a vertex cannot be scored ({pred.shape[0]} predicted, {gt.shape[0]} reference)")
-        row = compute_reconstruction_errors_device(pred, gt.contiguous(), threshold)
-        if not return_sizes:
-            return row
-        sizes = (int(pred.shape[0]), int(gt.shape[0]))
-        return (row, sizes) if face_counts is None else (row, sizes, face_counts)
+        row, transform, info = _score_device(pred, gt.contiguous(), threshold, None, None, None, None, None, align_distance, align_scale, None)
+        result = (row,)
+        if return_sizes:
+            result += ((int(pred.shape[0]), int(gt.shape[0])),) + (() if face_counts is None else (face_counts,))
+        if return_transform:
+            result += (transform,)
+        return (result[0] if len(result) == 1 else result), info
 
 
 class TSDFFusion:
@@ -739,7 +756,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False,
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
-        evaluate_3d_visible=False, evaluate_3d_min_views=1):
+        evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, groundtruth_transform=None):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -772,6 +789,15 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     parts of a scan that the camera never faced do not count against completeness and recall.  ``_errors3d.npz`` then also holds
     ``visible_faces`` and ``total_faces``.
 
+    ``evaluate_3d_align`` (metres; needs ``evaluate_3d``): the system's point set is registered to the ground truth's by trimmed ICP with
+    that inlier distance before it is scored (``TSDFVolume.score_against(align_distance=...)``), ``evaluate_3d_align_scale`` (needs
+    ``evaluate_3d_align``) with a scale.  ``_errors3d.npz`` then also holds ``transform`` float64 [4,4] (system -> ground truth),
+    ``align_iterations``, ``align_status`` (an index of ``dvmvs.errors.REGISTRATION_STATUS``), ``align_fitness`` and ``align_rmse`` (of the
+    last recorded iteration); they come down with the row, in the one download.  ``groundtruth_transform`` (needs
+    ``groundtruth_mesh``): a text file of 16 numbers, the 4x4 that takes the mesh's frame into the dataset's world frame, applied to the
+    mesh's vertices (in float64, rounded once) when the mesh is read, before visibility culling and sampling.  Without these flags the
+    files are what they are without them, byte for byte.
+
     ``filter_consistency``: after the masks above, the keyframe predictions go up once and are filtered by multi-view geometric consistency
     in one launch (``dvmvs.consistency.filter_depths``): a pixel is kept, with its own depth, where at least ``consistency_views`` of the
     ``consistency_sources`` keyframes nearest to it in keyframe order (never across a "TRACKING LOST" line) agree within
@@ -793,6 +819,14 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         raise ValueError("evaluate_3d_min_views says how evaluate_3d_visible culls: it needs evaluate_3d_visible")
     if int(evaluate_3d_min_views) < 1:
         raise ValueError(f"evaluate_3d_min_views must be at least 1, got {evaluate_3d_min_views}")
+    if evaluate_3d_align is not None and not evaluate_3d:
+        raise ValueError("evaluate_3d_align registers the surface that evaluate_3d scores: it needs evaluate_3d")
+    if evaluate_3d_align_scale and evaluate_3d_align is None:
+        raise ValueError("evaluate_3d_align_scale says how evaluate_3d_align registers: it needs evaluate_3d_align")
+    if groundtruth_transform is not None and groundtruth_mesh is None:
+        raise ValueError("groundtruth_transform moves the mesh of groundtruth_mesh: it needs groundtruth_mesh")
+    if evaluate_3d_align is not None and not float(evaluate_3d_align) > 0.0:
+        raise ValueError(f"evaluate_3d_align must be a positive distance, got {evaluate_3d_align}")
     fuse_groundtruth_3d = evaluate_3d and groundtruth_mesh is None
     from dvmvs.dataset_loader import PreprocessImage, load_depth_png, load_image, load_image_u8, resize_nearest
     if device_preprocess:
@@ -880,7 +914,10 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
             groundtruth_vertices = volume.mesh_tensors() if protocol_3d else volume.vertices()
         del volume
     if evaluate_3d and groundtruth_mesh is not None:
-        groundtruth_vertices = tuple(torch.as_tensor(a, device=device) for a in TSDFFusion.meshread(groundtruth_mesh))
+        mesh_verts, mesh_faces = TSDFFusion.meshread(groundtruth_mesh)
+        if groundtruth_transform is not None:
+            mesh_verts = apply_transform(mesh_verts, load_transform(groundtruth_transform))
+        groundtruth_vertices = tuple(torch.as_tensor(a, device=device) for a in (mesh_verts, mesh_faces))
     volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
     system_mesh_name = _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name, dataset_name, scene_name)
     TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K, system_mesh_name, save_progressive)
@@ -895,9 +932,9 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
                     raise ValueError("evaluate_3d_visible: the scene has no keyframe to take the visibility from")
                 visible_from = (scaled_K, np.stack(keyframe_poses), prediction_height, prediction_width, int(evaluate_3d_min_views))
             _evaluate_3d_protocol(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_density, evaluate_3d_voxel,
-                                  visible_from)
+                                  visible_from, evaluate_3d_align, evaluate_3d_align_scale)
         else:
-            _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name)
+            _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_align, evaluate_3d_align_scale)
     if render_keyframes:
         _render_keyframes(volume, keyframe_poses, keyframe_image_filenames, scaled_K, preprocessor, prediction_height, prediction_width,
                           scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
@@ -922,30 +959,68 @@ def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sour
     return list(kept.cpu().numpy()), cloud
 
 
-def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name):
+def load_transform(filename):
+    """The float64 4x4 of a ``groundtruth_transform`` file: 16 numbers separated by white space, row by row, on any number of lines."""
+    with open(filename) as f:
+        words = f.read().split()
+    try:
+        values = np.array([float(w) for w in words], dtype=np.float64)
+    except ValueError:
+        values = np.zeros(0)
+    if values.size != 16 or not np.isfinite(values).all():
+        raise ValueError(f"groundtruth_transform: {filename} must hold the 16 finite numbers of a 4x4 matrix")
+    return values.reshape(4, 4)
+
+
+def apply_transform(verts, transform):
+    """Mesh vertices [V,3] moved by a float64 4x4 (affine: its last row is not used), evaluated in float64 and rounded to float32 once."""
+    verts = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    return (verts @ transform[:3, :3].T + transform[:3, 3]).astype(np.float32)
+
+
+def _aligned_score(volume, align_distance, align_scale, **score):
+    """``score_against`` with its row on the host; with ``align_distance`` also the entries ``_errors3d.npz`` gains.  Row, transform and
+    record come down as ONE float64 tensor (a float32 row is exact in float64)."""
+    if align_distance is None:
+        result = volume.score_against(**score)
+        return (result[0].cpu().numpy(),) + tuple(result[1:]) + ({},)
+    score = {"return_sizes": False, "sample_density": None, "voxel": None, "visible_from": None, **score}
+    result, info = volume._score_against(align_distance=align_distance, align_scale=align_scale, return_transform=True, **score)
+    last = (info["iterations"] - 1).clamp(min=0).reshape(1)      # (selected on the device: indexing with a 0-d tensor would read it)
+    down = torch.cat([result[0].double(), result[-1].reshape(-1), info["iterations"].double().reshape(1), info["status"].double().reshape(1),
+                      info["fitness"].index_select(0, last), info["rmse"].index_select(0, last)]).cpu().numpy()
+    extra = {"transform": down[6:22].reshape(4, 4), "align_iterations": np.int64(down[22]), "align_status": np.int64(down[23]),
+             "align_fitness": np.float64(down[24]), "align_rmse": np.float64(down[25])}
+    from dvmvs.errors import REGISTRATION_STATUS
+    print("Registered the surface to the ground truth within {} m{}: {} after {} iterations, fitness {:.4f}, rmse {:.5f} m".format(
+        align_distance, " with scale" if align_scale else "", REGISTRATION_STATUS[int(down[23])], int(down[22]), down[24], down[25]))
+    return (down[:6].astype(np.float32),) + tuple(result[1:-1]) + (extra,)
+
+
+def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name, align_distance=None, align_scale=False):
     """Scores the fused surface against the ground-truth vertices on the device; one row comes down, is printed and saved."""
     from dvmvs.errors import RECONSTRUCTION_METRICS
-    row, sizes = volume.score_against(groundtruth_vertices, threshold, return_sizes=True)
-    row = row.cpu().numpy()
+    row, sizes, aligned = _aligned_score(volume, align_distance, align_scale, reference=groundtruth_vertices, threshold=threshold,
+                                         return_sizes=True)
     print("3-D metrics at {} m over {} predicted and {} ground-truth vertices: {}".format(
         threshold, sizes[0], sizes[1], ", ".join(f"{n} {v:.4f}" for n, v in zip(RECONSTRUCTION_METRICS, row))))
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
-                        counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold))
+                        counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold), **aligned)
 
 
-def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample_density, voxel, visible_from=None):
+def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample_density, voxel, visible_from=None, align_distance=None,
+                          align_scale=False):
     """``_evaluate_3d`` against a ground-truth mesh (device verts and faces), with face sampling and / or voxel down-sampling of both sides;
     with ``visible_from`` (``TSDFVolume.score_against``) against the part of the mesh those views observed."""
     from dvmvs.errors import RECONSTRUCTION_METRICS
     extra = {}
+    score = dict(reference=groundtruth_mesh, threshold=threshold, return_sizes=True, sample_density=sample_density, voxel=voxel)
     if visible_from is None:
-        row, points = volume.score_against(groundtruth_mesh, threshold, return_sizes=True, sample_density=sample_density, voxel=voxel)
+        row, points, aligned = _aligned_score(volume, align_distance, align_scale, **score)
     else:
-        row, points, kept = volume.score_against(groundtruth_mesh, threshold, return_sizes=True, sample_density=sample_density, voxel=voxel,
-                                                 visible_from=visible_from)
+        row, points, kept, aligned = _aligned_score(volume, align_distance, align_scale, visible_from=visible_from, **score)
         print("Ground truth restricted to what {} keyframes saw: {} of {} faces".format(len(visible_from[1]), kept[0], kept[1]))
         extra = {"visible_faces": np.int64(kept[0]), "total_faces": np.int64(kept[1])}
-    row = row.cpu().numpy()
     sizes = (int(volume.vertices().shape[0]), int(groundtruth_mesh[0].shape[0]))
     print("3-D metrics at {} m over {} predicted and {} ground-truth points (density {}, voxel {}; {} and {} vertices): {}".format(
         threshold, points[0], points[1], sample_density, voxel, sizes[0], sizes[1],
@@ -953,7 +1028,7 @@ def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
                         counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold),
                         sample_density=np.float64(np.nan if sample_density is None else sample_density),
-                        voxel=np.float64(np.nan if voxel is None else voxel), points=np.array(points, dtype=np.int64), **extra)
+                        voxel=np.float64(np.nan if voxel is None else voxel), points=np.array(points, dtype=np.int64), **extra, **aligned)
 
 
 def _render_keyframes(volume, poses, image_filenames, K, preprocessor, height, width, scene_folder, system_name, scene_name, save_folder):
@@ -1012,6 +1087,12 @@ def build_parser():
                              "mesh that the fused keyframes saw (the mesh is rasterised from their views on the device)")
     parser.add_argument("--evaluate_3d_min_views", default=1, type=int,
                         help="with --evaluate_3d_visible: keyframes that must see each vertex of a ground-truth face for it to be kept")
+    parser.add_argument("--evaluate_3d_align", default=None, type=float,
+                        help="with --evaluate_3d: register the system's point set to the ground truth's by trimmed ICP with this inlier "
+                             "distance, metres, before it is scored (on the device)")
+    parser.add_argument("--evaluate_3d_align_scale", action="store_true", help="with --evaluate_3d_align: the registration also finds a scale")
+    parser.add_argument("--groundtruth_transform", default=None, type=str,
+                        help="with --groundtruth_mesh: a text file of 16 numbers, the 4x4 that takes the mesh's frame into the dataset's world frame")
     parser.add_argument("--filter_consistency", action="store_true",
                         help="fuse only the pixels that neighbouring keyframes agree on (multi-view geometric consistency, on the device); "
                              "files are written under <system>+consistent")

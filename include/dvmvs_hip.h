@@ -59,7 +59,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_surface_sample_* and dvmvs_voxel_* (point sets for the 3-D metrics: area-weighted samples of a triangle
  * mesh, one point per occupied voxel of a cloud); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_mesh_raster_* and dvmvs_mesh_visibility_fwd (rasterising a triangle mesh to depth maps, and the vertices
- * that depth maps show); no earlier signature changed, the number stays 11 by the same rule. */
+ * that depth maps show); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_icp_* and dvmvs_transform_points_fwd (registering a point cloud to another by trimmed ICP on the device);
+ * no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -891,6 +893,73 @@ int dvmvs_mesh_raster_fwd(const float* verts, long long V, const int* faces, lon
 int dvmvs_mesh_visibility_fwd(const float* verts, long long V, const float* depth, const float* cam_intr, const float* cam_w2c,
                               int n_views, int im_h, int im_w, float near, float relative, float absolute, int* count,
                               dvmvs_stream_t stream);
+
+/*
+ * Registration of a point cloud to another by trimmed ICP (ABI 11, later addition; csrc/registration.hip).  The reference project has
+ * nothing for this: the definition is this project's own (the step the Tanks-and-Temples evaluation takes before precision and recall).
+ * The whole loop is enqueued by one call; no host read happens inside it, and the result stays on the device.
+ *   source [N,3], target [M,3]   fp32, contiguous, 4-byte aligned, finite (not checked)
+ *   grid_workspace     the target's grid: dvmvs_nearest_build(target, M, ...) into dvmvs_nearest_workspace_bytes(M) bytes
+ *   query_workspace    dvmvs_nearest_query_workspace_bytes(N, M) bytes, scratch of the loop's nearest queries
+ *   state              dvmvs_icp_workspace_bytes(N, max_iterations) bytes on the device, 16-byte aligned, any contents.  In 8-byte words:
+ *                        [0, 16)   T, fp64 4x4 row-major: takes source coordinates into the target's frame
+ *                        [16]      iterations (int64): the iterations that were recorded below
+ *                        [17]      status (int64): 0 running, 1 converged, 2 too few correspondences, 3 iteration limit
+ *                        [18, 36)  the moments of the last recorded iteration, fp64: n | sum p' [3] | sum q [3] | sum p' q^T [9, row-major:
+ *                                  entry 3 a + b is sum p'_a q_b] | sum |p'|^2 | sum d^2
+ *                        [36, 36 + I), [36 + I, 36 + 2 I), [36 + 2 I, 36 + 3 I) with I = max_iterations: per iteration the inlier count
+ *                                  (int64), the fitness and the RMSE (fp64); entries at and after `iterations` are not written
+ *                      and, from the next multiple of 256 bytes on, the loop's scratch: p' [N,3] fp32, d [N] fp32, j [N] int32 and the
+ *                      partial sums [ceil(N / 1024), 18] fp64 (each rounded up to 256 bytes).
+ *   init_host          16 doubles on the HOST (row-major 4x4, read before the call returns), or NULL for the identity
+ * Iteration k = 0, 1, ... with T_0 = init:
+ *   1. A = every entry of T_k[:3,:4] rounded to fp32; p' = ((A00 x + A01 y) + A02 z) + A03 and likewise for y and z: every operation
+ *      rounded to fp32, no FMA contraction.
+ *   2. (d_i, j_i) = dvmvs_nearest_distance_fwd of p'_i in target (the distance and the smallest index); q_i = target[j_i].
+ *   3. Pair i is an inlier when d_i <= max_distance, compared in fp32 (+inf keeps every pair).
+ *   4. The 18 moments above over the inliers, in fp64 from the fp32 values: the products p'_a q_b, p'_a p'_a and d d are exact,
+ *      |p'|^2 = (xx + yy) + zz.  Order of the additions, a function of N alone: the points are cut into consecutive blocks of 1024; in a
+ *      block, "thread" t of 256 adds the terms of its points t, t + 256, t + 512, t + 768 in that order from 0.0; the threads of each
+ *      group of 64 are combined by the xor butterfly (v[l] += v[l ^ m] for m = 32, 16, 8, 4, 2, 1), the 4 groups are added in order.
+ *      The block sums b = 0, 1, ... are then added by 64 "lanes": lane l adds b = l, l + 64, ... in order from 0.0, then the same
+ *      butterfly.  A trimmed point is skipped, which equals adding an exact +0.0.
+ *   5. n = the count, rmse_k = sqrt(sum d^2 / n) (0 when n = 0), fitness_k = n / N: recorded at entry k; iterations = k + 1.  They
+ *      describe T_k.  If n < 3: status 2, T stays, stop.  Else if k >= 1 and |rmse_k - rmse_{k-1}| < tolerance and
+ *      |fitness_k - fitness_{k-1}| < tolerance: status 1, T stays, stop.
+ *   6. Solve, fp64 with +, -, *, / and sqrt only, nothing contracted: pbar = sum p' / n, qbar = sum q / n,
+ *      S_ab = sum p'_a q_b - (sum p'_a * sum q_b) / n.  Horn's symmetric matrix
+ *        [ (Sxx+Syy)+Szz  Syz-Szy        Szx-Sxz        Sxy-Syx       ]
+ *        [                (Sxx-Syy)-Szz  Sxy+Syx        Szx+Sxz       ]
+ *        [                               (Syy-Sxx)-Szz  Syz+Szy       ]
+ *        [                                              (Szz-Sxx)-Syy ]
+ *      is diagonalised by cyclic Jacobi sweeps over (p, q) = (0,1), (0,2), (0,3), (1,2), (1,3), (2,3): a zero A_pq is skipped; otherwise
+ *      theta = (A_qq - A_pp) / (2 A_pq), t = +-1 / (|theta| + sqrt(theta theta + 1)) with the sign of theta (+ for 0),
+ *      c = 1 / sqrt(t t + 1), s = t c; for every k the columns A_kp <- c A_kp - s A_kq, A_kq <- s A_kp + c A_kq (old values on the right),
+ *      then the rows A_pk, A_qk by the same formulas, then A_pq = A_qp = 0, then the columns p, q of V (V starts as the identity) like
+ *      A's.  Before each sweep: stop when every off-diagonal is exactly zero; at most 16 sweeps.  The quaternion (w, x, y, z) is the
+ *      column of V of the largest diagonal entry (the lowest index on a tie), divided by sqrt(((ww + xx) + yy) + zz) and negated when
+ *      w < 0.  R = [1-2(yy+zz) 2(xy-wz) 2(xz+wy); 2(xy+wz) 1-2(xx+zz) 2(yz-wx); 2(xz-wy) 2(yz+wx) 1-2(xx+yy)]: never a reflection.
+ *      s = 1, or with with_scale s = (sum over a, b in row-major order of R_ab S_ba, from 0.0) / (sum |p'|^2 - ((sx sx + sy sy) + sz sz) / n)
+ *      with (sx, sy, sz) = sum p' (Umeyama); a denominator that is not > 0: status 2, T stays, stop.  M = s R,
+ *      t_a = qbar_a - ((M_a0 pbar_0 + M_a1 pbar_1) + M_a2 pbar_2), and for a < 3
+ *      T_{k+1}[a][c] = ((M_a0 T_k[0][c] + M_a1 T_k[1][c]) + M_a2 T_k[2][c]) + t_a T_k[3][c]; row 3 stays.  If k + 1 = max_iterations:
+ *      status 3.
+ * The transform, moments and solve kernels of an iteration read the status on the device and do nothing once it is not 0 (the nearest-point
+ * query between them cannot, and repeats a query that nothing reads), so a larger max_iterations cannot change
+ * a result that stopped earlier.  The result is bit-identical run to run, on any stream, for any alignment of the inputs.
+ * dvmvs_transform_points_fwd: out[i] = step 1 applied to points[i] with T (16 doubles on the DEVICE, 8-byte aligned); out may be points.
+ * dvmvs_icp_workspace_bytes: host only; 0 for N <= 0 or above 2^28 and for max_iterations outside [1, 1024]; non-decreasing in N.
+ * Returns DVMVS_EINVAL for a null or misaligned pointer (fp32: 4 bytes; workspaces and state: 16; T: 8), N or M < 1, max_iterations < 1,
+ * with_scale not 0 / 1, a max_distance that is NaN or <= 0, a tolerance that is NaN or negative, an init that is not finite, a
+ * state or query workspace that is too small; DVMVS_EUNSUPPORTED above 2^28 points or 1024 iterations.  Nothing is enqueued when a negative
+ * code is returned: these checks cover everything the nearest-point launcher inside the loop refuses, so from inside the loop only a
+ * positive hipError_t of a launch can come back, after earlier launches of the call have been enqueued.
+ */
+size_t dvmvs_icp_workspace_bytes(long long N, int max_iterations);
+int dvmvs_icp_fwd(const float* source, long long N, const float* target, long long M, const void* grid_workspace, void* query_workspace,
+                  size_t query_workspace_bytes, float max_distance, int with_scale, int max_iterations, double tolerance,
+                  const double* init_host, void* state, size_t state_bytes, dvmvs_stream_t stream);
+int dvmvs_transform_points_fwd(const float* points, long long N, const double* T, float* out, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
