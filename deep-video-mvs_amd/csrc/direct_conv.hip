@@ -543,6 +543,12 @@ extern "C" int dvmvs_direct_conv_tile(int B, int C_in, int H, int W, int C_out, 
   return id == 0 ? 0 : dvmvs::kDcShapes[id - 1].NT;
 }
 
+// the workgroup shape direct_conv_choose picks for the problem: 0 = not taken, else the id 1..4 of the comment above kDcShapes (with the
+// kernel size and the stride that names the kernel a launch runs; host only)
+extern "C" int dvmvs_direct_conv_shape(int B, int C_in, int H, int W, int C_out, int kernel_size, int stride) {
+  return dvmvs::direct_conv_choose(B, C_in, C_out, H, W, kernel_size, stride);
+}
+
 extern "C" size_t dvmvs_direct_conv_packed_bytes(int C_out, int C_in, int kernel_size, int n_tile) {
   if (C_out <= 0 || C_in <= 0 || (n_tile != 1 && n_tile != 2) || C_out % (16 * n_tile) != 0 || (kernel_size != 3 && kernel_size != 5)) return 0;
   const size_t Q = (n_tile * kernel_size + 3) / 4;

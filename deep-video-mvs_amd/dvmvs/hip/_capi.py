@@ -69,6 +69,7 @@ SIGNATURES = {
     "dvmvs_bottleneck_conv_fwd": (_c_int, [_c_fp, _c_fp, _c_fp] + [_c_int] * 6 + [_c_stream]),
     "dvmvs_bottleneck_conv_up2x_fwd": (_c_int, [_c_fp, _c_fp, _c_fp] + [_c_int] * 5 + [_c_stream]),
     "dvmvs_direct_conv_tile": (_c_int, [_c_int] * 7),
+    "dvmvs_direct_conv_shape": (_c_int, [_c_int] * 7),
     "dvmvs_direct_conv_packed_bytes": (ctypes.c_size_t, [_c_int] * 4),
     "dvmvs_direct_conv_pack": (_c_int, [_c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_stream]),
     "dvmvs_direct_conv_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_int, _c_fp, _c_fp, ctypes.c_longlong] + [_c_int] * 8 + [_c_stream]),
@@ -172,6 +173,8 @@ ADDED_WITHIN_ABI_MESH_RASTER = ("dvmvs_mesh_raster_workspace_bytes", "dvmvs_mesh
                                 "dvmvs_mesh_visibility_fwd")
 # ... and the ninth (registering a point cloud to another by trimmed ICP)
 ADDED_WITHIN_ABI_REGISTRATION = ("dvmvs_icp_workspace_bytes", "dvmvs_icp_fwd", "dvmvs_transform_points_fwd")
+# ... and the tenth (which workgroup shape of the direct convolution a problem runs with)
+ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE = ("dvmvs_direct_conv_shape",)
 
 _lib = None
 _lock = threading.Lock()
@@ -192,7 +195,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
                  + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER
-                 + ADDED_WITHIN_ABI_REGISTRATION)
+                 + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

@@ -25,7 +25,7 @@ from dvmvs.hip.ops.frame import (ACTIVATION_SIGMOID_TO_DEPTH, ACTIVATIONS, RESID
                                  bias_act_, bias_act_into, bottleneck_conv_into, bottleneck_conv_pack, bottleneck_conv_splits,
                                  conv_bias_act_into, conv_head_into, copy_batch, depth_reproject, depth_reproject_estimate_into,
                                  depth_reproject_lowres, depth_reproject_lowres_into, depthwise_conv, depthwise_conv_bwd, depthwise_conv_train,
-                                 direct_conv_into, direct_conv_pack, direct_conv_tile, hidden_warp, hidden_warp_into, lstm_gates, lstm_gates_into,
+                                 direct_conv_into, direct_conv_pack, direct_conv_shape, direct_conv_tile, hidden_warp, hidden_warp_into, lstm_gates, lstm_gates_into,
                                  lstm_gates_partials_into, partial_sums_bias_act_into, pointwise_conv_into, pointwise_conv_pack,
                                  pointwise_conv_supported, upsample2x, upsample2x_bwd, upsample2x_into, upsample2x_pair_into)
 from dvmvs.hip.ops.reconstruction import (CONSISTENCY_MAX_SOURCES, TSDF_FUSE_TILE, consistency_matrices, depth_consistency, depth_errors,  # noqa: F401

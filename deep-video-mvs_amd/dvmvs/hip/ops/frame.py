@@ -479,6 +479,12 @@ def direct_conv_tile(B: int, C_in: int, H: int, W: int, C_out: int, kernel_size:
     return _capi.lib().dvmvs_direct_conv_tile(int(B), int(C_in), int(H), int(W), int(C_out), int(kernel_size), int(stride))
 
 
+def direct_conv_shape(B: int, C_in: int, H: int, W: int, C_out: int, kernel_size: int, stride: int) -> int:
+    """0 when dvmvs_direct_conv_fwd does not take the problem; else the id (1..4) of the workgroup shape it runs with, which together with
+    the kernel size and the stride names the compiled kernel (ids 1 and 2 pack for ``direct_conv_tile`` 2, ids 3 and 4 for 1)."""
+    return _capi.lib().dvmvs_direct_conv_shape(int(B), int(C_in), int(H), int(W), int(C_out), int(kernel_size), int(stride))
+
+
 def direct_conv_pack(weight: Tensor, n_tile: int) -> Tensor:
     """[C_out, C_in, k, k] convolution weights re-packed once into the MFMA B-operand order the kernel streams."""
     check_tensors("direct_conv_pack", weight)

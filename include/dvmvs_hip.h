@@ -61,6 +61,8 @@ extern "C" {
  * ABI 11, later addition: dvmvs_mesh_raster_* and dvmvs_mesh_visibility_fwd (rasterising a triangle mesh to depth maps, and the vertices
  * that depth maps show); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_icp_* and dvmvs_transform_points_fwd (registering a point cloud to another by trimmed ICP on the device);
+ * no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_direct_conv_shape (which workgroup shape of the direct convolution a problem runs with; a host query);
  * no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
@@ -331,6 +333,10 @@ int dvmvs_lstm_gates_partials_fwd(const float* conv_partials, int n_partials, co
  *   dvmvs_direct_conv_tile          0 when the kernel does not take the problem (output width not a multiple of 40, C_out % 16 != 0,
  *                                   other kernel sizes / strides: the caller keeps its library convolution); else the number of
  *                                   16-channel output tiles per wave (1 or 2) the weights have to be packed for
+ *   dvmvs_direct_conv_shape         (ABI 11, later addition) which of the kernel's workgroup shapes the problem runs with: 0 when
+ *                                   dvmvs_direct_conv_tile is 0; 1 = 4 rows x 80 columns x 32 channels per workgroup (tile 2),
+ *                                   2 = 2 x 40 x 32 (tile 2), 3 = 1 x 80 x 16 (tile 1), 4 = 2 x 40 x 16 (tile 1).  With kernel_size and
+ *                                   stride it names the one of the 16 compiled kernels that a launch runs; host only, for tests and tools
  *   dvmvs_direct_conv_pack          weight [C_out,C_in,k,k] -> packed (dvmvs_direct_conv_packed_bytes), once per (layer, n_tile)
  *   dvmvs_direct_conv_fwd           x [B,C_in,H,W] (batch item b at x + b*x_batch_stride, 0 = dense) -> dst [B,C_out,H/stride,W/stride]
  *                                   (batch item b at dst + b*dst_batch_stride, 0 = dense: a channel slice of a concatenation buffer);
@@ -341,6 +347,7 @@ int dvmvs_lstm_gates_partials_fwd(const float* conv_partials, int n_partials, co
  *                                   convolution output when also activation == 0); activation / p0 / p1 as dvmvs_bias_act_fwd
  */
 int dvmvs_direct_conv_tile(int B, int C_in, int H, int W, int C_out, int kernel_size, int stride);
+int dvmvs_direct_conv_shape(int B, int C_in, int H, int W, int C_out, int kernel_size, int stride);
 size_t dvmvs_direct_conv_packed_bytes(int C_out, int C_in, int kernel_size, int n_tile);
 int dvmvs_direct_conv_pack(const float* weight, float* packed, int C_out, int C_in, int kernel_size, int n_tile, dvmvs_stream_t stream);
 int dvmvs_direct_conv_fwd(const float* x, long long x_batch_stride, const float* packed, int n_tile, const float* bias, float* dst,

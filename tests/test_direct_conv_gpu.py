@@ -1,6 +1,8 @@
 """GPU parity of the direct convolution kernel and the depth-head kernel (csrc/direct_conv.hip) against an fp64 convolution: the
-layer shapes of a 320x256 frame (all four workgroup shapes, both kernel sizes, both strides), ragged channel counts, batches,
-channel-slice destinations, and that shapes the kernel does not take are reported as such."""
+layer shapes of a 320x256 frame at batches 1 and 2, ragged channel counts, channel-slice destinations, and that shapes the kernel does
+not take are reported as such.  Of the 16 kernels (workgroup shape id x kernel size x stride, dvmvs_direct_conv_shape) SHAPES at these
+batches runs 11: shape 1 only as (k 5, stride 1), and not (3, k 3, stride 2) or (4, k 5, stride 2); output heights are multiples of the
+tile's.  tests/test_direct_conv_variants_gpu.py runs all 16, with ragged row tiles, and the kernels a frame's layers move to at batch 8."""
 import pytest
 import torch
 import torch.nn.functional as F
