@@ -300,10 +300,20 @@ class TSDFVolume:
     def get_weight_volume(self):
         return self._weight.cpu().numpy()
 
-    def get_mesh(self):
+    def _extract(self, color, clean):
+        """``marching_cubes`` of the volume, with ``clean`` (a ``dvmvs.components.ComponentFilter``) through ``filter_components`` on the
+        device: the components of the welded mesh that the filter does not keep (floaters) are gone before anything else sees it."""
+        mesh = marching_cubes(self._tsdf, 0.0, self._color if color else None, self._vol_origin, self._voxel_size)
+        if clean is not None:
+            from dvmvs.components import filter_components_device
+            mesh = filter_components_device(mesh[0], mesh[1], clean, mesh[2], mesh[3])
+        return mesh
+
+    def get_mesh(self, clean=None):
         """(verts [V,3] float32 in world units, faces [F,3] int32, normals [V,3] float32, colours [V,3] uint8 RGB) of the zero
-        iso-surface, as numpy arrays (run-tsdf-reconstruction.py:334-351); extracted on the device by ``marching_cubes``."""
-        verts, faces, norms, colors = marching_cubes(self._tsdf, 0.0, self._color, self._vol_origin, self._voxel_size)
+        iso-surface, as numpy arrays (run-tsdf-reconstruction.py:334-351); extracted on the device by ``marching_cubes``.  ``clean``: a
+        ``dvmvs.components.ComponentFilter``; the mesh then goes through ``filter_components`` on the device before it is downloaded."""
+        verts, faces, norms, colors = self._extract(True, clean)
         return verts.cpu().numpy(), faces.cpu().numpy(), norms.cpu().numpy(), colors.cpu().numpy()
 
     def get_point_cloud(self):
@@ -311,25 +321,27 @@ class TSDFVolume:
         verts, _, _, colors = self.get_mesh()
         return np.hstack([verts, colors])
 
-    def vertices(self):
+    def vertices(self, clean=None):
         """The vertices of the zero iso-surface (``get_mesh()[0]``) as a float32 [V,3] DEVICE tensor: nothing but ``marching_cubes``'
-        two counts is read by the host."""
-        return marching_cubes(self._tsdf, 0.0, None, self._vol_origin, self._voxel_size)[0]
+        two counts is read by the host (with ``clean``, as ``get_mesh`` takes it, also ``filter_components``' counts)."""
+        return self._extract(False, clean)[0]
 
-    def mesh_tensors(self):
-        """``(verts float32 [V,3], faces int32 [F,3])`` of the zero iso-surface as DEVICE tensors, as ``marching_cubes`` leaves them."""
-        return marching_cubes(self._tsdf, 0.0, None, self._vol_origin, self._voxel_size)[:2]
+    def mesh_tensors(self, clean=None):
+        """``(verts float32 [V,3], faces int32 [F,3])`` of the zero iso-surface as DEVICE tensors, as ``marching_cubes`` leaves them (with
+        ``clean``, as ``get_mesh`` takes it: as ``filter_components`` leaves them)."""
+        return self._extract(False, clean)[:2]
 
-    def surface_points(self, sample_density=None, voxel=None):
+    def surface_points(self, sample_density=None, voxel=None, clean=None):
         """The point set the 3-D metrics take from this volume's surface, as a float32 [N,3] DEVICE tensor: the vertices of the zero
         iso-surface; with ``sample_density`` (points per square metre) instead ``dvmvs.hip.ops.surface_sample`` of its faces; with ``voxel``
         (metres) then ``dvmvs.hip.ops.voxel_downsample`` of that (``dvmvs.errors.prepare_points`` is the host definition of both).  The
-        vertices and faces stay on the device; each step reads its output's size once."""
+        vertices and faces stay on the device; each step reads its output's size once.  ``clean``: as ``get_mesh`` takes it; the points are
+        then those of the cleaned mesh."""
         from dvmvs.errors import prepare_points_device
-        verts, faces = self.mesh_tensors()
+        verts, faces = self.mesh_tensors(clean)
         return prepare_points_device(verts, faces, sample_density, voxel)
 
-    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None,
+    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None, clean=None,
                       align_distance=None, align_scale=False, return_transform=False):
         """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
         DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
@@ -351,16 +363,20 @@ class TSDFVolume:
         the vertices of a culled face set would still include those that no kept face uses.  ``ValueError`` otherwise, and for a bare
         point set.  With ``return_sizes`` a third entry ``(kept faces, all faces)`` of the reference is returned.
 
+        ``clean``: a ``dvmvs.components.ComponentFilter``.  The PREDICTION's mesh, this volume's, goes through
+        ``filter_components`` on the device before its vertices are taken or its faces sampled, so that floaters do not count against
+        accuracy and precision; the reference is never cleaned (a ``TSDFVolume`` reference included).
+
         ``align_distance`` (metres): before it is scored, the prediction's point set is registered to the reference's by trimmed ICP
         with that inlier distance and moved by the result (``dvmvs.hip.registration.icp``; ``dvmvs.errors.register_points`` is the host
         definition), so that a residual pose offset does not decide the score; ``align_scale`` lets the registration also find a scale.
         Nothing is read by the host.  ``return_transform``: the transform, a float64 [4,4] DEVICE tensor that takes this volume's
         coordinates into the reference's, comes back as the LAST entry of the returned tuple."""
         return self._score_against(reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
-                                   return_transform)[0]
+                                   return_transform, clean=clean)[0]
 
     def _score_against(self, reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
-                       return_transform):
+                       return_transform, clean=None):
         """``score_against``: ``(what it returns, the registration's record or None)``; the record is ``dvmvs.hip.registration.icp``'s
         ``info`` (device tensors)."""
         from dvmvs.errors import _check_alignment, _score_device, prepare_points_device
@@ -393,10 +409,10 @@ class TSDFVolume:
         if prepare:
             if gt_faces is not None:
                 gt_faces = torch.as_tensor(gt_faces, device=self.device).to(torch.int32)
-            pred = self.surface_points(sample_density, voxel)
+            pred = self.surface_points(sample_density, voxel, clean=clean)
             gt = prepare_points_device(gt.contiguous(), gt_faces, sample_density, voxel)
         else:
-            pred = self.vertices()
+            pred = self.vertices(clean=clean)
         if pred.shape[0] == 0 or gt.shape[0] == 0:
             raise ValueError(f"score_against: a surface without a vertex cannot be scored ({pred.shape[0]} predicted, {gt.shape[0]} reference)")
         row, transform, info = _score_device(pred, gt.contiguous(), threshold, None, None, None, None, None, align_distance, align_scale, None)
@@ -610,9 +626,10 @@ class TSDFFusion:
             f.write(header + body)
 
     @staticmethod
-    def integrate(tsdf_volume, images, depths, poses, K, mesh_name, save_progressive):
+    def integrate(tsdf_volume, images, depths, poses, K, mesh_name, save_progressive, clean=None):
         """Fuses every (image, depth, pose) with weight 1 and writes ``<mesh_name>_complete.ply`` (with ``save_progressive``,
-        also ``<mesh_name>_frame_<i>.ply`` after each frame), like the reconstruction script (:442-462)."""
+        also ``<mesh_name>_frame_<i>.ply`` after each frame), like the reconstruction script (:442-462).  ``clean`` (a
+        ``dvmvs.components.ComponentFilter``) is handed to every ``get_mesh`` whose mesh is written, the progressive ones included."""
         n = len(images)
         start = time.time()
         for i in range(n):
@@ -620,11 +637,11 @@ class TSDFFusion:
             tsdf_volume.integrate(images[i], depths[i], K, poses[i], obs_weight=1.0)
             if save_progressive:
                 print("Saving for progressive visuals...")
-                TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *tsdf_volume.get_mesh())
+                TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *tsdf_volume.get_mesh(clean=clean))
         torch.cuda.synchronize(tsdf_volume.device)
         print("Average FPS: {:.2f}".format(n / max(time.time() - start, 1e-9)))
         print("Saving mesh to", mesh_name)
-        TSDFFusion.meshwrite(mesh_name + "_complete.ply", *tsdf_volume.get_mesh())
+        TSDFFusion.meshwrite(mesh_name + "_complete.ply", *tsdf_volume.get_mesh(clean=clean))
 
 
 class LiveFusion:
@@ -756,7 +773,8 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False,
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
-        evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, groundtruth_transform=None):
+        evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, groundtruth_transform=None,
+        clean_mesh_area=None, clean_mesh_faces=None, clean_mesh_largest=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -806,7 +824,17 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     and the files of ``evaluate_3d`` and ``render_keyframes`` are written under ``<system_name>+consistent``; the kept share of the valid
     pixels is printed.  ``save_point_cloud`` (needs ``filter_consistency``): also writes ``<mesh name>_pointcloud.ply``, the kept pixels of
     a second call that averages the agreeing depths, as coloured world-space points.  Without these flags the program writes what it
-    writes without them, byte for byte."""
+    writes without them, byte for byte.
+
+    ``clean_mesh_area`` (square metres), ``clean_mesh_faces`` (a count), ``clean_mesh_largest``: the system's mesh goes through
+    ``dvmvs.components.filter_components`` on the device, which removes the connected components (floaters) with less area or fewer faces
+    and, with ``clean_mesh_largest``, all but the largest (``ComponentFilter``).  With any of the three the system's files are written
+    under ``<system_name>+clean`` (after ``+consistent`` when both are given), its ``.ply`` files, the progressive ones included, are the
+    cleaned meshes, and ``evaluate_3d`` scores the cleaned surface; ``_errors3d.npz`` then also holds ``clean_min_area``,
+    ``clean_min_faces``, ``clean_largest`` and ``clean_faces`` int64 [2], the kept and all faces of the system's mesh.  The ground-truth
+    side is never cleaned, and ``render_keyframes`` ray-casts the VOLUME, which cleaning a mesh does not touch: its depth maps are what
+    they are without these flags (under the ``+clean`` name).  Without these flags every file is what it is without them, byte for byte."""
+    clean = _clean_filter(clean_mesh_area, clean_mesh_faces, clean_mesh_largest)
     if save_point_cloud and not filter_consistency:
         raise ValueError("save_point_cloud needs filter_consistency: the point cloud is made of the pixels the filter keeps")
     protocol_3d = evaluate_3d_density is not None or evaluate_3d_voxel is not None or groundtruth_mesh is not None
@@ -898,6 +926,8 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
                 keyframe_predictions, keyframe_images if save_point_cloud else None, keyframe_poses, scaled_K, keyframe_segments,
                 consistency_views, consistency_sources, consistency_pixel, consistency_relative, device)
 
+    if clean is not None:
+        system_name = f"{system_name}+clean"
     os.makedirs(reconstruction_folder, exist_ok=True)
     groundtruth_vertices = None
     if save_groundtruth or fuse_groundtruth_3d:
@@ -920,7 +950,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         groundtruth_vertices = tuple(torch.as_tensor(a, device=device) for a in (mesh_verts, mesh_faces))
     volume = TSDFVolume(volume_bounds, voxel_size=voxel_size, device=device)
     system_mesh_name = _mesh_name(reconstruction_folder, voxel_size, max_depth, use_groundtruth_to_anchor, system_name, dataset_name, scene_name)
-    TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K, system_mesh_name, save_progressive)
+    TSDFFusion.integrate(volume, keyframe_images, keyframe_predictions, keyframe_poses, scaled_K, system_mesh_name, save_progressive, clean=clean)
     if save_point_cloud:
         print("Saving point cloud to", system_mesh_name + "_pointcloud.ply")
         TSDFFusion.pcwrite(system_mesh_name + "_pointcloud.ply", point_cloud if point_cloud is not None else np.zeros((0, 6), np.float32))
@@ -932,9 +962,9 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
                     raise ValueError("evaluate_3d_visible: the scene has no keyframe to take the visibility from")
                 visible_from = (scaled_K, np.stack(keyframe_poses), prediction_height, prediction_width, int(evaluate_3d_min_views))
             _evaluate_3d_protocol(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_density, evaluate_3d_voxel,
-                                  visible_from, evaluate_3d_align, evaluate_3d_align_scale)
+                                  visible_from, evaluate_3d_align, evaluate_3d_align_scale, clean=clean)
         else:
-            _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_align, evaluate_3d_align_scale)
+            _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_align, evaluate_3d_align_scale, clean=clean)
     if render_keyframes:
         _render_keyframes(volume, keyframe_poses, keyframe_image_filenames, scaled_K, preprocessor, prediction_height, prediction_width,
                           scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
@@ -997,38 +1027,73 @@ def _aligned_score(volume, align_distance, align_scale, **score):
     return (down[:6].astype(np.float32),) + tuple(result[1:-1]) + (extra,)
 
 
-def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name, align_distance=None, align_scale=False):
+def _clean_filter(clean_mesh_area, clean_mesh_faces, clean_mesh_largest):
+    """The ``ComponentFilter`` of ``run``'s three settings, None when none is given; each refusal names its flag."""
+    if not isinstance(clean_mesh_largest, bool):
+        raise ValueError(f"clean_mesh_largest must be a bool, got {clean_mesh_largest!r}")
+    if clean_mesh_area is not None and not float(clean_mesh_area) >= 0.0:
+        raise ValueError(f"clean_mesh_area must be an area in square metres, not negative or NaN, got {clean_mesh_area}")
+    if clean_mesh_faces is not None and not (float(clean_mesh_faces) >= 0.0 and float(clean_mesh_faces).is_integer()):
+        raise ValueError(f"clean_mesh_faces must be a whole number of faces, not negative, got {clean_mesh_faces}")
+    if clean_mesh_area is None and clean_mesh_faces is None and not clean_mesh_largest:
+        return None
+    from dvmvs.components import ComponentFilter, filter_settings
+    clean = ComponentFilter(0.0 if clean_mesh_area is None else float(clean_mesh_area), 0 if clean_mesh_faces is None else int(clean_mesh_faces),
+                            clean_mesh_largest)
+    try:
+        filter_settings(clean)
+    except ValueError as e:
+        raise ValueError(f"clean_mesh_area / clean_mesh_faces: {e}") from None
+    return clean
+
+
+def _clean_entries(volume, clean):
+    """What ``_errors3d.npz`` gains with a ``ComponentFilter``: its settings and the kept and all faces of the system's mesh (tensor shapes:
+    nothing more is read than the extractions read themselves)."""
+    if clean is None:
+        return {}
+    kept, total = int(volume.mesh_tensors(clean=clean)[1].shape[0]), int(volume.mesh_tensors()[1].shape[0])
+    print("Mesh cleaned of small components: {} of {} faces kept".format(kept, total))
+    return {"clean_min_area": np.float64(clean.min_area), "clean_min_faces": np.int64(clean.min_faces), "clean_largest": np.bool_(clean.keep_largest),
+            "clean_faces": np.array([kept, total], dtype=np.int64)}
+
+
+def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name, align_distance=None, align_scale=False, clean=None):
     """Scores the fused surface against the ground-truth vertices on the device; one row comes down, is printed and saved."""
     from dvmvs.errors import RECONSTRUCTION_METRICS
+    cleaning = {} if clean is None else {"clean": clean}
     row, sizes, aligned = _aligned_score(volume, align_distance, align_scale, reference=groundtruth_vertices, threshold=threshold,
-                                         return_sizes=True)
+                                         return_sizes=True, **cleaning)
     print("3-D metrics at {} m over {} predicted and {} ground-truth vertices: {}".format(
         threshold, sizes[0], sizes[1], ", ".join(f"{n} {v:.4f}" for n, v in zip(RECONSTRUCTION_METRICS, row))))
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
-                        counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold), **aligned)
+                        counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold), **aligned, **_clean_entries(volume, clean))
 
 
 def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample_density, voxel, visible_from=None, align_distance=None,
-                          align_scale=False):
+                          align_scale=False, clean=None):
     """``_evaluate_3d`` against a ground-truth mesh (device verts and faces), with face sampling and / or voxel down-sampling of both sides;
     with ``visible_from`` (``TSDFVolume.score_against``) against the part of the mesh those views observed."""
     from dvmvs.errors import RECONSTRUCTION_METRICS
     extra = {}
     score = dict(reference=groundtruth_mesh, threshold=threshold, return_sizes=True, sample_density=sample_density, voxel=voxel)
+    if clean is not None:
+        score["clean"] = clean
     if visible_from is None:
         row, points, aligned = _aligned_score(volume, align_distance, align_scale, **score)
     else:
         row, points, kept, aligned = _aligned_score(volume, align_distance, align_scale, visible_from=visible_from, **score)
         print("Ground truth restricted to what {} keyframes saw: {} of {} faces".format(len(visible_from[1]), kept[0], kept[1]))
         extra = {"visible_faces": np.int64(kept[0]), "total_faces": np.int64(kept[1])}
-    sizes = (int(volume.vertices().shape[0]), int(groundtruth_mesh[0].shape[0]))
+    sizes = (int(volume.vertices(clean=clean).shape[0]), int(groundtruth_mesh[0].shape[0]))
     print("3-D metrics at {} m over {} predicted and {} ground-truth points (density {}, voxel {}; {} and {} vertices): {}".format(
         threshold, points[0], points[1], sample_density, voxel, sizes[0], sizes[1],
         ", ".join(f"{n} {v:.4f}" for n, v in zip(RECONSTRUCTION_METRICS, row))))
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS),
                         counts=np.array(sizes, dtype=np.int64), threshold=np.float32(threshold),
                         sample_density=np.float64(np.nan if sample_density is None else sample_density),
-                        voxel=np.float64(np.nan if voxel is None else voxel), points=np.array(points, dtype=np.int64), **extra, **aligned)
+                        voxel=np.float64(np.nan if voxel is None else voxel), points=np.array(points, dtype=np.int64), **extra, **aligned,
+                        **_clean_entries(volume, clean))
 
 
 def _render_keyframes(volume, poses, image_filenames, K, preprocessor, height, width, scene_folder, system_name, scene_name, save_folder):
@@ -1102,6 +1167,13 @@ def build_parser():
     parser.add_argument("--consistency_relative", default=0.01, type=float, help="largest relative depth difference of an agreeing view")
     parser.add_argument("--save_point_cloud", action="store_true",
                         help="with --filter_consistency: also write the kept pixels as a coloured point cloud (<mesh name>_pointcloud.ply)")
+    parser.add_argument("--clean_mesh_area", default=None, type=float,
+                        help="remove the connected components of the system's mesh with less area than this, square metres (on the device); "
+                             "files are written under <system>+clean")
+    parser.add_argument("--clean_mesh_faces", default=None, type=int,
+                        help="remove the connected components of the system's mesh with fewer faces than this; files are written under <system>+clean")
+    parser.add_argument("--clean_mesh_largest", action="store_true",
+                        help="keep only the largest connected component of the system's mesh (by area), if it passes the two thresholds")
     return parser
 
 

@@ -63,7 +63,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_icp_* and dvmvs_transform_points_fwd (registering a point cloud to another by trimmed ICP on the device);
  * no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_direct_conv_shape (which workgroup shape of the direct convolution a problem runs with; a host query);
- * no earlier signature changed, the number stays 11 by the same rule. */
+ * no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_mesh_components_* and dvmvs_mesh_filter_* (connected components of a triangle mesh and their removal by
+ * size); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -967,6 +969,52 @@ int dvmvs_icp_fwd(const float* source, long long N, const float* target, long lo
                   size_t query_workspace_bytes, float max_distance, int with_scale, int max_iterations, double tolerance,
                   const double* init_host, void* state, size_t state_bytes, dvmvs_stream_t stream);
 int dvmvs_transform_points_fwd(const float* points, long long N, const double* T, float* out, dvmvs_stream_t stream);
+
+/*
+ * Connected components of a triangle mesh, and their removal by size (ABI 11, later addition; csrc/mesh_components.hip).  The reference
+ * project has nothing for this: the definition is this project's own (dvmvs/components.py is its host form; Open3D's
+ * cluster_connected_triangles and remove_triangles_by_mask are the usual tools).  Everything that decides a result is an integer.
+ *   faces [F,3] int32, verts [V,3] fp32 (normals [V,3] fp32, colors [V,3] uint8), contiguous, 4-byte aligned; V, F in [0, 2^28].
+ * A face is VALID when its three indices lie in [0, V); an invalid face joins nothing and no vertex is read for it.
+ *   labels [V] int32        the smallest vertex index reachable from v over the edges of valid faces (v itself when no valid face uses v)
+ *   face_labels [F] int32   labels[faces[f][0]], -1 for an invalid face
+ *   face_count [V] int32    at r: the valid faces of the component whose label is r; 0 at every vertex that is no label of a face
+ *   area [V] int64          at r: the sum of A_f over those faces, A_f of dvmvs_surface_sample_count's definition (units of 2^-32 m^2);
+ *                           only with verts (both NULL otherwise)
+ *   result [2] int64        {the number of r with face_count[r] > 0, status}: status 1 when a valid face's area is not finite or does not
+ *                           fit or the mesh's total area is 2^63 units or more (decided exactly, from separately summed upper and lower
+ *                           halves; the areas of bad faces count as 0), status 2 when the labelling gave up (below); 0 otherwise.
+ * The labelling is a lock-free union-find over the vertices: parent[v] = v; one thread per valid face (a, b, c) unites (a, b) and (b, c);
+ * labels[v] = the end of v's chain, written to a separate array.  A union finds both roots and hooks the larger under the smaller by a
+ * compare-and-swap of parent[larger] that expects `larger`; when it fails it continues from the value the compare-and-swap returned.
+ * Invariant: parent[v] <= v always, an entry only ever decreases, and every write to parent during the unions is an atomic (that
+ * compare-and-swap, or the atomicMin of path halving).  A stale read can therefore cost a retry and never a wrong hook, and the smallest
+ * vertex of a component is never hooked: the labels are the canonical ones whatever the schedule.  A union makes at most 65536
+ * compare-and-swaps, then sets status 2.
+ * dvmvs_mesh_filter_count: root r is KEPT when face_count[r] > 0, face_count[r] >= min_faces and area[r] >= min_area_units; with
+ * keep_largest only the one r of all with face_count[r] > 0 that has the greatest area (ties: the greater face count, then the smaller r),
+ * and it only if it passes the thresholds.  A face is kept when it is valid and its label is kept, a vertex when its label is kept (the
+ * vertices that kept faces use).  counts [3] int64 = {V', F', status} with the status of `result` (V' = F' = 0 unless it is 0).
+ * dvmvs_mesh_filter_emit (with V_out = V', F_out = F' of the count call of the same arguments and workspace): kept vertices and kept faces
+ * in their original order, the faces re-indexed; normals / colors are gathered alongside (each NULL with its output); vertex_index
+ * [V'] and face_index [F'] (int32, each may be NULL): the old indices.
+ * workspace: dvmvs_mesh_components_workspace_bytes(V, F) bytes, 16-byte aligned, the same block for the three calls of one mesh (fwd
+ * initialises it; count leaves what emit reads).  dvmvs_mesh_components_workspace_bytes: host only; 0 for V or F outside [0, 2^28].
+ * Every entry returns DVMVS_EINVAL for a null or misaligned pointer that a non-empty side needs, a negative V or F (emit: V or F < 1, V_out
+ * or F_out outside [0, V] / [0, F]), verts without area or the reverse, a negative threshold, keep_largest not 0 / 1, a workspace that is
+ * too small; DVMVS_EUNSUPPORTED for V or F above 2^28.  Nothing is enqueued in either case.  The results are bit-identical run to run.
+ */
+size_t dvmvs_mesh_components_workspace_bytes(long long V, long long F);
+int dvmvs_mesh_components_fwd(const float* verts, long long V, const int* faces, long long F, void* workspace, size_t workspace_bytes,
+                              int* labels, int* face_labels, int* face_count, long long* area, long long* result, dvmvs_stream_t stream);
+int dvmvs_mesh_filter_count(const int* labels, const int* face_labels, const int* face_count, const long long* area, const long long* result,
+                            long long V, long long F, long long min_area_units, long long min_faces, int keep_largest, void* workspace,
+                            size_t workspace_bytes, long long* counts, dvmvs_stream_t stream);
+int dvmvs_mesh_filter_emit(const float* verts, const int* faces, const float* normals, const unsigned char* colors, const int* labels,
+                           const int* face_labels, const int* face_count, const long long* area, long long V, long long F,
+                           long long min_area_units, long long min_faces, int keep_largest, void* workspace, size_t workspace_bytes,
+                           long long V_out, long long F_out, float* verts_out, int* faces_out, float* normals_out, unsigned char* colors_out,
+                           int* vertex_index, int* face_index, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
