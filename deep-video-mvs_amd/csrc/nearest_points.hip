@@ -44,43 +44,13 @@
 // Preconditions, not checked on the device: finite coordinates.  (A NaN cannot make an access go out of bounds: fmin / fmax drop it and
 // the cell index is clamped; the distances are then meaningless.)
 #include "dvmvs_device.h"
+#include "nearest_grid.h"      // NnHeader, nn_cell, the workspace layouts, nn_wave_sum: shared with point_neighbours.hip
 
 #pragma clang fp contract(off)
 
 namespace dvmvs {
 
 namespace {
-
-constexpr int kNnBlock = 256;
-constexpr int kNnBboxGroups = 256;          // workgroups of the box reduction at most
-constexpr int kNnScanCells = 4 * kNnBlock;  // cells per workgroup of the scan
-constexpr int kNnScanThreads = 1024;        // the one workgroup that scans the workgroup totals
-constexpr long long kNnMaxPoints = 1LL << 28;
-constexpr int kNnMaxCells = 1 << 22;
-constexpr int kNnMaxDim = 1024;
-constexpr int kNnMetricThreads = 1024;
-
-struct NnHeader {
-  float mn[3], mx[3];
-  float inv_h, h_lo;
-  int dim[3];
-  int ncells;
-};
-
-typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
-
-__device__ inline int nn_cell_axis(float x, float mn, float mx, float inv_h, int dim) {
-  const float c = fminf(fmaxf(x, mn), mx);                 // the projection onto the box (exact)
-  const int k = static_cast<int>((c - mn) * inv_h);        // >= 0: truncation is floor
-  return min(max(k, 0), dim - 1);                          // no effect on finite input (file comment)
-}
-
-__device__ inline int nn_cell(const NnHeader& h, float x, float y, float z, int& cx, int& cy, int& cz) {
-  cx = nn_cell_axis(x, h.mn[0], h.mx[0], h.inv_h, h.dim[0]);
-  cy = nn_cell_axis(y, h.mn[1], h.mx[1], h.inv_h, h.dim[1]);
-  cz = nn_cell_axis(z, h.mn[2], h.mx[2], h.inv_h, h.dim[2]);
-  return (cx * h.dim[1] + cy) * h.dim[2] + cz;
-}
 
 // partials [gridDim.x, 6]: min x, y, z, max x, y, z of the points i = global thread, + threads, ...
 __global__ __launch_bounds__(kNnBlock) void nn_bbox_kernel(const float* __restrict__ pts, int n, float* __restrict__ partials) {
@@ -329,15 +299,6 @@ __global__ __launch_bounds__(kNnBlock) void nn_query_kernel(const uint4v* __rest
   if (index) index[qi] = best.j;
 }
 
-// xor butterfly over the wave: every lane ends with the same value (a + b and b + a are the same bits)
-__device__ inline void nn_wave_sum(double& s, unsigned long long& c) {
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) {
-    s += __shfl_xor(s, m, kWave);
-    c += __shfl_xor(c, m, kWave);
-  }
-}
-
 // ONE workgroup, so the order of the additions is a function of (na, nb) alone: thread t adds the elements t, t + 1024, ... of an array in
 // fp64, the 64 lanes of a wave are combined by the butterfly, the 16 waves in order by thread 0.
 __global__ __launch_bounds__(kNnMetricThreads) void nn_metrics_kernel(const float* __restrict__ dist_a, long long na, const float* __restrict__ dist_b,
@@ -386,13 +347,6 @@ __global__ __launch_bounds__(kNnMetricThreads) void nn_metrics_kernel(const floa
   row[5] = pr > 0.0 ? static_cast<float>(2.0 * share[0] * share[1] / pr) : 0.0f;
 }
 
-size_t nn_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
-int nn_capacity(long long m) {
-  const long long c = 4 * m < 64 ? 64 : 4 * m;
-  return static_cast<int>(c < kNnMaxCells ? c : kNnMaxCells);
-}
-
 int nn_scan_blocks(int capacity) { return (capacity + kNnScanCells - 1) / kNnScanCells; }      // <= 4096
 
 int nn_bbox_groups(long long m) {
@@ -400,35 +354,7 @@ int nn_bbox_groups(long long m) {
   return static_cast<int>(g < kNnBboxGroups ? g : kNnBboxGroups);
 }
 
-// Target workspace: header | box partials [256, 6] | scan totals [4096] | cells [capacity] | sorted [M] x 16 bytes.
-struct NnLayout {
-  size_t partials_off, totals_off, cells_off, sorted_off, total;
-  int capacity;
-};
-
-NnLayout nn_layout(long long m) {
-  NnLayout l;
-  l.capacity = nn_capacity(m);
-  l.partials_off = nn_align(sizeof(NnHeader));
-  l.totals_off = l.partials_off + nn_align(kNnBboxGroups * 6 * sizeof(float));
-  l.cells_off = l.totals_off + nn_align(static_cast<size_t>(kNnMaxCells / kNnScanCells) * sizeof(int));
-  l.sorted_off = l.cells_off + nn_align(static_cast<size_t>(l.capacity) * sizeof(int));
-  l.total = l.sorted_off + nn_align(static_cast<size_t>(m) * 16);
-  return l;
-}
-
-// Query workspace: scan totals [4096] | cells [capacity of M] | sorted [N] x 16 bytes.
-struct NnQueryLayout {
-  size_t cells_off, sorted_off, total;
-};
-
-NnQueryLayout nn_query_layout(long long n, long long m) {
-  NnQueryLayout l;
-  l.cells_off = nn_align(static_cast<size_t>(kNnMaxCells / kNnScanCells) * sizeof(int));
-  l.sorted_off = l.cells_off + nn_align(static_cast<size_t>(nn_capacity(m)) * sizeof(int));
-  l.total = l.sorted_off + nn_align(static_cast<size_t>(n) * 16);
-  return l;
-}
+}  // namespace
 
 // count -> scan -> scatter of `n` points into the grid of `hdr`: `cells` ends as the cells' ends, `sorted` as the binned copy
 int nn_bin(const float* pts, int n, const NnHeader* hdr, int capacity, int* cells, int* totals, uint4v* sorted, hipStream_t s) {
@@ -441,8 +367,6 @@ int nn_bin(const float* pts, int n, const NnHeader* hdr, int capacity, int* cell
   hipLaunchKernelGGL(nn_scatter_kernel, points, block, 0, s, pts, n, hdr, cells, sorted);
   return launch_status();
 }
-
-}  // namespace
 
 }  // namespace dvmvs
 

@@ -155,6 +155,11 @@ SIGNATURES = {
                                          ctypes.c_longlong, _c_int, _c_fp, ctypes.c_size_t, _c_fp, _c_stream]),
     "dvmvs_mesh_filter_emit": (_c_int, [_c_fp] * 8 + [ctypes.c_longlong] * 4 + [_c_int, _c_fp, ctypes.c_size_t, ctypes.c_longlong,
                                                                                 ctypes.c_longlong] + [_c_fp] * 6 + [_c_stream]),
+    "dvmvs_knn_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_size_t, _c_int, ctypes.c_float, _c_int,
+                               _c_fp, _c_fp, _c_stream]),
+    "dvmvs_radius_count_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_size_t, ctypes.c_float, _c_int,
+                                        _c_int, _c_fp, _c_stream]),
+    "dvmvs_outlier_statistics_fwd": (_c_int, [_c_fp, _c_fp, ctypes.c_longlong, _c_int, _c_dbl, _c_fp, _c_fp, _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -185,6 +190,8 @@ ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE = ("dvmvs_direct_conv_shape",)
 # ... and the eleventh (connected components of a triangle mesh and their removal by size)
 ADDED_WITHIN_ABI_MESH_COMPONENTS = ("dvmvs_mesh_components_workspace_bytes", "dvmvs_mesh_components_fwd", "dvmvs_mesh_filter_count",
                                     "dvmvs_mesh_filter_emit")
+# ... and the twelfth (the k nearest neighbours of points, neighbours within a radius, statistical outlier scores)
+ADDED_WITHIN_ABI_POINT_NEIGHBOURS = ("dvmvs_knn_fwd", "dvmvs_radius_count_fwd", "dvmvs_outlier_statistics_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -205,7 +212,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
                  + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER
-                 + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE + ADDED_WITHIN_ABI_MESH_COMPONENTS)
+                 + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE + ADDED_WITHIN_ABI_MESH_COMPONENTS
+                 + ADDED_WITHIN_ABI_POINT_NEIGHBOURS)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

@@ -774,7 +774,8 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, groundtruth_transform=None,
-        clean_mesh_area=None, clean_mesh_faces=None, clean_mesh_largest=False):
+        clean_points_neighbours=None, clean_points_ratio=2.0, clean_points_max_distance=None, clean_points_radius=None,
+        clean_points_min_neighbours=None, clean_mesh_area=None, clean_mesh_faces=None, clean_mesh_largest=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -833,8 +834,20 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     cleaned meshes, and ``evaluate_3d`` scores the cleaned surface; ``_errors3d.npz`` then also holds ``clean_min_area``,
     ``clean_min_faces``, ``clean_largest`` and ``clean_faces`` int64 [2], the kept and all faces of the system's mesh.  The ground-truth
     side is never cleaned, and ``render_keyframes`` ray-casts the VOLUME, which cleaning a mesh does not touch: its depth maps are what
-    they are without these flags (under the ``+clean`` name).  Without these flags every file is what it is without them, byte for byte."""
+    they are without these flags (under the ``+clean`` name).  Without these flags every file is what it is without them, byte for byte.
+
+    ``clean_points_neighbours`` (a count, 1 .. 32) with ``clean_points_ratio`` and ``clean_points_max_distance`` (metres),
+    ``clean_points_radius`` (metres) with ``clean_points_min_neighbours`` (each needs ``save_point_cloud``): the fused point cloud goes
+    through ``dvmvs.outliers.filter_outliers`` on the device before it comes down (``OutlierFilter``).  The first removes the points whose
+    mean distance to their ``clean_points_neighbours`` nearest points is more than ``clean_points_ratio`` sample deviations above the
+    cloud's mean (statistical outlier removal; ``clean_points_max_distance`` bounds the neighbour search, which otherwise follows a far
+    outlier until it has its neighbours, and a point without a neighbour inside it is removed), the second those with fewer than
+    ``clean_points_min_neighbours`` points within ``clean_points_radius``; with both, the second runs on what the first keeps.  The
+    filtered cloud is written ADDITIONALLY as ``<mesh name>_pointcloud_clean.ply`` and the kept share of the points is printed;
+    ``_pointcloud.ply`` and every other file are what they are without these flags, byte for byte."""
     clean = _clean_filter(clean_mesh_area, clean_mesh_faces, clean_mesh_largest)
+    clean_points = _clean_points_filter(save_point_cloud, clean_points_neighbours, clean_points_ratio, clean_points_max_distance,
+                                        clean_points_radius, clean_points_min_neighbours)
     if save_point_cloud and not filter_consistency:
         raise ValueError("save_point_cloud needs filter_consistency: the point cloud is made of the pixels the filter keeps")
     protocol_3d = evaluate_3d_density is not None or evaluate_3d_voxel is not None or groundtruth_mesh is not None
@@ -918,13 +931,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         volume_bounds = TSDFFusion.calculate_volume_bounds(keyframe_predictions, keyframe_poses, scaled_K)
     volume_bounds *= 1.05      # margin for errors in the bounds
 
-    point_cloud = None
+    point_cloud = clean_point_cloud = None
     if filter_consistency:
         system_name = f"{system_name}+consistent"
         if keyframe_predictions:
-            keyframe_predictions, point_cloud = _filter_keyframes(
+            keyframe_predictions, point_cloud, clean_point_cloud = _filter_keyframes(
                 keyframe_predictions, keyframe_images if save_point_cloud else None, keyframe_poses, scaled_K, keyframe_segments,
-                consistency_views, consistency_sources, consistency_pixel, consistency_relative, device)
+                consistency_views, consistency_sources, consistency_pixel, consistency_relative, device, clean_points)
 
     if clean is not None:
         system_name = f"{system_name}+clean"
@@ -954,6 +967,10 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     if save_point_cloud:
         print("Saving point cloud to", system_mesh_name + "_pointcloud.ply")
         TSDFFusion.pcwrite(system_mesh_name + "_pointcloud.ply", point_cloud if point_cloud is not None else np.zeros((0, 6), np.float32))
+        if clean_points is not None:
+            print("Saving cleaned point cloud to", system_mesh_name + "_pointcloud_clean.ply")
+            TSDFFusion.pcwrite(system_mesh_name + "_pointcloud_clean.ply",
+                               clean_point_cloud if clean_point_cloud is not None else np.zeros((0, 6), np.float32))
     if evaluate_3d:
         if protocol_3d:
             visible_from = None
@@ -970,9 +987,11 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
                           scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
 
 
-def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sources, pixel_threshold, relative_threshold, device):
+def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sources, pixel_threshold, relative_threshold, device,
+                      clean_points=None):
     """The keyframe predictions filtered by consistency (a list of host arrays, as they came) and, with ``images``, the fused point cloud
-    [P,6] xyzrgb on the host."""
+    [P,6] xyzrgb on the host, and with ``clean_points`` (an ``OutlierFilter``) also the rows of it that the filter keeps, chosen on the
+    device."""
     from dvmvs.consistency import filter_depths, fused_point_cloud, nearest_sources
     depths = torch.as_tensor(np.stack(predictions).astype(np.float32), device=device)
     cameras = torch.as_tensor(np.stack(poses).astype(np.float32), device=device)
@@ -982,11 +1001,17 @@ def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sour
     valid = torch.isfinite(depths) & (depths > 0)
     print("Consistency filter: kept {:.1f} % of the valid pixels of {} keyframes".format(
         100.0 * float((kept > 0).sum()) / max(int(valid.sum()), 1), len(predictions)))
-    cloud = None
+    cloud = clean_cloud = None
     if images is not None:
         averaged, _, points = filter_depths(depths, K, cameras, sources, average=True, with_count=False, with_points=True, **thresholds)
-        cloud = fused_point_cloud(averaged, points, np.stack(images)).cpu().numpy()
-    return list(kept.cpu().numpy()), cloud
+        cloud = fused_point_cloud(averaged, points, np.stack(images))
+        if clean_points is not None:
+            from dvmvs.outliers import filter_outliers_device
+            clean_cloud = filter_outliers_device(cloud, clean_points).cpu().numpy()
+            print("Outlier filter: kept {:.1f} % of the {} points of the cloud".format(
+                100.0 * len(clean_cloud) / max(int(cloud.shape[0]), 1), int(cloud.shape[0])))
+        cloud = cloud.cpu().numpy()
+    return list(kept.cpu().numpy()), cloud, clean_cloud
 
 
 def load_transform(filename):
@@ -1045,6 +1070,39 @@ def _clean_filter(clean_mesh_area, clean_mesh_faces, clean_mesh_largest):
     except ValueError as e:
         raise ValueError(f"clean_mesh_area / clean_mesh_faces: {e}") from None
     return clean
+
+
+def _clean_points_filter(save_point_cloud, neighbours, ratio, max_distance, radius, min_neighbours):
+    """The ``OutlierFilter`` of ``run``'s five ``clean_points_*`` settings, None when none is given; each refusal names its flag."""
+    def number(value):
+        return not isinstance(value, bool) and isinstance(value, (int, float, np.integer, np.floating))
+    if not number(ratio) or not 0.0 <= float(ratio) < np.inf:
+        raise ValueError(f"clean_points_ratio must be a finite number of deviations, not negative, got {ratio!r}")
+    if neighbours is not None and not (number(neighbours) and float(neighbours).is_integer() and 1 <= int(neighbours) <= 32):
+        raise ValueError(f"clean_points_neighbours must be a whole number of neighbours in [1, 32], got {neighbours!r}")
+    if max_distance is not None and not (number(max_distance) and float(max_distance) > 0.0):
+        raise ValueError(f"clean_points_max_distance must be a positive distance in metres, got {max_distance!r}")
+    if radius is not None and not (number(radius) and 0.0 <= float(radius) < np.inf):
+        raise ValueError(f"clean_points_radius must be a finite distance in metres, not negative, got {radius!r}")
+    if min_neighbours is not None and not (number(min_neighbours) and float(min_neighbours).is_integer() and 1 <= int(min_neighbours) < 2 ** 31):
+        raise ValueError(f"clean_points_min_neighbours must be a whole number of neighbours, at least 1, got {min_neighbours!r}")
+    if float(ratio) != 2.0 and neighbours is None:
+        raise ValueError("clean_points_ratio says how clean_points_neighbours filters: it needs clean_points_neighbours")
+    if max_distance is not None and neighbours is None:
+        raise ValueError("clean_points_max_distance bounds the search of clean_points_neighbours: it needs clean_points_neighbours")
+    if radius is not None and min_neighbours is None:
+        raise ValueError("clean_points_radius needs clean_points_min_neighbours, the neighbours a point must have within it")
+    if min_neighbours is not None and radius is None:
+        raise ValueError("clean_points_min_neighbours needs clean_points_radius, the distance its neighbours are counted within")
+    if neighbours is None and radius is None:
+        return None
+    if not save_point_cloud:
+        raise ValueError("clean_points_neighbours and clean_points_radius filter the cloud of save_point_cloud: they need save_point_cloud")
+    from dvmvs.outliers import OutlierFilter, filter_settings
+    clean_points = OutlierFilter(None if neighbours is None else int(neighbours), float(ratio), None if max_distance is None else float(max_distance),
+                                 None if radius is None else float(radius), None if min_neighbours is None else int(min_neighbours))
+    filter_settings(clean_points)
+    return clean_points
 
 
 def _clean_entries(volume, clean):
@@ -1167,6 +1225,20 @@ def build_parser():
     parser.add_argument("--consistency_relative", default=0.01, type=float, help="largest relative depth difference of an agreeing view")
     parser.add_argument("--save_point_cloud", action="store_true",
                         help="with --filter_consistency: also write the kept pixels as a coloured point cloud (<mesh name>_pointcloud.ply)")
+    parser.add_argument("--clean_points_neighbours", default=None, type=int,
+                        help="with --save_point_cloud: statistical outlier removal of the fused cloud on the device, over this many nearest "
+                             "neighbours (1 .. 32); the result is written additionally as <mesh name>_pointcloud_clean.ply")
+    parser.add_argument("--clean_points_ratio", default=2.0, type=float,
+                        help="with --clean_points_neighbours: a point goes when its mean neighbour distance is more than this many sample "
+                             "deviations above the cloud's mean")
+    parser.add_argument("--clean_points_max_distance", default=None, type=float,
+                        help="with --clean_points_neighbours: neighbours are searched within this distance only, metres (bounds the search "
+                             "of far outliers; a point without a neighbour inside it goes)")
+    parser.add_argument("--clean_points_radius", default=None, type=float,
+                        help="with --save_point_cloud and --clean_points_min_neighbours: radius outlier removal of the fused cloud on the "
+                             "device, metres (after the statistical filter when both are given)")
+    parser.add_argument("--clean_points_min_neighbours", default=None, type=int,
+                        help="with --clean_points_radius: a point stays when it has at least this many other points within the radius")
     parser.add_argument("--clean_mesh_area", default=None, type=float,
                         help="remove the connected components of the system's mesh with less area than this, square metres (on the device); "
                              "files are written under <system>+clean")

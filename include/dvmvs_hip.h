@@ -65,7 +65,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_direct_conv_shape (which workgroup shape of the direct convolution a problem runs with; a host query);
  * no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_mesh_components_* and dvmvs_mesh_filter_* (connected components of a triangle mesh and their removal by
- * size); no earlier signature changed, the number stays 11 by the same rule. */
+ * size); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_knn_fwd, dvmvs_radius_count_fwd and dvmvs_outlier_statistics_fwd (the k nearest neighbours of points,
+ * neighbours within a radius, statistical outlier scores); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -1015,6 +1017,49 @@ int dvmvs_mesh_filter_emit(const float* verts, const int* faces, const float* no
                            long long min_area_units, long long min_faces, int keep_largest, void* workspace, size_t workspace_bytes,
                            long long V_out, long long F_out, float* verts_out, int* faces_out, float* normals_out, unsigned char* colors_out,
                            int* vertex_index, int* face_index, dvmvs_stream_t stream);
+
+/*
+ * The k nearest neighbours of points, neighbours within a radius, and statistical outlier scores (ABI 11, later addition;
+ * csrc/point_neighbours.hip).  The reference project has nothing for this: the definitions are this project's own (dvmvs/outliers.py is
+ * their host form; Open3D's remove_statistical_outlier and remove_radius_outlier are the usual tools).  The two searches run on the grid
+ * of the nearest-point block above and take its arguments:
+ *   target [M,3], query [N,3]   fp32, contiguous, 4-byte aligned, FINITE (a precondition; not checked on the device)
+ *   workspace         the target's grid: dvmvs_nearest_build(target, M, ...) into dvmvs_nearest_workspace_bytes(M) bytes; not changed
+ *   query_workspace   dvmvs_nearest_query_workspace_bytes(N, M) bytes, 16-byte aligned, scratch of one call.  Calls that share it must be
+ *                     ordered.
+ * Arithmetic contract, that of the nearest-point block: d2(q, t) = (dx dx + dy dy) + dz dz, every operation rounded to fp32, no FMA
+ * contraction; distances are sqrt(d2), correctly rounded.
+ * dvmvs_knn_fwd: the CANDIDATES of query i are the targets j with d2(query_i, target_j) <= cap2 = fl(max_distance * max_distance) in fp32
+ *   (max_distance = inf: all) and, with exclude_same_index = 1, j != i (by index, for a cloud searched against itself: a duplicate point
+ *   at distance 0 is a neighbour).  dist [N,k] fp32 and index [N,k] int32: row i holds the k smallest candidates in ascending
+ *   lexicographic order of (d2, j), the distance as sqrt(d2); missing slots are (inf, -1).  1 <= k <= 32.  The set of the k smallest
+ *   pairs does not depend on the order of evaluation, so the rows are bit-identical to a brute force over all j, run to run, on any
+ *   stream.  The search visits the cells around the query's cell in growing Chebyshev rings and stops only, and never before ring 1, when
+ *   every unvisited target is provably no candidate (its d2 exceeds cap2) or provably larger than the k-th pair of a full list (bound and
+ *   its fp32 margins: csrc/point_neighbours.hip); otherwise it goes on until it has visited the whole grid.  A query with fewer than k
+ *   candidates therefore walks the whole grid unless max_distance ends the walk: max_distance is what bounds the work for far outliers.
+ * dvmvs_radius_count_fwd: count [N] int32 = min(number of candidates of cap2 = fl(radius * radius), cap), cap >= 1.  The saturation is
+ *   part of the definition: the search leaves a query once it has counted cap.
+ * dvmvs_outlier_statistics_fwd: dist / index [N,k] as dvmvs_knn_fwd wrote them (a slot counts when its index is >= 0), ratio >= 0 finite.
+ *   mean [N] fp32: m_i = the fp64 sum of the counted distances of row i in slot order, divided by their number, rounded to fp32 once; inf
+ *     for a row without one.  Point i is VALID when m_i is finite.
+ *   stats [4] fp64 = {n, mu, sigma, threshold}: n the valid points, mu = sum of fp64(m_i) over them / n, sigma = sqrt(sum of (m_i - mu)^2
+ *     / (n - 1)) (a second pass; 0 for n < 2), threshold = mu + ratio * sigma; n = 0 gives four zeros.  Both sums run in fp64 in ONE
+ *     workgroup in the order of dvmvs_distance_metrics_fwd, a function of N alone (thread t of 1024 adds the elements t, t + 1024, ...,
+ *     an invalid one adds 0; 64-lane xor butterfly; the 16 waves in order); division and square root are correctly rounded.
+ *   keep [N] uint8: 1 where point i is valid and fp64(m_i) <= threshold.  Three launches, nothing read by the host.
+ * With N == 0 every entry enqueues nothing and returns 0.
+ * Every entry returns DVMVS_EINVAL for a null or misaligned pointer (4 bytes; workspaces 16; stats 8), k outside [1,32], cap < 1, a NaN or
+ * negative max_distance / radius / ratio (ratio also: infinite), exclude_same_index not 0 / 1, N < 0, M < 1, a query workspace that is too
+ * small; DVMVS_EUNSUPPORTED above 2^28 points.  Nothing is enqueued in either case.  No floating-point atomics are used.
+ */
+int dvmvs_knn_fwd(const float* query, long long N, const float* target, long long M, const void* workspace, void* query_workspace,
+                  size_t query_workspace_bytes, int k, float max_distance, int exclude_same_index, float* dist, int* index,
+                  dvmvs_stream_t stream);
+int dvmvs_radius_count_fwd(const float* query, long long N, const float* target, long long M, const void* workspace, void* query_workspace,
+                           size_t query_workspace_bytes, float radius, int cap, int exclude_same_index, int* count, dvmvs_stream_t stream);
+int dvmvs_outlier_statistics_fwd(const float* dist, const int* index, long long N, int k, double ratio, float* mean, unsigned char* keep,
+                                 double* stats, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
