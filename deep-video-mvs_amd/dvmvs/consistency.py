@@ -75,3 +75,13 @@ def fused_point_cloud(depth, points, colours=None):
             raise ValueError(f"fused_point_cloud: colours {tuple(colours.shape)} do not belong to points {tuple(points.shape)}")
         cloud = torch.cat([points, colours.to(torch.float32)], dim=-1)
     return cloud[depth > 0]
+
+
+def fused_point_views(depth):
+    """Which frame every point of ``fused_point_cloud(depth, ...)`` came from: ``depth`` [N,H,W] (a tensor on any device) -> int32 [P] on
+    its device, the frame index of every kept pixel in that function's order (frame-major, then row-major): what orients a point's normal
+    toward the camera that saw it (``dvmvs.normals``).  One boolean index, as there: one synchronisation with the device."""
+    if depth.dim() != 3:
+        raise ValueError(f"fused_point_views: depth must be [N,H,W], got {tuple(depth.shape)}")
+    frames = torch.arange(depth.shape[0], dtype=torch.int32, device=depth.device)[:, None, None].expand(depth.shape)
+    return frames[depth > 0]

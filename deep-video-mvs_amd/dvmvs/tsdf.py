@@ -626,6 +626,22 @@ class TSDFFusion:
             f.write(header + body)
 
     @staticmethod
+    def pcwrite_normals(filename, xyzrgb, normals):
+        """ASCII .ply of a coloured point cloud [N,6] (xyz, rgb) with a normal [N,3] for every point: ``pcwrite``'s format with ``property float
+        nx/ny/nz`` between z and red, the vertex layout of ``meshwrite`` (what MeshLab, Open3D and ``meshread`` read)."""
+        xyzrgb, normals = np.asarray(xyzrgb), np.asarray(normals)
+        if normals.shape != (len(xyzrgb), 3):
+            raise ValueError(f"pcwrite_normals: normals {normals.shape} do not belong to {len(xyzrgb)} points")
+        xyz, rgb = xyzrgb[:, :3], xyzrgb[:, 3:].astype(np.uint8)
+        header = ("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                  "property float nx\nproperty float ny\nproperty float nz\n"
+                  "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n") % len(xyz)
+        body = TSDFFusion._columns(["%f"] * 6 + ["%d"] * 3, [xyz[:, 0], xyz[:, 1], xyz[:, 2], normals[:, 0], normals[:, 1], normals[:, 2],
+                                                            rgb[:, 0], rgb[:, 1], rgb[:, 2]])
+        with open(filename, "w") as f:
+            f.write(header + body)
+
+    @staticmethod
     def integrate(tsdf_volume, images, depths, poses, K, mesh_name, save_progressive, clean=None):
         """Fuses every (image, depth, pose) with weight 1 and writes ``<mesh_name>_complete.ply`` (with ``save_progressive``,
         also ``<mesh_name>_frame_<i>.ply`` after each frame), like the reconstruction script (:442-462).  ``clean`` (a
@@ -774,8 +790,9 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, groundtruth_transform=None,
-        clean_points_neighbours=None, clean_points_ratio=2.0, clean_points_max_distance=None, clean_points_radius=None,
-        clean_points_min_neighbours=None, clean_mesh_area=None, clean_mesh_faces=None, clean_mesh_largest=False):
+        point_normals_neighbours=None, point_normals_max_distance=None, clean_points_neighbours=None, clean_points_ratio=2.0,
+        clean_points_max_distance=None, clean_points_radius=None, clean_points_min_neighbours=None, clean_mesh_area=None,
+        clean_mesh_faces=None, clean_mesh_largest=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -844,10 +861,20 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     outlier until it has its neighbours, and a point without a neighbour inside it is removed), the second those with fewer than
     ``clean_points_min_neighbours`` points within ``clean_points_radius``; with both, the second runs on what the first keeps.  The
     filtered cloud is written ADDITIONALLY as ``<mesh name>_pointcloud_clean.ply`` and the kept share of the points is printed;
-    ``_pointcloud.ply`` and every other file are what they are without these flags, byte for byte."""
+    ``_pointcloud.ply`` and every other file are what they are without these flags, byte for byte.
+
+    ``point_normals_neighbours`` (a count, 3 .. 32) with ``point_normals_max_distance`` (metres; None: unbounded), each needing
+    ``save_point_cloud``: the point cloud, the cleaned one where ``clean_points_*`` are given and the fused one otherwise, gets oriented
+    normals on the device (``dvmvs.normals.estimate_normals``): the direction of least spread of each point's ``point_normals_neighbours``
+    nearest points within ``point_normals_max_distance``, the point itself among them, turned toward the camera centre of the keyframe
+    the point came from (``dvmvs.consistency.fused_point_views``).  The cloud with its normals is written ADDITIONALLY as
+    ``<mesh name>_pointcloud_normals.ply`` (``TSDFFusion.pcwrite_normals``), without the points that have no valid normal (fewer than
+    three neighbours within the distance, or all of them in one place), and the share of valid points is printed; every other file is
+    what it is without these flags, byte for byte."""
     clean = _clean_filter(clean_mesh_area, clean_mesh_faces, clean_mesh_largest)
     clean_points = _clean_points_filter(save_point_cloud, clean_points_neighbours, clean_points_ratio, clean_points_max_distance,
                                         clean_points_radius, clean_points_min_neighbours)
+    point_normals = _point_normals_settings(save_point_cloud, point_normals_neighbours, point_normals_max_distance)
     if save_point_cloud and not filter_consistency:
         raise ValueError("save_point_cloud needs filter_consistency: the point cloud is made of the pixels the filter keeps")
     protocol_3d = evaluate_3d_density is not None or evaluate_3d_voxel is not None or groundtruth_mesh is not None
@@ -931,13 +958,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         volume_bounds = TSDFFusion.calculate_volume_bounds(keyframe_predictions, keyframe_poses, scaled_K)
     volume_bounds *= 1.05      # margin for errors in the bounds
 
-    point_cloud = clean_point_cloud = None
+    point_cloud = clean_point_cloud = normals_point_cloud = None
     if filter_consistency:
         system_name = f"{system_name}+consistent"
         if keyframe_predictions:
-            keyframe_predictions, point_cloud, clean_point_cloud = _filter_keyframes(
+            keyframe_predictions, point_cloud, clean_point_cloud, normals_point_cloud = _filter_keyframes(
                 keyframe_predictions, keyframe_images if save_point_cloud else None, keyframe_poses, scaled_K, keyframe_segments,
-                consistency_views, consistency_sources, consistency_pixel, consistency_relative, device, clean_points)
+                consistency_views, consistency_sources, consistency_pixel, consistency_relative, device, clean_points, point_normals)
 
     if clean is not None:
         system_name = f"{system_name}+clean"
@@ -971,6 +998,11 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
             print("Saving cleaned point cloud to", system_mesh_name + "_pointcloud_clean.ply")
             TSDFFusion.pcwrite(system_mesh_name + "_pointcloud_clean.ply",
                                clean_point_cloud if clean_point_cloud is not None else np.zeros((0, 6), np.float32))
+        if point_normals is not None:
+            print("Saving point cloud with normals to", system_mesh_name + "_pointcloud_normals.ply")
+            TSDFFusion.pcwrite_normals(system_mesh_name + "_pointcloud_normals.ply",
+                                       *(normals_point_cloud if normals_point_cloud is not None
+                                         else (np.zeros((0, 6), np.float32), np.zeros((0, 3), np.float32))))
     if evaluate_3d:
         if protocol_3d:
             visible_from = None
@@ -988,11 +1020,12 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
 
 
 def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sources, pixel_threshold, relative_threshold, device,
-                      clean_points=None):
+                      clean_points=None, point_normals=None):
     """The keyframe predictions filtered by consistency (a list of host arrays, as they came) and, with ``images``, the fused point cloud
-    [P,6] xyzrgb on the host, and with ``clean_points`` (an ``OutlierFilter``) also the rows of it that the filter keeps, chosen on the
-    device."""
-    from dvmvs.consistency import filter_depths, fused_point_cloud, nearest_sources
+    [P,6] xyzrgb on the host, with ``clean_points`` (an ``OutlierFilter``) also the rows of it that the filter keeps, chosen on the
+    device, and with ``point_normals`` (``(neighbours, max_distance)``) also ``(xyzrgb [Q,6], normals [Q,3])``: the points of the cleaned
+    cloud (of the fused one without ``clean_points``) that have a valid normal, oriented toward the camera centre of their keyframe."""
+    from dvmvs.consistency import filter_depths, fused_point_cloud, fused_point_views, nearest_sources
     depths = torch.as_tensor(np.stack(predictions).astype(np.float32), device=device)
     cameras = torch.as_tensor(np.stack(poses).astype(np.float32), device=device)
     sources = torch.as_tensor(nearest_sources(len(predictions), n_sources, segments), device=device)
@@ -1001,17 +1034,28 @@ def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sour
     valid = torch.isfinite(depths) & (depths > 0)
     print("Consistency filter: kept {:.1f} % of the valid pixels of {} keyframes".format(
         100.0 * float((kept > 0).sum()) / max(int(valid.sum()), 1), len(predictions)))
-    cloud = clean_cloud = None
+    cloud = clean_cloud = normals_cloud = None
     if images is not None:
         averaged, _, points = filter_depths(depths, K, cameras, sources, average=True, with_count=False, with_points=True, **thresholds)
         cloud = fused_point_cloud(averaged, points, np.stack(images))
+        oriented = cloud                                                  # the cloud that gets the normals, on the device
         if clean_points is not None:
             from dvmvs.outliers import filter_outliers_device
-            clean_cloud = filter_outliers_device(cloud, clean_points).cpu().numpy()
+            oriented, keep = filter_outliers_device(cloud, clean_points, return_mask=True)
+            clean_cloud = oriented.cpu().numpy()
             print("Outlier filter: kept {:.1f} % of the {} points of the cloud".format(
                 100.0 * len(clean_cloud) / max(int(cloud.shape[0]), 1), int(cloud.shape[0])))
+        if point_normals is not None:
+            from dvmvs.normals import estimate_normals_device
+            views = fused_point_views(averaged)
+            if clean_points is not None:
+                views = views[keep]
+            normals, _, valid = estimate_normals_device(oriented[:, :3], point_normals[0], point_normals[1], cameras[:, :3, 3], views)
+            normals_cloud = (oriented[valid].cpu().numpy(), normals[valid].cpu().numpy())
+            print("Point normals: {:.1f} % of the {} points have a valid normal".format(
+                100.0 * len(normals_cloud[0]) / max(int(oriented.shape[0]), 1), int(oriented.shape[0])))
         cloud = cloud.cpu().numpy()
-    return list(kept.cpu().numpy()), cloud, clean_cloud
+    return list(kept.cpu().numpy()), cloud, clean_cloud, normals_cloud
 
 
 def load_transform(filename):
@@ -1103,6 +1147,24 @@ def _clean_points_filter(save_point_cloud, neighbours, ratio, max_distance, radi
                                  None if radius is None else float(radius), None if min_neighbours is None else int(min_neighbours))
     filter_settings(clean_points)
     return clean_points
+
+
+def _point_normals_settings(save_point_cloud, neighbours, max_distance):
+    """``(neighbours, max_distance)`` of ``run``'s two ``point_normals_*`` settings (``max_distance`` inf when not given), None when neither
+    is given; each refusal names its flag."""
+    def number(value):
+        return not isinstance(value, bool) and isinstance(value, (int, float, np.integer, np.floating))
+    if neighbours is not None and not (number(neighbours) and float(neighbours).is_integer() and 3 <= int(neighbours) <= 32):
+        raise ValueError(f"point_normals_neighbours must be a whole number of neighbours in [3, 32], got {neighbours!r}")
+    if max_distance is not None and not (number(max_distance) and float(max_distance) > 0.0):
+        raise ValueError(f"point_normals_max_distance must be a positive distance in metres, got {max_distance!r}")
+    if max_distance is not None and neighbours is None:
+        raise ValueError("point_normals_max_distance bounds the search of point_normals_neighbours: it needs point_normals_neighbours")
+    if neighbours is None:
+        return None
+    if not save_point_cloud:
+        raise ValueError("point_normals_neighbours estimates the normals of the cloud of save_point_cloud: it needs save_point_cloud")
+    return int(neighbours), np.inf if max_distance is None else float(max_distance)
 
 
 def _clean_entries(volume, clean):
@@ -1225,6 +1287,13 @@ def build_parser():
     parser.add_argument("--consistency_relative", default=0.01, type=float, help="largest relative depth difference of an agreeing view")
     parser.add_argument("--save_point_cloud", action="store_true",
                         help="with --filter_consistency: also write the kept pixels as a coloured point cloud (<mesh name>_pointcloud.ply)")
+    parser.add_argument("--point_normals_neighbours", default=None, type=int,
+                        help="with --save_point_cloud: oriented normals of the point cloud (the cleaned one with --clean_points_*) on the "
+                             "device, from this many nearest neighbours (3 .. 32), turned toward the camera that saw each point; the "
+                             "cloud with normals is written additionally as <mesh name>_pointcloud_normals.ply")
+    parser.add_argument("--point_normals_max_distance", default=None, type=float,
+                        help="with --point_normals_neighbours: neighbours are searched within this distance only, metres (bounds the search; "
+                             "a point with fewer than three inside it gets no normal and is left out of the file)")
     parser.add_argument("--clean_points_neighbours", default=None, type=int,
                         help="with --save_point_cloud: statistical outlier removal of the fused cloud on the device, over this many nearest "
                              "neighbours (1 .. 32); the result is written additionally as <mesh name>_pointcloud_clean.ply")

@@ -67,7 +67,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_mesh_components_* and dvmvs_mesh_filter_* (connected components of a triangle mesh and their removal by
  * size); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_knn_fwd, dvmvs_radius_count_fwd and dvmvs_outlier_statistics_fwd (the k nearest neighbours of points,
- * neighbours within a radius, statistical outlier scores); no earlier signature changed, the number stays 11 by the same rule. */
+ * neighbours within a radius, statistical outlier scores); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_point_normals_fwd (oriented normals of points from rows of nearest neighbours); no earlier signature
+ * changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -1060,6 +1062,46 @@ int dvmvs_radius_count_fwd(const float* query, long long N, const float* target,
                            size_t query_workspace_bytes, float radius, int cap, int exclude_same_index, int* count, dvmvs_stream_t stream);
 int dvmvs_outlier_statistics_fwd(const float* dist, const int* index, long long N, int k, double ratio, float* mean, unsigned char* keep,
                                  double* stats, dvmvs_stream_t stream);
+
+/*
+ * Oriented normals of points from rows of nearest neighbours (ABI 11, later addition; csrc/point_normals.hip).  The reference project has
+ * nothing for this: the definition is this project's own (dvmvs/normals.py is its host form; Open3D's estimate_normals followed by
+ * orient_normals_towards_camera_location is the usual tool).
+ *   points [N,3]      fp32: where normals are wanted (used by the orientation only)
+ *   target [M,3]      fp32: the cloud the neighbours come from, usually the same array; M >= 1
+ *   index [N,k]       int32, 3 <= k <= 32: row i as dvmvs_knn_fwd(points, target, k, max_distance, exclude_same_index = 0) wrote it (for a
+ *                     cloud against itself the point is its own slot 0)
+ *   viewpoints [V,3]  fp32 or NULL (then V = 0): where the cloud was seen from
+ *   view [N]          int32 or NULL: the viewpoint of every point; NULL needs V <= 1 (every point was seen from viewpoints[0])
+ *   normals [N,3] fp32, curvature [N] fp32, valid [N] uint8: the outputs.  Coordinates must be FINITE (a precondition, not checked).
+ * All arithmetic is fp64 from the fp32 inputs, +, -, *, / and sqrt only, each operation correctly rounded, no FMA contraction.  Point i:
+ *   1. The VALID slots of row i, in slot order, are those with 0 <= j < M: j0, j1, ..., n of them.  A slot that is -1 or any other value
+ *      outside [0, M) is skipped and never becomes an address.  n < 3: normal (0,0,0), curvature 0, valid 0.
+ *   2. Single-pass moments about the anchor a = target[j0]: for each valid slot in order e = target[j] - a (per component), s_c += e_c,
+ *      S_cd += e_c e_d for (c,d) = (0,0), (0,1), (0,2), (1,1), (1,2), (2,2); all sums start from 0.0.  m_c = s_c / n and
+ *      C_cd = S_cd / n - m_c m_d, mirrored to be symmetric.
+ *   3. A = C is diagonalised by cyclic Jacobi sweeps, the rule of the ICP block above on a 3x3: pairs (p, q) = (0,1), (0,2), (1,2); a zero
+ *      A_pq is skipped; otherwise theta = (A_qq - A_pp) / (2 A_pq), t = +-1 / (|theta| + sqrt(theta theta + 1)) with the sign of theta (+
+ *      for 0), c = 1 / sqrt(t t + 1), s = t c; the columns p, q of A (new_p = c old_p - s old_q, new_q = s old_p + c old_q), then its rows
+ *      p, q likewise, then A_pq = A_qp = 0, then the columns p, q of V (V starts as the identity).  Before each sweep: stop when the three
+ *      off-diagonals are exactly zero; at most 16 sweeps.
+ *   4. lambda = the smallest diagonal entry, the lowest index on a tie; trace = (A_00 + A_11) + A_22.  If trace is not > 0 (coincident
+ *      points): normal 0, curvature 0, valid 0.  Otherwise curvature = fp32(max(lambda, 0) / trace) (a lambda of -0 counts as 0) and
+ *      valid 1.
+ *   5. The normal is that column of V, (x, y, z), divided by sqrt((x x + y y) + z z); it is negated when the first non-zero of (z, y, x)
+ *      is negative: the canonical sign.
+ *   6. With viewpoints: v = viewpoints[view[i]], or viewpoints[0] without view; a view[i] outside [0, V) means "unknown" and keeps the
+ *      canonical sign.  d = (n_x (v_x - p_x) + n_y (v_y - p_y)) + n_z (v_z - p_z) with p = points[i]; the normal is negated when d < 0
+ *      (d = 0 keeps it).  Then each component is rounded to fp32.
+ * One point per lane and nothing crosses lanes, so the outputs are bit-identical run to run and on any stream, and equal to the host
+ * form.  One launch, nothing read by the host.  N == 0 enqueues nothing and returns 0.
+ * DVMVS_EINVAL for a null or misaligned pointer (4 bytes for everything but valid), N < 0, M < 1, k outside [3,32], V < 0, viewpoints
+ * NULL with V > 0 or given with V = 0, view without viewpoints, no view with V > 1; DVMVS_EUNSUPPORTED above 2^28 points.  Nothing is
+ * enqueued in either case.
+ */
+int dvmvs_point_normals_fwd(const float* points, long long N, const float* target, long long M, const int* index, int k,
+                            const float* viewpoints, long long V, const int* view, float* normals, float* curvature, unsigned char* valid,
+                            dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
