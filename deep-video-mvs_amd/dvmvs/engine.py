@@ -709,6 +709,11 @@ class DepthEngine:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DepthEngine runs on an MI355X; there is no CPU execution path in this package")
+        # (before anything is allocated) the encoder halves the frame five times and the decoder doubles its 1/32 map back onto the skip
+        # connections: a size that is no multiple of 32 has no 1/32 map whose x2 up-samplings meet the 1/16 ... 1/2 maps
+        if Config.test_image_height <= 0 or Config.test_image_width <= 0 or Config.test_image_height % 32 or Config.test_image_width % 32:
+            raise ValueError(f"the frame size must be a positive multiple of 32 in both dimensions, got {Config.test_image_width}x{Config.test_image_height} "
+                             "(Config.test_image_width x Config.test_image_height)")
         if os.environ.get(_DETERMINISTIC_MIOPEN[0]) != _DETERMINISTIC_MIOPEN[1] and not _MIOPEN_SWITCH_WAS_PRESET:
             import warnings
             warnings.warn(f"{_DETERMINISTIC_MIOPEN[0]} was changed after dvmvs.engine set it: MIOpen may pick atomically accumulating kernels "

@@ -12,7 +12,16 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [  # (C_in, C_out, H, W, stride): the layers of a 320x256 frame the kernel takes, + a ragged channel count
     (1024, 2048, 8, 10, 1), (512, 512, 8, 10, 1), (256, 512, 16, 20, 2), (512, 256, 16, 20, 1), (288, 256, 16, 20, 1),
-    (256, 256, 16, 20, 1), (64, 40, 8, 10, 1), (32, 1, 16, 20, 1), (128, 256, 32, 40, 2), (48, 20, 32, 40, 2)]
+    (256, 256, 16, 20, 1), (64, 40, 8, 10, 1), (32, 1, 16, 20, 1), (128, 256, 32, 40, 2), (48, 20, 32, 40, 2),
+    # the 320x256 frame's FPN output layers (two waves per split) and its 1/16 depth head as a layer of its own
+    (32, 32, 8, 10, 1), (32, 32, 16, 20, 1), (256, 1, 16, 20, 1),
+    # what frames of other sizes send (tests/engine_size_cases.py): 160x128 -- its 1/16, 1/8 and 1/4 maps are these maps --
+    (64, 128, 32, 40, 2), (128, 1, 16, 20, 1), (128, 128, 16, 20, 1), (128, 256, 16, 20, 2), (160, 128, 16, 20, 1), (256, 1, 8, 10, 1),
+    (256, 128, 16, 20, 1), (256, 256, 8, 10, 1), (288, 256, 8, 10, 1), (512, 256, 8, 10, 1),
+    # and 640x512: its 1/32 and 1/16 maps, and its ConvLSTM convolution (the 16x20 map staged by windows, 32 splits)
+    (512, 512, 16, 20, 1), (256, 512, 32, 40, 2), (1024, 2048, 16, 20, 1)]
+# at batch 1 only: its float64 reference convolution costs what (1024, 2048, 8, 10) at batch 8 does
+BATCH_ONE_ONLY = [(1024, 2048, 16, 20, 1)]
 
 
 @pytest.fixture(scope="module")
@@ -59,9 +68,18 @@ def test_split_count_respects_the_lds_budget(ops):
             assert (C_in // S) * staged_rows * (W + 2) * 4 <= 64 * 1024, (B, C_in, S)
 
 
-@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("shape", BATCH_ONE_ONLY)
+def test_partial_sums_add_up_to_the_convolution_at_batch_one(ops, hip_device, shape):
+    partial_sums_add_up_to_the_convolution(ops, hip_device, shape, 1)
+
+
+@pytest.mark.parametrize("shape", [shape for shape in SHAPES if shape not in BATCH_ONE_ONLY])
 @pytest.mark.parametrize("B", [1, 2, 8])
 def test_partial_sums_add_up_to_the_convolution(ops, hip_device, shape, B):
+    partial_sums_add_up_to_the_convolution(ops, hip_device, shape, B)
+
+
+def partial_sums_add_up_to_the_convolution(ops, hip_device, shape, B):
     C_in, C_out, H, W, stride = shape
     dev = hip_device
     x, w, bias = problem(C_in, C_out, H, W, B, seed=C_in + C_out + B)
@@ -117,20 +135,31 @@ def test_unsupported_shapes_are_refused(ops, hip_device):
         ops.bottleneck_conv_pack(torch.zeros(8, 32, 3, 3))                 # no CPU path
 
 
+# (splits, H, W): the 320x256 frame's ConvLSTM (rows of 80: the four-waves-per-row kernel); 640x512's (rows of 320: the generic kernel, 32 splits)
+GATE_PARTIALS = [(16, 8, 10), (32, 16, 20)]
+
+
 def test_gates_on_partial_sums_equal_gates_on_the_sum(ops, hip_device):
     dev = hip_device
-    g = torch.Generator().manual_seed(5)
-    S = 16
-    parts = (torch.randn(S, 1, 2048, 8, 10, generator=g) * 0.3).to(dev)
-    c0 = torch.randn(1, 512, 8, 10, generator=g).to(dev)
-    total = parts[0].clone()
-    for s in range(1, S):
-        total += parts[s]                          # the kernel's order: ascending, one fp32 addition per split
-    h_a, c_a = torch.zeros_like(c0), c0.clone()
-    ops.lstm_gates_into(total, c_a, h_a)
-    h_b, c_b = torch.zeros_like(c0), c0.clone()
-    ops.lstm_gates_partials_into(parts.reshape(-1), S, c_b, h_b)
-    assert torch.equal(h_a, h_b) and torch.equal(c_a, c_b)
+    for S, H, W in GATE_PARTIALS:
+        assert ops.bottleneck_conv_splits(1, 2048, 1024, H, W, 1) == S      # the split count the ConvLSTM convolution produces on this map
+        g = torch.Generator().manual_seed(5)
+        parts = (torch.randn(S, 1, 2048, H, W, generator=g) * 0.3).to(dev)
+        c0 = torch.randn(1, 512, H, W, generator=g).to(dev)
+        total = parts[0].clone()
+        for s in range(1, S):
+            total += parts[s]                          # the kernel's order: ascending, one fp32 addition per split
+        h_a, c_a = torch.zeros_like(c0), c0.clone()
+        ops.lstm_gates_into(total, c_a, h_a)
+        h_b, c_b = torch.full_like(c0, float("nan")), c0.clone()
+        ops.lstm_gates_partials_into(parts.reshape(-1), S, c_b, h_b)
+        assert torch.equal(h_a, h_b) and torch.equal(c_a, c_b), (S, H, W)
+        # and they are the gates: LayerNorm over the map, CELU, the cell update (float64)
+        i_, f_, o_, g_ = (t.double() for t in torch.split(total, 512, dim=1))
+        norm = lambda t: (t - t.mean(dim=(2, 3), keepdim=True)) / torch.sqrt(t.var(dim=(2, 3), unbiased=False, keepdim=True) + 1e-5)
+        c_want = norm(torch.sigmoid(f_) * c0.double() + torch.sigmoid(i_) * torch.celu(norm(g_)))
+        h_want = torch.sigmoid(o_) * torch.celu(c_want)
+        assert float((c_b.double() - c_want).abs().max()) <= 1e-4 and float((h_b.double() - h_want).abs().max()) <= 1e-4, (S, H, W)
 
 
 def test_engine_with_bottleneck_kernels_equals_the_all_miopen_engine(hip_device):

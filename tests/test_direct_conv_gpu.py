@@ -116,7 +116,12 @@ def test_problems_the_kernel_does_not_take():
         ops.direct_conv_into(x, packed, 3 - tile, None, dst, 32, 3, 1, 0)   # packed for the other tile count
 
 
-@pytest.mark.parametrize("shape", [(256, 16, 20), (128, 32, 40), (64, 64, 80), (32, 128, 160), (32, 256, 320), (5, 7, 9)])
+# (C_in, H, W): the depth heads of a 320x256 frame and a ragged one; then what a 640x512 frame adds (tests/engine_size_cases.py): its widest head
+# on twice the map, and its full-resolution head on a map four times any above
+HEAD_SHAPES = [(256, 16, 20), (128, 32, 40), (64, 64, 80), (32, 128, 160), (32, 256, 320), (5, 7, 9), (256, 32, 40), (32, 512, 640)]
+
+
+@pytest.mark.parametrize("shape", HEAD_SHAPES)
 @pytest.mark.parametrize("batch", [1, 2])
 def test_conv_head_matches_fp64(shape, batch):
     ops = _ops()

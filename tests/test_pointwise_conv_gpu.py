@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import engine_size_cases
+
 pytestmark = pytest.mark.gpu
 
 # (C_in, C_out, H, W)
@@ -15,6 +17,11 @@ FRAME_SHAPES = [
     (192, 1152, 8, 10), (1152, 192, 8, 10), (1152, 320, 8, 10), (320, 32, 8, 10), (96, 32, 16, 20), (40, 32, 32, 40), (24, 32, 64, 80), (16, 32, 128, 160),
 ]
 RAGGED_SHAPES = [(20, 19, 6, 10), (4, 1, 2, 2), (68, 33, 5, 12), (36, 100, 3, 4), (260, 17, 7, 8)]
+# the 1x1 layers of frames of other sizes (tests/engine_size_cases.py: 96x64, 160x128, 256x256, 640x512) that the kernel takes
+SIZE_SHAPES = sorted({p for size in engine_size_cases.SIZES for p in engine_size_cases.EXPECTED[size]["pointwise"]} - set(FRAME_SHAPES))
+# the layers whose epilogue adds the nearest-up-sampled coarser level (the FPN's lateral layers): a 320x256 frame's and a ragged one, then the other sizes'
+LATERAL_SHAPES = [(96, 32, 16, 20), (24, 32, 64, 80), (16, 32, 128, 160), (36, 20, 6, 8)]
+SIZE_LATERAL_SHAPES = sorted({p for size in engine_size_cases.SIZES for p in engine_size_cases.lateral_problems(*size)} - set(LATERAL_SHAPES))
 
 
 def _ops():
@@ -46,7 +53,7 @@ def _tolerance(want):
     return 2e-5 * max(1.0, float(want.abs().max()))      # fp32 sums of <= 1 152 terms of O(1 / sqrt(n))
 
 
-@pytest.mark.parametrize("shape", FRAME_SHAPES + RAGGED_SHAPES)
+@pytest.mark.parametrize("shape", FRAME_SHAPES + RAGGED_SHAPES + SIZE_SHAPES)
 @pytest.mark.parametrize("batch", [1, 2])
 def test_pointwise_conv_matches_fp64(shape, batch):
     ops = _ops()
@@ -79,7 +86,7 @@ def test_residual_of_the_same_shape_is_added_after_the_activation(shape):
         assert float((dst - two).abs().max()) <= _tolerance(want)
 
 
-@pytest.mark.parametrize("shape", [(96, 32, 16, 20), (24, 32, 64, 80), (16, 32, 128, 160), (36, 20, 6, 8)])
+@pytest.mark.parametrize("shape", LATERAL_SHAPES + SIZE_LATERAL_SHAPES)
 def test_half_resolution_residual_is_nearest_upsampled(shape):
     ops = _ops()
     C_in, C_out, H, W = shape
