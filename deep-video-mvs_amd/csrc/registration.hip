@@ -4,6 +4,8 @@
 //   dvmvs_icp_workspace_bytes   : the size of a registration's state block (host arithmetic)
 //   dvmvs_icp_fwd               : enqueues max_iterations iterations; the state block ends with T, the status and the per-iteration record
 //   dvmvs_transform_points_fwd  : p' = fp32(T[:3,:4]) p for a cloud
+//   dvmvs_icp_plane_workspace_bytes, dvmvs_icp_plane_fwd : the same loop, point to plane on the target's normals (second half of the file;
+//                                 dvmvs/errors.py::register_points_plane)
 //
 // One iteration is four steps on the stream; the three kernels of an iteration begin by reading the status word and do nothing unless
 // it says "running" (icp_init_kernel, which sets it, and the stand-alone transform, which has none, do not), so the iterations enqueued
@@ -305,6 +307,226 @@ __global__ __launch_bounds__(kWave) void icp_solve_kernel(const double* __restri
   if (iteration + 1 >= max_iterations) words[kIcpWordStatus] = kIcpLimit;
 }
 
+// ---- point-to-plane ------------------------------------------------------------------------------------------------------------------
+// The same loop with the target's normals (definition: include/dvmvs_hip.h; dvmvs/errors.py::register_points_plane): steps 1 and 2 are the
+// kernels above, step 3 adds 30 moments of the linearised plane residual, step 4 solves the 6x6 normal equations by LDL^T.
+constexpr int kIcpPlaneMoments = 30;                     // n | sum J_a J_b, a <= b [21] | sum J_a r [6] | sum r^2 | sum d^2
+constexpr int kIcpPlaneWordMoments = 18, kIcpPlaneHeadWords = 48;
+constexpr int kIcpPlaneMinInliers = 6;
+constexpr double kIcpPlanePivot = 0x1p-30;
+
+enum IcpPlaneStatus : long long { kIcpDegenerate = 4 };
+
+struct IcpPlaneLayout {
+  size_t inliers_off, fitness_off, rmse_off, rmse_point_off, points_off, dist_off, index_off, partials_off, total;
+  int groups;
+};
+
+IcpPlaneLayout icp_plane_layout(long long n, int max_iterations) {
+  IcpPlaneLayout l;
+  const size_t it = static_cast<size_t>(max_iterations);
+  l.groups = static_cast<int>((n + kIcpGroupPoints - 1) / kIcpGroupPoints);
+  l.inliers_off = kIcpPlaneHeadWords * 8;
+  l.fitness_off = l.inliers_off + it * 8;
+  l.rmse_off = l.fitness_off + it * 8;
+  l.rmse_point_off = l.rmse_off + it * 8;
+  l.points_off = icp_align(l.rmse_point_off + it * 8);
+  l.dist_off = l.points_off + icp_align(static_cast<size_t>(n) * 12);
+  l.index_off = l.dist_off + icp_align(static_cast<size_t>(n) * 4);
+  l.partials_off = l.index_off + icp_align(static_cast<size_t>(n) * 4);
+  l.total = l.partials_off + icp_align(static_cast<size_t>(l.groups) * kIcpPlaneMoments * 8);
+  return l;
+}
+
+__global__ void icp_plane_init_kernel(IcpInit init, double* __restrict__ state) {
+  const int t = threadIdx.x;
+  if (t < 16) state[kIcpWordT + t] = init.t[t];
+  if (t >= kIcpPlaneWordMoments && t < kIcpPlaneHeadWords) state[t] = 0.0;
+  if (t == 0) {
+    long long* words = reinterpret_cast<long long*>(state);
+    words[kIcpWordIterations] = 0;
+    words[kIcpWordStatus] = kIcpRunning;
+  }
+}
+
+__device__ inline void icp_plane_wave_sum(double* v) {
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int k = 0; k < kIcpPlaneMoments; ++k) v[k] += __shfl_xor(v[k], m, kWave);
+  }
+}
+
+__device__ inline bool icp_plane_has_normal(float x, float y, float z) {
+  return x - x == 0.0f && y - y == 0.0f && z - z == 0.0f && (x != 0.0f || y != 0.0f || z != 0.0f);
+}
+
+__global__ __launch_bounds__(kIcpBlock) void icp_plane_moments_kernel(const float* __restrict__ moved, int n, const float* __restrict__ target,
+                                                                      const float* __restrict__ normals, int m, const float* __restrict__ dist,
+                                                                      const int* __restrict__ index, float max_distance,
+                                                                      const long long* __restrict__ status, double* __restrict__ partials) {
+  __shared__ double s_wave[kIcpBlock / kWave][kIcpPlaneMoments];
+  if (*status != kIcpRunning) return;
+  const int t = threadIdx.x;
+  double v[kIcpPlaneMoments];
+#pragma unroll
+  for (int k = 0; k < kIcpPlaneMoments; ++k) v[k] = 0.0;
+  const double o[3] = {static_cast<double>(moved[0]), static_cast<double>(moved[1]), static_cast<double>(moved[2])};     // n >= 1
+  const long long first = static_cast<long long>(blockIdx.x) * kIcpGroupPoints;
+#pragma unroll
+  for (int r = 0; r < kIcpRows; ++r) {
+    const long long i = first + r * kIcpBlock + t;
+    if (i >= n) break;
+    const float d = dist[i];
+    const int j = index[i];
+    if (!(d <= max_distance) || j < 0 || j >= m) continue;         // trimmed (the index test cannot fail after a query; it keeps the reads in bounds)
+    const size_t po = static_cast<size_t>(i) * 3, qo = static_cast<size_t>(j) * 3;
+    const float nx = normals[qo], ny = normals[qo + 1], nz = normals[qo + 2];
+    if (!icp_plane_has_normal(nx, ny, nz)) continue;                 // a target without a normal pairs with nothing
+    const double p[3] = {static_cast<double>(moved[po]), static_cast<double>(moved[po + 1]), static_cast<double>(moved[po + 2])};
+    const double q[3] = {static_cast<double>(target[qo]), static_cast<double>(target[qo + 1]), static_cast<double>(target[qo + 2])};
+    const double nn[3] = {static_cast<double>(nx), static_cast<double>(ny), static_cast<double>(nz)};
+    const double e[3] = {p[0] - o[0], p[1] - o[1], p[2] - o[2]};
+    const double res = ((p[0] - q[0]) * nn[0] + (p[1] - q[1]) * nn[1]) + (p[2] - q[2]) * nn[2];
+    const double J[6] = {e[1] * nn[2] - e[2] * nn[1], e[2] * nn[0] - e[0] * nn[2], e[0] * nn[1] - e[1] * nn[0], nn[0], nn[1], nn[2]};
+    const double dd = static_cast<double>(d);
+    v[0] += 1.0;
+    int c = 1;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+      for (int b = a; b < 6; ++b) v[c++] += J[a] * J[b];
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[22 + a] += J[a] * res;
+    v[28] += res * res;
+    v[29] += dd * dd;
+  }
+  icp_plane_wave_sum(v);
+  if (t % kWave == 0) {
+#pragma unroll
+    for (int k = 0; k < kIcpPlaneMoments; ++k) s_wave[t / kWave][k] = v[k];
+  }
+  __syncthreads();
+  if (t < kIcpPlaneMoments) {
+    double s = s_wave[0][t];
+    for (int w = 1; w < kIcpBlock / kWave; ++w) s += s_wave[w][t];
+    partials[static_cast<size_t>(blockIdx.x) * kIcpPlaneMoments + t] = s;
+  }
+}
+
+// `moved`: the moved source of this iteration; its first point is the origin o of the rotation
+__global__ __launch_bounds__(kWave) void icp_plane_solve_kernel(const double* __restrict__ partials, int groups, long long n_points, int iteration,
+                                                                int max_iterations, double tolerance, const float* __restrict__ moved,
+                                                                double* __restrict__ state, long long* __restrict__ inliers,
+                                                                double* __restrict__ fitness, double* __restrict__ rmse,
+                                                                double* __restrict__ rmse_point) {
+  long long* words = reinterpret_cast<long long*>(state);
+  if (words[kIcpWordStatus] != kIcpRunning) return;
+  double v[kIcpPlaneMoments];
+#pragma unroll
+  for (int k = 0; k < kIcpPlaneMoments; ++k) v[k] = 0.0;
+  for (int g = threadIdx.x; g < groups; g += kWave) {
+#pragma unroll
+    for (int k = 0; k < kIcpPlaneMoments; ++k) v[k] += partials[static_cast<size_t>(g) * kIcpPlaneMoments + k];
+  }
+  icp_plane_wave_sum(v);
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int k = 0; k < kIcpPlaneMoments; ++k) state[kIcpPlaneWordMoments + k] = v[k];
+  const double n = v[0];
+  const double rmse_k = n > 0.0 ? sqrt(v[28] / n) : 0.0;
+  const double fitness_k = n / static_cast<double>(n_points);
+  inliers[iteration] = static_cast<long long>(n);
+  fitness[iteration] = fitness_k;
+  rmse[iteration] = rmse_k;
+  rmse_point[iteration] = n > 0.0 ? sqrt(v[29] / n) : 0.0;
+  words[kIcpWordIterations] = iteration + 1;
+  if (n < static_cast<double>(kIcpPlaneMinInliers)) {
+    words[kIcpWordStatus] = kIcpTooFew;
+    return;
+  }
+  if (iteration >= 1 && fabs(rmse_k - rmse[iteration - 1]) < tolerance && fabs(fitness_k - fitness[iteration - 1]) < tolerance) {
+    words[kIcpWordStatus] = kIcpConverged;
+    return;
+  }
+  // A x = -b by LDL^T without pivoting: A = sum J J^T (the lower triangle is read), b = sum J r
+  double A[6][6], L[6][6], D[6], x[6];
+  {
+    int c = 1;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+      for (int b = a; b < 6; ++b) A[b][a] = v[c++];
+    }
+  }
+  bool degenerate = false;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d = d - (L[j][k] * L[j][k]) * D[k];
+    if (!(d > kIcpPlanePivot * A[j][j])) degenerate = true;      // (what follows a failed pivot is not used)
+    D[j] = d;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s = s - (L[i][k] * L[j][k]) * D[k];
+      L[i][j] = s / d;
+    }
+  }
+  if (degenerate) {
+    words[kIcpWordStatus] = kIcpDegenerate;
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = -v[22 + i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s = s - L[i][k] * x[k];
+    x[i] = s;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) x[i] = x[i] / D[i];
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double s = x[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
+    x[i] = s;
+  }
+  double qx = x[0] / 2.0, qy = x[1] / 2.0, qz = x[2] / 2.0;
+  const double norm = sqrt(((1.0 + qx * qx) + qy * qy) + qz * qz);
+  const double w = 1.0 / norm;
+  qx = qx / norm;
+  qy = qy / norm;
+  qz = qz / norm;
+  double R[9];
+  R[0] = 1.0 - 2.0 * (qy * qy + qz * qz);
+  R[1] = 2.0 * (qx * qy - w * qz);
+  R[2] = 2.0 * (qx * qz + w * qy);
+  R[3] = 2.0 * (qx * qy + w * qz);
+  R[4] = 1.0 - 2.0 * (qx * qx + qz * qz);
+  R[5] = 2.0 * (qy * qz - w * qx);
+  R[6] = 2.0 * (qx * qz - w * qy);
+  R[7] = 2.0 * (qy * qz + w * qx);
+  R[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+  const double o[3] = {static_cast<double>(moved[0]), static_cast<double>(moved[1]), static_cast<double>(moved[2])};
+  double shift[3], next[12];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) shift[a] = (o[a] - ((R[a * 3] * o[0] + R[a * 3 + 1] * o[1]) + R[a * 3 + 2] * o[2])) + x[3 + a];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      next[a * 4 + c] = ((R[a * 3] * state[c] + R[a * 3 + 1] * state[4 + c]) + R[a * 3 + 2] * state[8 + c]) + shift[a] * state[12 + c];
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) state[kIcpWordT + i] = next[i];
+  if (iteration + 1 >= max_iterations) words[kIcpWordStatus] = kIcpLimit;
+}
+
 bool icp_finite(double x) { return x - x == 0.0; }
 
 }  // namespace
@@ -355,6 +577,57 @@ extern "C" int dvmvs_icp_fwd(const float* source, long long N, const float* targ
     hipLaunchKernelGGL(icp_moments_kernel, dim3(l.groups), block, 0, s, moved, n, target, m, dist, index, max_distance, status, partials);
     hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(kWave), 0, s, partials, l.groups, N, k, max_iterations, with_scale, tolerance, head,
                        inliers, fitness, rmse);
+  }
+  return launch_status();
+}
+
+extern "C" size_t dvmvs_icp_plane_workspace_bytes(long long N, int max_iterations) {
+  if (N <= 0 || N > dvmvs::kIcpMaxPoints || max_iterations < 1 || max_iterations > dvmvs::kIcpMaxIterations) return 0;
+  return dvmvs::icp_plane_layout(N, max_iterations).total;
+}
+
+extern "C" int dvmvs_icp_plane_fwd(const float* source, long long N, const float* target, const float* target_normals, long long M,
+                                   const void* grid_workspace, void* query_workspace, size_t query_workspace_bytes, float max_distance,
+                                   int max_iterations, double tolerance, const double* init_host, void* state, size_t state_bytes,
+                                   dvmvs_stream_t stream) {
+  using namespace dvmvs;
+  if (!source || !target || !target_normals || !grid_workspace || !query_workspace || !state) return DVMVS_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(source) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(target_normals)) % 4 != 0 ||
+      (reinterpret_cast<uintptr_t>(grid_workspace) | reinterpret_cast<uintptr_t>(query_workspace) | reinterpret_cast<uintptr_t>(state)) % 16 != 0)
+    return DVMVS_EINVAL;
+  if (N < 1 || M < 1 || max_iterations < 1) return DVMVS_EINVAL;
+  if (!(max_distance > 0.0f) || !(tolerance >= 0.0)) return DVMVS_EINVAL;            // NaN fails both
+  IcpInit init;
+  for (int i = 0; i < 16; ++i) {
+    init.t[i] = init_host ? init_host[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    if (!icp_finite(init.t[i])) return DVMVS_EINVAL;
+  }
+  if (N > kIcpMaxPoints || M > kIcpMaxPoints || max_iterations > kIcpMaxIterations) return DVMVS_EUNSUPPORTED;
+  const IcpPlaneLayout l = icp_plane_layout(N, max_iterations);
+  if (state_bytes < l.total || query_workspace_bytes < dvmvs_nearest_query_workspace_bytes(N, M)) return DVMVS_EINVAL;
+  char* base = static_cast<char*>(state);
+  double* head = reinterpret_cast<double*>(base);
+  long long* status = reinterpret_cast<long long*>(base) + kIcpWordStatus;
+  long long* inliers = reinterpret_cast<long long*>(base + l.inliers_off);
+  double* fitness = reinterpret_cast<double*>(base + l.fitness_off);
+  double* rmse = reinterpret_cast<double*>(base + l.rmse_off);
+  double* rmse_point = reinterpret_cast<double*>(base + l.rmse_point_off);
+  float* moved = reinterpret_cast<float*>(base + l.points_off);
+  float* dist = reinterpret_cast<float*>(base + l.dist_off);
+  int* index = reinterpret_cast<int*>(base + l.index_off);
+  double* partials = reinterpret_cast<double*>(base + l.partials_off);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n = static_cast<int>(N), m = static_cast<int>(M);
+  const dim3 points((n + kIcpBlock - 1) / kIcpBlock), block(kIcpBlock);
+  hipLaunchKernelGGL(icp_plane_init_kernel, dim3(1), dim3(kWave), 0, s, init, head);
+  for (int k = 0; k < max_iterations; ++k) {
+    hipLaunchKernelGGL(icp_transform_kernel, points, block, 0, s, source, n, head, status, moved);
+    const int rc = dvmvs_nearest_distance_fwd(moved, N, target, M, grid_workspace, query_workspace, query_workspace_bytes, dist, index, stream);
+    if (rc != 0) return rc;                                  // a HIP error only: every argument the launcher refuses was checked above
+    hipLaunchKernelGGL(icp_plane_moments_kernel, dim3(l.groups), block, 0, s, moved, n, target, target_normals, m, dist, index, max_distance,
+                       status, partials);
+    hipLaunchKernelGGL(icp_plane_solve_kernel, dim3(1), dim3(kWave), 0, s, partials, l.groups, N, k, max_iterations, tolerance, moved, head,
+                       inliers, fitness, rmse, rmse_point);
   }
   return launch_status();
 }

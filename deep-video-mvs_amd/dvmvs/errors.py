@@ -425,12 +425,282 @@ def register_points_device(source, target, max_distance, init=None, max_iteratio
                             grid=grid)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# point-to-plane registration: the same loop with the target's normals, a 6x6 linearised step instead of Horn's closed form
+# ----------------------------------------------------------------------------------------------------------------------
+REGISTRATION_PLANE_STATUS = ("running", "converged", "too few correspondences", "iteration limit", "degenerate geometry")
+REGISTRATION_PLANE_MOMENTS = 30
+REGISTRATION_PLANE_MIN_INLIERS = 6
+REGISTRATION_PLANE_PIVOT = 2.0 ** -30           # a pivot of the LDL^T must exceed this share of its diagonal entry
+
+
+def has_normal(normals):
+    """bool [M]: the rows of ``normals`` float32 [M,3] that are finite and not all zero."""
+    normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+    return np.isfinite(normals).all(axis=1) & (normals != 0.0).any(axis=1)
+
+
+def _ordered_sums(terms):
+    """The column sums of ``terms`` float64 [N,C] in the order of ``registration_moments``: blocks of 1024 rows, 256 strided threads x 4
+    rows, wave butterfly, waves in order; then 64 strided lanes over the block sums and one more butterfly."""
+    n, columns = terms.shape
+    group = _ICP_BLOCK * _ICP_ROWS
+    groups = -(-n // group)
+    padded = np.zeros((groups * group, columns), dtype=np.float64)
+    padded[:n] = terms
+    padded = padded.reshape(groups, _ICP_ROWS, _ICP_BLOCK, columns)
+    threads = np.zeros((groups, _ICP_BLOCK, columns), dtype=np.float64)
+    for r in range(_ICP_ROWS):
+        threads = threads + padded[:, r]
+    waves = _butterfly(threads.reshape(groups, _ICP_BLOCK // _ICP_WAVE, _ICP_WAVE, columns))[:, :, 0]
+    partials = waves[:, 0]
+    for w in range(1, _ICP_BLOCK // _ICP_WAVE):
+        partials = partials + waves[:, w]
+    rounds = -(-groups // _ICP_WAVE)
+    padded = np.zeros((rounds * _ICP_WAVE, columns), dtype=np.float64)
+    padded[:groups] = partials
+    padded = padded.reshape(rounds, _ICP_WAVE, columns)
+    lanes = np.zeros((_ICP_WAVE, columns), dtype=np.float64)
+    for r in range(rounds):
+        lanes = lanes + padded[r]
+    return _butterfly(lanes)[0]
+
+
+def registration_plane_moments(moved, target_points, target_normals, dist, inlier):
+    """The 30 float64 sums of one point-to-plane iteration over the inliers: n | sum J_a J_b for a <= b, row-major [21] | sum J_a r [6] |
+    sum r^2 | sum d^2, with p = moved_i, q, n = the nearest target and its normal, o = moved_0 (inlier or not),
+    r = ((p0-q0) n0 + (p1-q1) n1) + (p2-q2) n2, c = (p - o) x n, J = (c0, c1, c2, n0, n1, n2); every product and sum rounded to float64,
+    nothing fused; added in the order of ``registration_moments``.  ``target_points``, ``target_normals``: q_i and n_i per moved point."""
+    p, q, nn, d = (np.asarray(a, dtype=np.float32).astype(np.float64) for a in (moved, target_points, target_normals, dist))
+    inlier = np.asarray(inlier, dtype=bool)
+    n = len(p)
+    terms = np.empty((n, REGISTRATION_PLANE_MOMENTS), dtype=np.float64)
+    with np.errstate(all="ignore"):
+        e = p - p[0]
+        r = ((p[:, 0] - q[:, 0]) * nn[:, 0] + (p[:, 1] - q[:, 1]) * nn[:, 1]) + (p[:, 2] - q[:, 2]) * nn[:, 2]
+        J = np.stack([e[:, 1] * nn[:, 2] - e[:, 2] * nn[:, 1], e[:, 2] * nn[:, 0] - e[:, 0] * nn[:, 2], e[:, 0] * nn[:, 1] - e[:, 1] * nn[:, 0],
+                      nn[:, 0], nn[:, 1], nn[:, 2]], axis=1)
+        terms[:, 0] = 1.0
+        column = 1
+        for a in range(6):
+            for b in range(a, 6):
+                terms[:, column] = J[:, a] * J[:, b]
+                column += 1
+        for a in range(6):
+            terms[:, 22 + a] = J[:, a] * r
+        terms[:, 28] = r * r
+        terms[:, 29] = d * d
+    terms[~inlier] = 0.0                                       # a skipped point and an added +0.0 are the same bits
+    return _ordered_sums(terms)
+
+
+def _registration_plane_moments_loop(moved, target_points, target_normals, dist, inlier):
+    """``registration_plane_moments`` point by point in Python floats, as a thread of the device adds them: a trimmed point is skipped."""
+    rows = [np.asarray(a, dtype=np.float32).astype(np.float64).tolist() for a in (moved, target_points, target_normals)]
+    d = np.asarray(dist, dtype=np.float32).astype(np.float64).tolist()
+    count, C = len(d), REGISTRATION_PLANE_MOMENTS
+    o = rows[0][0]
+
+    def butterfly(lanes):
+        for m in (32, 16, 8, 4, 2, 1):
+            lanes = [[lanes[l][k] + lanes[l ^ m][k] for k in range(C)] for l in range(_ICP_WAVE)]
+        return lanes[0]
+
+    group = _ICP_BLOCK * _ICP_ROWS
+    partials = []
+    for first in range(0, count, group):
+        threads = [[0.0] * C for _ in range(_ICP_BLOCK)]
+        for t in range(_ICP_BLOCK):
+            v = threads[t]
+            for i in range(first + t, min(first + group, count), _ICP_BLOCK):
+                if not inlier[i]:
+                    continue
+                p, q, n = rows[0][i], rows[1][i], rows[2][i]
+                e = [p[0] - o[0], p[1] - o[1], p[2] - o[2]]
+                r = ((p[0] - q[0]) * n[0] + (p[1] - q[1]) * n[1]) + (p[2] - q[2]) * n[2]
+                J = [e[1] * n[2] - e[2] * n[1], e[2] * n[0] - e[0] * n[2], e[0] * n[1] - e[1] * n[0], n[0], n[1], n[2]]
+                v[0] += 1.0
+                column = 1
+                for a in range(6):
+                    for b in range(a, 6):
+                        v[column] += J[a] * J[b]
+                        column += 1
+                for a in range(6):
+                    v[22 + a] += J[a] * r
+                v[28] += r * r
+                v[29] += d[i] * d[i]
+        waves = [butterfly(threads[w * _ICP_WAVE:(w + 1) * _ICP_WAVE]) for w in range(_ICP_BLOCK // _ICP_WAVE)]
+        total = waves[0]
+        for w in waves[1:]:
+            total = [a + b for a, b in zip(total, w)]
+        partials.append(total)
+    lanes = [[0.0] * C for _ in range(_ICP_WAVE)]
+    for lane in range(_ICP_WAVE):
+        for b in range(lane, len(partials), _ICP_WAVE):
+            lanes[lane] = [x + y for x, y in zip(lanes[lane], partials[b])]
+    return np.array(butterfly(lanes), dtype=np.float64)
+
+
+def _ldlt_solve(A, b):
+    """x with A x = -b for a symmetric 6x6 ``A`` (lists of Python floats; the lower triangle is read), by LDL^T without pivoting in the
+    order include/dvmvs_hip.h states; None when a pivot is not above ``REGISTRATION_PLANE_PIVOT`` times its diagonal entry."""
+    L = [[0.0] * 6 for _ in range(6)]
+    D = [0.0] * 6
+    for j in range(6):
+        d = A[j][j]
+        for k in range(j):
+            d = d - (L[j][k] * L[j][k]) * D[k]
+        if not d > REGISTRATION_PLANE_PIVOT * A[j][j]:
+            return None
+        D[j] = d
+        for i in range(j + 1, 6):
+            s = A[i][j]
+            for k in range(j):
+                s = s - (L[i][k] * L[j][k]) * D[k]
+            L[i][j] = s / d
+    x = [0.0] * 6
+    for i in range(6):
+        s = -b[i]
+        for k in range(i):
+            s = s - L[i][k] * x[k]
+        x[i] = s
+    for i in range(6):
+        x[i] = x[i] / D[i]
+    for i in range(5, -1, -1):
+        s = x[i]
+        for k in range(i + 1, 6):
+            s = s - L[k][i] * x[k]
+        x[i] = s
+    return x
+
+
+def _plane_system(v):
+    A = [[0.0] * 6 for _ in range(6)]
+    column = 1
+    for a in range(6):
+        for b in range(a, 6):
+            A[a][b] = A[b][a] = v[column]
+            column += 1
+    return A, v[22:28]
+
+
+def registration_plane_solve(moments, T, origin):
+    """The update of one point-to-plane iteration from its 30 sums: the float64 4x4 ``[R, (o - R o) + t; 0 1] T`` with ``origin`` = o (the
+    first moved point), or None for degenerate geometry (a pivot of the LDL^T at or below 2^-30 of its diagonal entry).  x = (alpha, beta,
+    gamma, t) solves (sum J J^T) x = -(sum J r); the rotation is that of the unit quaternion (1, alpha/2, beta/2, gamma/2) / norm.  Every
+    operation in float64, in the order include/dvmvs_hip.h states."""
+    v = [float(m) for m in moments]
+    T = [[float(e) for e in row] for row in np.asarray(T, dtype=np.float64)]
+    o = [float(e) for e in np.asarray(origin, dtype=np.float32)]
+    with np.errstate(all="ignore"):
+        A, b = _plane_system(v)
+        step = _ldlt_solve(A, b)
+        if step is None:
+            return None
+        x, y, z = step[0] / 2.0, step[1] / 2.0, step[2] / 2.0
+        norm = math.sqrt(((1.0 + x * x) + y * y) + z * z)
+        w, x, y, z = 1.0 / norm, x / norm, y / norm, z / norm
+        R = [1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+             2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+             2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)]
+        shift = [(o[a] - ((R[a * 3] * o[0] + R[a * 3 + 1] * o[1]) + R[a * 3 + 2] * o[2])) + step[3 + a] for a in range(3)]
+        out = [[((R[a * 3] * T[0][c] + R[a * 3 + 1] * T[1][c]) + R[a * 3 + 2] * T[2][c]) + shift[a] * T[3][c] for c in range(4)]
+               for a in range(3)]
+    return np.array(out + [T[3]], dtype=np.float64)
+
+
+def register_points_plane(source, target, target_normals, max_distance, init=None, max_iterations=30, tolerance=1e-6):
+    """Registers ``source`` [N,3] to ``target`` [M,3] with normals ``target_normals`` float32 [M,3] by trimmed point-to-plane ICP:
+    ``(T float64 [4,4], info)``.  The host definition that ``dvmvs.hip.registration.icp_plane`` reproduces bit for bit (include/dvmvs_hip.h
+    restates it).  A normal that is all zero or not finite is "no normal"; a normal's sign does not matter (every term is even in it).
+    Iteration k, from ``T_0 = init`` (or the identity): the source moved by ``transform_points``; its nearest targets by
+    ``nearest_distances``; the inliers ``d <= float32(max_distance)`` whose target has a normal; their ``registration_plane_moments``;
+    rmse_k = sqrt(sum r^2 / n) (the plane residual; 0 without inliers), rmse_point_k = sqrt(sum d^2 / n) and fitness_k = n / N, which
+    describe T_k; fewer than 6 inliers stop with status 2; from k = 1 on, rmse and fitness both within ``tolerance`` (strictly) of the
+    iteration before stop with status 1 and leave T; otherwise ``registration_plane_solve`` gives T_{k+1}, or stops with status 4 and leaves
+    T where the geometry does not fix all six freedoms; status 3 at the limit.  ``info``: ``iterations``, ``status`` (an index of
+    ``REGISTRATION_PLANE_STATUS``), and per recorded iteration ``inliers`` (int64), ``fitness``, ``rmse``, ``rmse_point`` (float64), with
+    ``moments`` [30], the sums of the last one."""
+    source = np.ascontiguousarray(source, dtype=np.float32).reshape(-1, 3)
+    target = np.ascontiguousarray(target, dtype=np.float32).reshape(-1, 3)
+    target_normals = np.ascontiguousarray(target_normals, dtype=np.float32)
+    max_distance, tolerance, max_iterations = np.float32(max_distance), float(tolerance), int(max_iterations)
+    if len(source) == 0 or len(target) == 0:
+        raise ValueError("register_points_plane: both point clouds must hold at least one point")
+    if target_normals.shape != target.shape:
+        raise ValueError(f"register_points_plane: target_normals must be float32 {target.shape} like the target, got {target_normals.shape}")
+    if not max_distance > 0.0 or not tolerance >= 0.0:
+        raise ValueError(f"register_points_plane: max_distance must be positive and tolerance not negative, got {max_distance}, {tolerance}")
+    if not 1 <= max_iterations <= REGISTRATION_MAX_ITERATIONS:
+        raise ValueError(f"register_points_plane: max_iterations must be in 1 .. {REGISTRATION_MAX_ITERATIONS}, got {max_iterations}")
+    T = np.eye(4, dtype=np.float64) if init is None else np.array(init, dtype=np.float64)
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError("register_points_plane: init must be a finite 4x4 matrix")
+    with_normal = has_normal(target_normals)
+    inliers, fitness, rmse, rmse_point = [], [], [], []
+    status, moments = 0, np.zeros(REGISTRATION_PLANE_MOMENTS, dtype=np.float64)
+    for k in range(max_iterations):
+        moved = transform_points(source, T)
+        dist, index = nearest_distances(moved, target, return_index=True)
+        moments = registration_plane_moments(moved, target[index], target_normals[index], dist, (dist <= max_distance) & with_normal[index])
+        n = float(moments[0])
+        inliers.append(int(n))
+        fitness.append(n / float(len(source)))
+        rmse.append(math.sqrt(float(moments[28]) / n) if n > 0.0 else 0.0)
+        rmse_point.append(math.sqrt(float(moments[29]) / n) if n > 0.0 else 0.0)
+        if n < float(REGISTRATION_PLANE_MIN_INLIERS):
+            status = 2
+            break
+        if k >= 1 and abs(rmse[k] - rmse[k - 1]) < tolerance and abs(fitness[k] - fitness[k - 1]) < tolerance:
+            status = 1
+            break
+        update = registration_plane_solve(moments, T, moved[0])
+        if update is None:
+            status = 4
+            break
+        T = update
+        if k + 1 == max_iterations:
+            status = 3
+    info = {"iterations": len(inliers), "status": status, "inliers": np.array(inliers, dtype=np.int64),
+            "fitness": np.array(fitness, dtype=np.float64), "rmse": np.array(rmse, dtype=np.float64),
+            "rmse_point": np.array(rmse_point, dtype=np.float64), "moments": moments}
+    return T, info
+
+
+def register_points_plane_device(source, target, target_normals, max_distance, init=None, max_iterations=30, tolerance=1e-6, grid=None):
+    """``register_points_plane`` for device tensors (``dvmvs.hip.registration.icp_plane``): the same bits, ``T`` and every entry of ``info``
+    on the GPU, nothing read by the call.  ``grid``: an existing ``ops.nearest_build`` workspace of ``target``."""
+    from dvmvs.hip import registration
+    return registration.icp_plane(source, target, target_normals, max_distance, init=init, max_iterations=max_iterations, tolerance=tolerance,
+                                  grid=grid)
+
+
 def _check_alignment(name, align_distance, align_scale, align_init, return_transform):
     if align_distance is None and (align_scale or align_init is not None or return_transform):
         raise ValueError(f"{name}: align_scale, align_init and return_transform say how align_distance registers: they need align_distance")
 
 
+def _check_plane(name, align_plane, align_distance, align_scale, gt_normals, gt_replaced, neighbours, normal_distance):
+    """The point-to-plane keywords of the scoring functions: ``align_plane`` needs ``align_distance`` and excludes ``align_scale``; the
+    other three say how it registers."""
+    if not isinstance(align_plane, (bool, np.bool_)):
+        raise ValueError(f"{name}: align_plane must be a bool, got {align_plane!r}")
+    if not align_plane:
+        if gt_normals is not None or neighbours != 20 or normal_distance != np.inf:
+            raise ValueError(f"{name}: gt_normals, align_normal_neighbours and align_normal_distance say how align_plane registers: they need "
+                             f"align_plane")
+        return
+    if align_distance is None:
+        raise ValueError(f"{name}: align_plane says how align_distance registers: it needs align_distance")
+    if align_scale:
+        raise ValueError(f"{name}: align_plane finds a rigid motion; it excludes align_scale")
+    if gt_normals is not None and gt_replaced:
+        raise ValueError(f"{name}: gt_normals are the normals of gt_points as given; face sampling and voxel down-sampling replace those "
+                         f"points (leave gt_normals out: the normals are then estimated)")
+
+
 def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05, pred_faces=None, gt_faces=None, sample_density=None, voxel=None,
+                                  align_plane=False, gt_normals=None, align_normal_neighbours=20, align_normal_distance=np.inf,
                                   align_distance=None, align_scale=False, align_init=None, return_transform=False):
     """The 3-D reconstruction metrics of the Atlas / NeuralRecon / SimpleRecon evaluations between a predicted point set [N,3] and a
     ground-truth point set [M,3], float32 [6] in the order of ``RECONSTRUCTION_METRICS``:
@@ -448,14 +718,28 @@ def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05, pred_f
     ``align_distance`` (metres): the prediction's prepared point set is first registered to the ground truth's by ``register_points`` with
     that inlier distance (``align_scale``: a similarity instead of a rigid motion; ``align_init``: a 4x4 to start from), moved by the
     result (``transform_points``) and then scored, as the Tanks-and-Temples evaluation does; ``return_transform``: return
-    ``(row, T float64 [4,4])``.  With ``align_distance`` at None nothing is registered and the row is what it is without the keywords."""
+    ``(row, T float64 [4,4])``.  With ``align_distance`` at None nothing is registered and the row is what it is without the keywords.
+
+    ``align_plane`` (needs ``align_distance``, excludes ``align_scale``): the registration is ``register_points_plane``, point-to-plane
+    on the ground truth's normals, which does not crawl along walls and floors as point-to-point does.  ``gt_normals`` float32 [M,3]: the
+    normals of ``gt_points`` as given (an error together with ``gt_faces`` sampling or ``voxel``, which replace the points); without
+    them the normals are ``dvmvs.normals.estimate_normals`` of the prepared ground-truth points from ``align_normal_neighbours`` nearest
+    points within ``align_normal_distance``."""
     _check_alignment("compute_reconstruction_errors", align_distance, align_scale, align_init, return_transform)
+    _check_plane("compute_reconstruction_errors", align_plane, align_distance, align_scale, gt_normals,
+                 (gt_faces is not None and sample_density is not None) or voxel is not None, align_normal_neighbours, align_normal_distance)
     pred_points = prepare_points(pred_points, pred_faces, sample_density, voxel)
     gt_points = prepare_points(gt_points, gt_faces, sample_density, voxel)
     if len(pred_points) == 0 or len(gt_points) == 0:
         raise ValueError("compute_reconstruction_errors: both point clouds must hold at least one point")
     transform = None
-    if align_distance is not None:
+    if align_plane:
+        if gt_normals is None:
+            from dvmvs.normals import estimate_normals
+            gt_normals = estimate_normals(gt_points, align_normal_neighbours, align_normal_distance)[0]
+        transform, _ = register_points_plane(pred_points, gt_points, gt_normals, align_distance, init=align_init)
+        pred_points = transform_points(pred_points, transform)
+    elif align_distance is not None:
         transform, _ = register_points(pred_points, gt_points, align_distance, init=align_init, with_scale=align_scale)
         pred_points = transform_points(pred_points, transform)
     row = reconstruction_metrics_from_distances(nearest_distances(pred_points, gt_points), nearest_distances(gt_points, pred_points),
@@ -464,7 +748,8 @@ def compute_reconstruction_errors(pred_points, gt_points, threshold=0.05, pred_f
 
 
 def compute_reconstruction_errors_device(pred_points, gt_points, threshold=0.05, counts=None, pred_faces=None, gt_faces=None,
-                                         sample_density=None, voxel=None, align_distance=None, align_scale=False, align_init=None,
+                                         sample_density=None, voxel=None, align_plane=False, gt_normals=None, align_normal_neighbours=20,
+                                         align_normal_distance=np.inf, align_distance=None, align_scale=False, align_init=None,
                                          return_transform=False):
     """``compute_reconstruction_errors`` for point sets that live on the GPU (float32 [N,3] and [M,3] device tensors, both non-empty):
     a float32 device tensor [6].  Two grid builds, two nearest-point queries (csrc/nearest_points.hip: the distances are the host
@@ -474,15 +759,19 @@ def compute_reconstruction_errors_device(pred_points, gt_points, threshold=0.05,
     (csrc/surface_sample.hip: the host definitions' bits; each sampling and each down-sampling reads its output's size once).
     ``align_distance``, ``align_scale``, ``align_init`` (a HOST 4x4) and ``return_transform`` as in the host function: the registration
     (``dvmvs.hip.registration.icp``: the host definition's bits, no host read) uses the ground truth's grid, which then also serves the
-    accuracy query; the transform comes back as a float64 [4,4] device tensor."""
+    accuracy query; the transform comes back as a float64 [4,4] device tensor.  ``align_plane``, ``gt_normals`` (a float32 [M,3] device
+    tensor), ``align_normal_neighbours`` and ``align_normal_distance`` as in the host function (``dvmvs.hip.registration.icp_plane``);
+    normals that are not given are estimated on the same grid (``dvmvs.hip.normals.estimate_normals``)."""
     _check_alignment("compute_reconstruction_errors_device", align_distance, align_scale, align_init, return_transform)
+    _check_plane("compute_reconstruction_errors_device", align_plane, align_distance, align_scale, gt_normals,
+                 (gt_faces is not None and sample_density is not None) or voxel is not None, align_normal_neighbours, align_normal_distance)
     row, transform, _ = _score_device(pred_points, gt_points, threshold, counts, pred_faces, gt_faces, sample_density, voxel, align_distance,
-                                      align_scale, align_init)
+                                      align_scale, align_init, align_plane, gt_normals, align_normal_neighbours, align_normal_distance)
     return (row, transform) if return_transform else row
 
 
 def _score_device(pred_points, gt_points, threshold, counts, pred_faces, gt_faces, sample_density, voxel, align_distance, align_scale,
-                  align_init):
+                  align_init, align_plane=False, gt_normals=None, align_normal_neighbours=20, align_normal_distance=np.inf):
     """``compute_reconstruction_errors_device``: ``(row, transform or None, the registration's info or None)``."""
     from dvmvs.hip import ops      # (imported here: this module stays importable, and the host functions usable, without a GPU)
     transform = info = None
@@ -497,7 +786,13 @@ def _score_device(pred_points, gt_points, threshold, counts, pred_faces, gt_face
     else:       # one grid of the ground truth serves the registration's queries and the accuracy query
         from dvmvs.hip import registration
         grid = ops.nearest_build(gt_points)
-        transform, info = registration.icp(pred_points, gt_points, align_distance, init=align_init, with_scale=align_scale, grid=grid)
+        if align_plane:
+            if gt_normals is None:
+                from dvmvs.hip import normals
+                gt_normals = normals.estimate_normals(gt_points, align_normal_neighbours, align_normal_distance, grid=grid)[0]
+            transform, info = registration.icp_plane(pred_points, gt_points, gt_normals, align_distance, init=align_init, grid=grid)
+        else:
+            transform, info = registration.icp(pred_points, gt_points, align_distance, init=align_init, with_scale=align_scale, grid=grid)
         pred_points = registration.transform_points(pred_points, transform)
         dist_pred = ops.nearest_query(pred_points, gt_points, grid)
     dist_gt = ops.nearest_distance(gt_points, pred_points)

@@ -92,6 +92,64 @@ def icp(source: Tensor, target: Tensor, max_distance: float, init=None, max_iter
     return state[:16].view(4, 4), info
 
 
+PLANE_STATUS_NAMES = STATUS_NAMES + ("degenerate geometry",)
+STATUS_DEGENERATE = 4
+# the head of the point-to-plane state block: T | iterations | status | 30 moments, then four arrays per iteration
+_PLANE_HEAD_WORDS = 48
+
+
+def icp_plane_workspace(device, N, max_iterations):
+    """``icp_workspace`` for ``icp_plane``: ``dvmvs_icp_plane_workspace_bytes(N, max_iterations)`` bytes, a fresh float64 device tensor."""
+    N, max_iterations = int(N), int(max_iterations)
+    nbytes = _capi.lib().dvmvs_icp_plane_workspace_bytes(N, max_iterations)
+    if nbytes == 0:
+        raise ValueError(f"dvmvs::icp_plane: {N} points over {max_iterations} iterations are outside what the kernels take (1 .. 2^28 "
+                         f"points, 1 .. {MAX_ITERATIONS} iterations)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def icp_plane(source: Tensor, target: Tensor, target_normals: Tensor, max_distance: float, init=None, max_iterations: int = 30,
+              tolerance: float = 1e-6, grid: Optional[Tensor] = None):
+    """Registers ``source`` (float32 [N,3]) to ``target`` (float32 [M,3]) with normals ``target_normals`` (float32 [M,3], all on one GPU)
+    by trimmed point-to-plane ICP: ``(T, info)`` as ``icp`` returns them, rigid only.  A normal that is all zero or not finite is "no
+    normal": such a target pairs with nothing; a normal's sign does not matter.  ``info`` holds ``iterations``, ``status``
+    (``PLANE_STATUS_NAMES``), ``inliers``, ``fitness``, ``rmse`` (of the plane residual), ``rmse_point`` (of the point distance), each
+    [max_iterations], and ``moments`` (float64 [30]).  The loop stops when RMSE and fitness both change by less than ``tolerance``, with
+    fewer than 6 inliers, at the limit, or with status 4 where the paired geometry (a single plane, two planes) leaves a freedom open, in
+    which case T is left as it was.  Nothing is read by the call.  ``init`` and ``grid`` as in ``icp``.  The arithmetic is fixed
+    (include/dvmvs_hip.h): ``dvmvs.errors.register_points_plane`` gives the same bits."""
+    from dvmvs.hip.ops import reconstruction
+    source = _cloud("icp_plane", "source", source)
+    dev = source.device
+    target = _cloud("icp_plane", "target", target, dev)
+    N, M = int(source.shape[0]), int(target.shape[0])
+    check_tensors("icp_plane", target_normals, label="target_normals", shape=(M, 3), device=dev)
+    target_normals = target_normals.contiguous()
+    max_distance, tolerance, max_iterations = float(max_distance), float(tolerance), int(max_iterations)
+    if not max_distance > 0.0 or not tolerance >= 0.0:
+        raise ValueError(f"dvmvs::icp_plane: max_distance must be positive and tolerance not negative (neither NaN), got {max_distance}, "
+                         f"{tolerance}")
+    if not 1 <= max_iterations <= MAX_ITERATIONS:
+        raise ValueError(f"dvmvs::icp_plane: max_iterations must be in 1 .. {MAX_ITERATIONS}, got {max_iterations}")
+    init = _host_matrix("icp_plane", init)
+    if grid is None:
+        grid = reconstruction.nearest_build(target)
+    else:
+        check_tensors("icp_plane", grid, dtype=torch.uint8, label="grid", device=dev, contiguous=True)
+        if grid.numel() < _capi.lib().dvmvs_nearest_workspace_bytes(M):
+            raise ValueError(f"dvmvs::icp_plane: grid is smaller than the workspace of a {M}-point target")
+    scratch = _workspace.grown("nearest_query", dev, _capi.lib().dvmvs_nearest_query_workspace_bytes(N, M), torch.uint8)
+    state = icp_plane_workspace(dev, N, max_iterations)
+    init_ptr = None if init is None else init.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    launch("dvmvs_icp_plane_fwd", dev, ptr(source), N, ptr(target), ptr(target_normals), M, ptr(grid), ptr(scratch), scratch.numel(),
+           max_distance, max_iterations, tolerance, init_ptr, ptr(state), state.numel() * 8)
+    words = state.view(torch.int64)
+    a, I = _PLANE_HEAD_WORDS, max_iterations
+    info = {"iterations": words[_WORD_ITERATIONS], "status": words[_WORD_STATUS], "inliers": words[a:a + I], "fitness": state[a + I:a + 2 * I],
+            "rmse": state[a + 2 * I:a + 3 * I], "rmse_point": state[a + 3 * I:a + 4 * I], "moments": state[_WORD_MOMENTS:_PLANE_HEAD_WORDS]}
+    return state[:16].view(4, 4), info
+
+
 def transform_points(points: Tensor, T: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """``points`` float32 [N,3] moved by ``T`` (float64 [4,4] on the same GPU, e.g. ``icp``'s): every entry of ``T[:3,:4]`` is rounded to
     float32 and ``p' = ((A00 x + A01 y) + A02 z) + A03`` (and so on) is evaluated in float32 without FMA, as the registration itself

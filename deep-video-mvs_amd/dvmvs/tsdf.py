@@ -342,7 +342,8 @@ class TSDFVolume:
         return prepare_points_device(verts, faces, sample_density, voxel)
 
     def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None, clean=None,
-                      align_distance=None, align_scale=False, return_transform=False):
+                      align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, align_distance=None, align_scale=False,
+                      return_transform=False):
         """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
         DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
         ``dvmvs.errors.compute_reconstruction_errors_device`` without a download.  ``reference``: another ``TSDFVolume``, [M,3] points as a
@@ -371,16 +372,25 @@ class TSDFVolume:
         with that inlier distance and moved by the result (``dvmvs.hip.registration.icp``; ``dvmvs.errors.register_points`` is the host
         definition), so that a residual pose offset does not decide the score; ``align_scale`` lets the registration also find a scale.
         Nothing is read by the host.  ``return_transform``: the transform, a float64 [4,4] DEVICE tensor that takes this volume's
-        coordinates into the reference's, comes back as the LAST entry of the returned tuple."""
+        coordinates into the reference's, comes back as the LAST entry of the returned tuple.
+
+        ``align_plane`` (needs ``align_distance``, excludes ``align_scale``): the registration is point-to-plane on the reference's
+        normals (``dvmvs.hip.registration.icp_plane``; ``dvmvs.errors.register_points_plane`` is the host definition), which needs a
+        fraction of the iterations on walls and floors.  A ``TSDFVolume`` reference scored on its vertices brings the normals of its
+        marching-cubes mesh; in every other mode they are estimated from the reference's prepared points
+        (``dvmvs.hip.normals.estimate_normals`` with ``align_normal_neighbours`` nearest points within ``align_normal_distance``)."""
         return self._score_against(reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
-                                   return_transform, clean=clean)[0]
+                                   return_transform, clean=clean, align_plane=align_plane, align_normal_neighbours=align_normal_neighbours,
+                                   align_normal_distance=align_normal_distance)[0]
 
     def _score_against(self, reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
-                       return_transform, clean=None):
+                       return_transform, clean=None, align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf):
         """``score_against``: ``(what it returns, the registration's record or None)``; the record is ``dvmvs.hip.registration.icp``'s
-        ``info`` (device tensors)."""
-        from dvmvs.errors import _check_alignment, _score_device, prepare_points_device
+        (with ``align_plane``: ``icp_plane``'s) ``info`` (device tensors)."""
+        from dvmvs.errors import _check_alignment, _check_plane, _score_device, prepare_points_device
         _check_alignment("score_against", align_distance, align_scale, None, return_transform)
+        _check_plane("score_against", align_plane, align_distance, align_scale, None, False, align_normal_neighbours, align_normal_distance)
+        gt_normals = None
         prepare = sample_density is not None or voxel is not None
         if visible_from is not None:
             if sample_density is None:
@@ -389,7 +399,13 @@ class TSDFVolume:
                 raise ValueError("score_against: visible_from is (cam_intr, cam_poses, height, width[, min_views])")
         gt_faces = None
         if isinstance(reference, TSDFVolume):
-            gt, gt_faces = reference.mesh_tensors() if prepare else (reference.vertices(), None)
+            if prepare:
+                gt, gt_faces = reference.mesh_tensors()
+            elif align_plane:                            # the gradient normals of the reference's marching-cubes mesh come with its vertices
+                gt, _, gt_normals = reference._extract(False, None)[:3]
+                gt_normals = gt_normals.to(self.device).contiguous()
+            else:
+                gt = reference.vertices()
             gt = gt.to(self.device)
         else:
             if isinstance(reference, (tuple, list)) and len(reference) == 2 and all(len(getattr(part, "shape", ())) == 2 for part in reference):
@@ -415,7 +431,8 @@ class TSDFVolume:
             pred = self.vertices(clean=clean)
         if pred.shape[0] == 0 or gt.shape[0] == 0:
             raise ValueError(f"score_against: a surface without a vertex cannot be scored ({pred.shape[0]} predicted, {gt.shape[0]} reference)")
-        row, transform, info = _score_device(pred, gt.contiguous(), threshold, None, None, None, None, None, align_distance, align_scale, None)
+        row, transform, info = _score_device(pred, gt.contiguous(), threshold, None, None, None, None, None, align_distance, align_scale, None,
+                                             align_plane, gt_normals, align_normal_neighbours, align_normal_distance)
         result = (row,)
         if return_sizes:
             result += ((int(pred.shape[0]), int(gt.shape[0])),) + (() if face_counts is None else (face_counts,))
@@ -789,7 +806,8 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         use_groundtruth_to_anchor, save_progressive, save_groundtruth, device="cuda", device_preprocess=False, render_keyframes=False,
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
-        evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, groundtruth_transform=None,
+        evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, evaluate_3d_align_plane=False,
+        evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, groundtruth_transform=None,
         point_normals_neighbours=None, point_normals_max_distance=None, clean_points_neighbours=None, clean_points_ratio=2.0,
         clean_points_max_distance=None, clean_points_radius=None, clean_points_min_neighbours=None, clean_mesh_area=None,
         clean_mesh_faces=None, clean_mesh_largest=False):
@@ -833,6 +851,12 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     ``groundtruth_mesh``): a text file of 16 numbers, the 4x4 that takes the mesh's frame into the dataset's world frame, applied to the
     mesh's vertices (in float64, rounded once) when the mesh is read, before visibility culling and sampling.  Without these flags the
     files are what they are without them, byte for byte.
+
+    ``evaluate_3d_align_plane`` (needs ``evaluate_3d_align``, excludes ``evaluate_3d_align_scale``): the registration is point-to-plane
+    (``TSDFVolume.score_against(align_plane=True)``) on normals estimated from the ground truth's point set, from
+    ``evaluate_3d_align_neighbours`` nearest points within ``evaluate_3d_align_normal_distance`` metres (None: any distance).
+    ``align_status`` is then an index of ``dvmvs.errors.REGISTRATION_PLANE_STATUS``, ``align_rmse`` the RMSE of the plane residual, and
+    ``_errors3d.npz`` also holds ``align_status_name`` and ``align_rmse_point``.
 
     ``filter_consistency``: after the masks above, the keyframe predictions go up once and are filtered by multi-view geometric consistency
     in one launch (``dvmvs.consistency.filter_depths``): a pixel is kept, with its own depth, where at least ``consistency_views`` of the
@@ -891,6 +915,16 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         raise ValueError("evaluate_3d_align registers the surface that evaluate_3d scores: it needs evaluate_3d")
     if evaluate_3d_align_scale and evaluate_3d_align is None:
         raise ValueError("evaluate_3d_align_scale says how evaluate_3d_align registers: it needs evaluate_3d_align")
+    if evaluate_3d_align_plane and (evaluate_3d_align is None or evaluate_3d_align_scale):
+        raise ValueError("evaluate_3d_align_plane says how evaluate_3d_align registers, a rigid motion: it needs evaluate_3d_align and excludes "
+                         "evaluate_3d_align_scale")
+    if not evaluate_3d_align_plane and (int(evaluate_3d_align_neighbours) != 20 or evaluate_3d_align_normal_distance is not None):
+        raise ValueError("evaluate_3d_align_neighbours and evaluate_3d_align_normal_distance say how evaluate_3d_align_plane estimates normals: "
+                         "they need evaluate_3d_align_plane")
+    align_plane = None
+    if evaluate_3d_align_plane:
+        align_plane = {"align_plane": True, "align_normal_neighbours": int(evaluate_3d_align_neighbours),
+                       "align_normal_distance": np.inf if evaluate_3d_align_normal_distance is None else float(evaluate_3d_align_normal_distance)}
     if groundtruth_transform is not None and groundtruth_mesh is None:
         raise ValueError("groundtruth_transform moves the mesh of groundtruth_mesh: it needs groundtruth_mesh")
     if evaluate_3d_align is not None and not float(evaluate_3d_align) > 0.0:
@@ -1011,9 +1045,10 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
                     raise ValueError("evaluate_3d_visible: the scene has no keyframe to take the visibility from")
                 visible_from = (scaled_K, np.stack(keyframe_poses), prediction_height, prediction_width, int(evaluate_3d_min_views))
             _evaluate_3d_protocol(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_density, evaluate_3d_voxel,
-                                  visible_from, evaluate_3d_align, evaluate_3d_align_scale, clean=clean)
+                                  visible_from, evaluate_3d_align, evaluate_3d_align_scale, clean=clean, align_plane=align_plane)
         else:
-            _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_align, evaluate_3d_align_scale, clean=clean)
+            _evaluate_3d(volume, groundtruth_vertices, threshold_3d, system_mesh_name, evaluate_3d_align, evaluate_3d_align_scale, clean=clean,
+                         align_plane=align_plane)
     if render_keyframes:
         _render_keyframes(volume, keyframe_poses, keyframe_image_filenames, scaled_K, preprocessor, prediction_height, prediction_width,
                           scene_folder, f"keyframe_{dataset_name}_{system_name}+tsdf", scene_name, reconstruction_folder)
@@ -1077,13 +1112,16 @@ def apply_transform(verts, transform):
     return (verts @ transform[:3, :3].T + transform[:3, 3]).astype(np.float32)
 
 
-def _aligned_score(volume, align_distance, align_scale, **score):
+def _aligned_score(volume, align_distance, align_scale, align_plane=None, **score):
     """``score_against`` with its row on the host; with ``align_distance`` also the entries ``_errors3d.npz`` gains.  Row, transform and
-    record come down as ONE float64 tensor (a float32 row is exact in float64)."""
+    record come down as ONE float64 tensor (a float32 row is exact in float64).  ``align_plane``: None, or ``score_against``'s
+    point-to-plane keywords."""
     if align_distance is None:
         result = volume.score_against(**score)
         return (result[0].cpu().numpy(),) + tuple(result[1:]) + ({},)
     score = {"return_sizes": False, "sample_density": None, "voxel": None, "visible_from": None, **score}
+    if align_plane is not None:
+        return _aligned_score_plane(volume, align_distance, align_plane, score)
     result, info = volume._score_against(align_distance=align_distance, align_scale=align_scale, return_transform=True, **score)
     last = (info["iterations"] - 1).clamp(min=0).reshape(1)      # (selected on the device: indexing with a 0-d tensor would read it)
     down = torch.cat([result[0].double(), result[-1].reshape(-1), info["iterations"].double().reshape(1), info["status"].double().reshape(1),
@@ -1093,6 +1131,23 @@ def _aligned_score(volume, align_distance, align_scale, **score):
     from dvmvs.errors import REGISTRATION_STATUS
     print("Registered the surface to the ground truth within {} m{}: {} after {} iterations, fitness {:.4f}, rmse {:.5f} m".format(
         align_distance, " with scale" if align_scale else "", REGISTRATION_STATUS[int(down[23])], int(down[22]), down[24], down[25]))
+    return (down[:6].astype(np.float32),) + tuple(result[1:-1]) + (extra,)
+
+
+def _aligned_score_plane(volume, align_distance, align_plane, score):
+    """``_aligned_score`` with the point-to-plane registration: the same single download, with the point RMSE and the status name."""
+    from dvmvs.errors import REGISTRATION_PLANE_STATUS
+    result, info = volume._score_against(align_distance=align_distance, align_scale=False, return_transform=True, **align_plane, **score)
+    last = (info["iterations"] - 1).clamp(min=0).reshape(1)
+    down = torch.cat([result[0].double(), result[-1].reshape(-1), info["iterations"].double().reshape(1), info["status"].double().reshape(1),
+                      info["fitness"].index_select(0, last), info["rmse"].index_select(0, last),
+                      info["rmse_point"].index_select(0, last)]).cpu().numpy()
+    name = REGISTRATION_PLANE_STATUS[int(down[23])]
+    extra = {"transform": down[6:22].reshape(4, 4), "align_iterations": np.int64(down[22]), "align_status": np.int64(down[23]),
+             "align_fitness": np.float64(down[24]), "align_rmse": np.float64(down[25]), "align_rmse_point": np.float64(down[26]),
+             "align_status_name": np.array(name)}
+    print("Registered the surface to the ground truth within {} m, point to plane: {} after {} iterations, fitness {:.4f}, plane rmse {:.5f} m, "
+          "point rmse {:.5f} m".format(align_distance, name, int(down[22]), down[24], down[25], down[26]))
     return (down[:6].astype(np.float32),) + tuple(result[1:-1]) + (extra,)
 
 
@@ -1178,11 +1233,11 @@ def _clean_entries(volume, clean):
             "clean_faces": np.array([kept, total], dtype=np.int64)}
 
 
-def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name, align_distance=None, align_scale=False, clean=None):
+def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name, align_distance=None, align_scale=False, clean=None, align_plane=None):
     """Scores the fused surface against the ground-truth vertices on the device; one row comes down, is printed and saved."""
     from dvmvs.errors import RECONSTRUCTION_METRICS
     cleaning = {} if clean is None else {"clean": clean}
-    row, sizes, aligned = _aligned_score(volume, align_distance, align_scale, reference=groundtruth_vertices, threshold=threshold,
+    row, sizes, aligned = _aligned_score(volume, align_distance, align_scale, align_plane, reference=groundtruth_vertices, threshold=threshold,
                                          return_sizes=True, **cleaning)
     print("3-D metrics at {} m over {} predicted and {} ground-truth vertices: {}".format(
         threshold, sizes[0], sizes[1], ", ".join(f"{n} {v:.4f}" for n, v in zip(RECONSTRUCTION_METRICS, row))))
@@ -1191,7 +1246,7 @@ def _evaluate_3d(volume, groundtruth_vertices, threshold, mesh_name, align_dista
 
 
 def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample_density, voxel, visible_from=None, align_distance=None,
-                          align_scale=False, clean=None):
+                          align_scale=False, clean=None, align_plane=None):
     """``_evaluate_3d`` against a ground-truth mesh (device verts and faces), with face sampling and / or voxel down-sampling of both sides;
     with ``visible_from`` (``TSDFVolume.score_against``) against the part of the mesh those views observed."""
     from dvmvs.errors import RECONSTRUCTION_METRICS
@@ -1200,9 +1255,9 @@ def _evaluate_3d_protocol(volume, groundtruth_mesh, threshold, mesh_name, sample
     if clean is not None:
         score["clean"] = clean
     if visible_from is None:
-        row, points, aligned = _aligned_score(volume, align_distance, align_scale, **score)
+        row, points, aligned = _aligned_score(volume, align_distance, align_scale, align_plane, **score)
     else:
-        row, points, kept, aligned = _aligned_score(volume, align_distance, align_scale, visible_from=visible_from, **score)
+        row, points, kept, aligned = _aligned_score(volume, align_distance, align_scale, align_plane, visible_from=visible_from, **score)
         print("Ground truth restricted to what {} keyframes saw: {} of {} faces".format(len(visible_from[1]), kept[0], kept[1]))
         extra = {"visible_faces": np.int64(kept[0]), "total_faces": np.int64(kept[1])}
     sizes = (int(volume.vertices(clean=clean).shape[0]), int(groundtruth_mesh[0].shape[0]))
@@ -1276,6 +1331,13 @@ def build_parser():
                         help="with --evaluate_3d: register the system's point set to the ground truth's by trimmed ICP with this inlier "
                              "distance, metres, before it is scored (on the device)")
     parser.add_argument("--evaluate_3d_align_scale", action="store_true", help="with --evaluate_3d_align: the registration also finds a scale")
+    parser.add_argument("--evaluate_3d_align_plane", action="store_true",
+                        help="with --evaluate_3d_align: register point to plane, on normals estimated from the ground truth's points (a rigid "
+                             "motion; far fewer iterations on walls and floors)")
+    parser.add_argument("--evaluate_3d_align_neighbours", default=20, type=int,
+                        help="with --evaluate_3d_align_plane: nearest points a ground-truth normal is estimated from (3 .. 32)")
+    parser.add_argument("--evaluate_3d_align_normal_distance", default=None, type=float,
+                        help="with --evaluate_3d_align_plane: those points are searched within this distance only, metres")
     parser.add_argument("--groundtruth_transform", default=None, type=str,
                         help="with --groundtruth_mesh: a text file of 16 numbers, the 4x4 that takes the mesh's frame into the dataset's world frame")
     parser.add_argument("--filter_consistency", action="store_true",

@@ -69,7 +69,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_knn_fwd, dvmvs_radius_count_fwd and dvmvs_outlier_statistics_fwd (the k nearest neighbours of points,
  * neighbours within a radius, statistical outlier scores); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_point_normals_fwd (oriented normals of points from rows of nearest neighbours); no earlier signature
- * changed, the number stays 11 by the same rule. */
+ * changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_icp_plane_* (registering a point cloud to another with normals by point-to-plane ICP); no earlier
+ * signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -973,6 +975,51 @@ int dvmvs_icp_fwd(const float* source, long long N, const float* target, long lo
                   size_t query_workspace_bytes, float max_distance, int with_scale, int max_iterations, double tolerance,
                   const double* init_host, void* state, size_t state_bytes, dvmvs_stream_t stream);
 int dvmvs_transform_points_fwd(const float* points, long long N, const double* T, float* out, dvmvs_stream_t stream);
+
+/*
+ * Point-to-plane registration (ABI 11, later addition; csrc/registration.hip): the loop above with the target's normals, for surfaces made
+ * of planes, along which point-to-point correspondences slide.  The definition is this project's own (dvmvs/errors.py::
+ * register_points_plane is its host form, the same bits).  Arguments as dvmvs_icp_fwd, without with_scale, and
+ *   target_normals [M,3]  fp32, contiguous, 4-byte aligned.  A row that is all zero or holds a value that is not finite is "no normal".
+ *                         Neither the length nor the sign of a normal is looked at: every term below is even in it.
+ *   state              dvmvs_icp_plane_workspace_bytes(N, max_iterations) bytes on the device, 16-byte aligned, any contents.  In 8-byte words:
+ *                        [0, 16)   T; [16] iterations; [17] status: 0 running, 1 converged, 2 too few correspondences, 3 iteration limit,
+ *                                  4 degenerate geometry
+ *                        [18, 48)  the moments of the last recorded iteration, fp64: n | sum J_a J_b for a <= b, row-major (00, 01, .., 05,
+ *                                  11, .., 55) [21] | sum J_a r [6] | sum r^2 | sum d^2
+ *                        [48, 48 + I), .., [48 + 3 I, 48 + 4 I) with I = max_iterations: per iteration the inlier count (int64), the
+ *                                  fitness, the RMSE of the plane residual and the RMSE of the point distance (fp64)
+ *                      and, from the next multiple of 256 bytes on, the loop's scratch as in dvmvs_icp_fwd with partial sums [.., 30].
+ * Iteration k = 0, 1, ... with T_0 = init:
+ *   1., 2. as in dvmvs_icp_fwd: p' and (d_i, j_i); q_i = target[j_i], n_i = target_normals[j_i].
+ *   3. Pair i is an inlier when d_i <= max_distance (fp32) and n_i is a normal.  An index outside [0, M) is skipped and never addressed.
+ *   4. Per inlier, in fp64 from the fp32 values, every product and sum rounded, nothing contracted: p = p'_i, o = p'_0 (the first moved
+ *      point, inlier or not), r = ((p0 - q0) n0 + (p1 - q1) n1) + (p2 - q2) n2, e = p - o,
+ *      c = (e1 n2 - e2 n1, e2 n0 - e0 n2, e0 n1 - e1 n0), J = (c0, c1, c2, n0, n1, n2).  The 30 moments above are added in the order of
+ *      dvmvs_icp_fwd's step 4.
+ *   5. rmse_k = sqrt(sum r^2 / n), rmse_point_k = sqrt(sum d^2 / n) (both 0 when n = 0), fitness_k = n / N: recorded at entry k;
+ *      iterations = k + 1.  If n < 6: status 2, T stays, stop.  Else if k >= 1 and |rmse_k - rmse_{k-1}| < tolerance and
+ *      |fitness_k - fitness_{k-1}| < tolerance: status 1, T stays, stop.
+ *   6. A = sum J J^T (6x6 symmetric), b = sum J r; x with A x = -b by LDL^T without pivoting, fp64 with +, -, *, / only:
+ *        for j = 0 .. 5:  d = A_jj; for k = 0 .. j-1: d = d - (L_jk L_jk) D_k;
+ *                         if not d > 2^-30 A_jj: status 4, T stays, stop;  D_j = d;
+ *                         for i = j+1 .. 5:  s = A_ij; for k = 0 .. j-1: s = s - (L_ik L_jk) D_k;  L_ij = s / d
+ *        for i = 0 .. 5:  s = -b_i; for k = 0 .. i-1: s = s - L_ik x_k;  x_i = s
+ *        for i = 0 .. 5:  x_i = x_i / D_i
+ *        for i = 5 .. 0:  s = x_i; for k = i+1 .. 5: s = s - L_ki x_k;  x_i = s
+ *      (the constant 2^-30 is part of the definition: a single plane or two planes leave a pivot at rounding level, every well-posed
+ *      scene stays orders of magnitude above it).
+ *   7. x = (alpha, beta, gamma, t0, t1, t2).  qx = alpha / 2, qy = beta / 2, qz = gamma / 2, norm = sqrt(((1 + qx qx) + qy qy) + qz qz),
+ *      w = 1 / norm, qx = qx / norm (qy, qz likewise); R from (w, qx, qy, qz) by the formula of dvmvs_icp_fwd's step 6;
+ *      s_a = (o_a - ((R_a0 o_0 + R_a1 o_1) + R_a2 o_2)) + t_a, and for a < 3
+ *      T_{k+1}[a][c] = ((R_a0 T_k[0][c] + R_a1 T_k[1][c]) + R_a2 T_k[2][c]) + s_a T_k[3][c]; row 3 stays.  If k + 1 = max_iterations: status 3.
+ * dvmvs_icp_plane_workspace_bytes and the return codes: as dvmvs_icp_workspace_bytes and dvmvs_icp_fwd (target_normals among the pointers).
+ */
+size_t dvmvs_icp_plane_workspace_bytes(long long N, int max_iterations);
+int dvmvs_icp_plane_fwd(const float* source, long long N, const float* target, const float* target_normals, long long M,
+                        const void* grid_workspace, void* query_workspace, size_t query_workspace_bytes, float max_distance,
+                        int max_iterations, double tolerance, const double* init_host, void* state, size_t state_bytes,
+                        dvmvs_stream_t stream);
 
 /*
  * Connected components of a triangle mesh, and their removal by size (ABI 11, later addition; csrc/mesh_components.hip).  The reference
