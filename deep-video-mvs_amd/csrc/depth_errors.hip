@@ -63,15 +63,10 @@ __device__ inline void err_pixel(ErrAcc& a, float gt, float pred, float max_dept
   a.c[3] += ratio < 1.953125f ? 1u : 0u;
 }
 
-// xor butterfly over the wave: every lane ends with the same value (a + b and b + a are the same bits)
+// the sums and the counts of the wave in every lane (wave_sum of dvmvs_device.h: the xor butterfly, masks 32, 16, .., 1)
 __device__ inline void err_wave_sum(ErrAcc& a) {
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int k = 0; k < kErrSums; ++k) a.s[k] += __shfl_xor(a.s[k], m, kWave);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a.c[k] += __shfl_xor(a.c[k], m, kWave);
-  }
+  wave_sum(a.s);
+  wave_sum(a.c);
 }
 
 // grid (G, n_frames), 256 threads.  workspace: n_frames ticket words (zero between calls), padded to 64 bytes; then per (frame, g) one

@@ -1,5 +1,6 @@
 // Shared device helpers for the gfx950 plane-sweep kernels: small fp64 matrix algebra for the pose set-up,
-// the bilinear tap decomposition used by every warp kernel, and launch plumbing.
+// the bilinear tap decomposition used by every warp kernel, and launch plumbing; and what the point-cloud and mesh kernels share:
+// the block scans, the scan of per-workgroup totals, the ordered sum over a wave and the quantised area of a face.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -202,6 +203,77 @@ __device__ inline long long block_exclusive_scan(long long v, long long* lds, lo
     total += t;
   }
   return prefix + incl - v;
+}
+
+// The scan of per-workgroup totals, by ONE workgroup of kThreads threads: totals[b] <- the sum of the totals before b, in place; every
+// thread returns the sum of all.  Thread t takes the chunk of ceil(nblocks / kThreads) consecutive totals from t * chunk, clipped to
+// nblocks (the last threads' chunks are short or empty).  `s` holds kThreads values in LDS and may be used again after the return.
+// Integer sums: any association gives the same result.
+template <int kThreads, typename T>
+__device__ inline T scan_totals(T* __restrict__ totals, int nblocks, T* s) {
+  const int t = threadIdx.x;
+  const int chunk = (nblocks + kThreads - 1) / kThreads;
+  const int begin = min(t * chunk, nblocks), end = min(begin + chunk, nblocks);
+  T v = 0;
+  for (int b = begin; b < end; ++b) v += totals[b];
+  s[t] = v;
+  __syncthreads();
+  for (int off = 1; off < kThreads; off <<= 1) {       // Hillis-Steele inclusive scan
+    const T a = t >= off ? s[t - off] : 0;
+    __syncthreads();
+    s[t] += a;
+    __syncthreads();
+  }
+  T o = s[t] - v;
+  for (int b = begin; b < end; ++b) {
+    const T c = totals[b];
+    totals[b] = o;
+    o += c;
+  }
+  const T all = s[kThreads - 1];
+  __syncthreads();                                     // (s is used again)
+  return all;
+}
+
+// ---- sums over a wave -------------------------------------------------------------------------------------------
+// xor butterfly over the 64 lanes, masks 32, 16, .., 1: every lane ends with the same value (a + b and b + a are the same bits).  The
+// order of the masks is part of the definition of every fp64 sum that uses it.
+template <typename T>
+__device__ inline T wave_sum(T x) {
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, kWave);
+  return x;
+}
+
+// The same for every element of an array, in place.
+template <typename T, int kCount>
+__device__ inline void wave_sum(T (&v)[kCount]) {
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int k = 0; k < kCount; ++k) v[k] += __shfl_xor(v[k], m, kWave);
+  }
+}
+
+// ---- the quantised area of a face ---------------------------------------------------------------------------------
+// A_f of dvmvs/errors.py::quantised_face_areas for a face whose vertex indices are known to be valid: the fp64 area in units of
+// 2^-32 m^2, rounded to nearest even; -1 for an area that is not finite or does not fit (an error).  Nothing is contracted into an FMA.
+__device__ inline long long quantised_face_area(const float* __restrict__ verts, int ia, int ib, int ic) {
+#pragma clang fp contract(off)
+  double a[3], e1[3], e2[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    a[d] = static_cast<double>(verts[static_cast<size_t>(ia) * 3 + d]);
+    e1[d] = static_cast<double>(verts[static_cast<size_t>(ib) * 3 + d]) - a[d];
+    e2[d] = static_cast<double>(verts[static_cast<size_t>(ic) * 3 + d]) - a[d];
+  }
+  const double cx = e1[1] * e2[2] - e1[2] * e2[1];
+  const double cy = e1[2] * e2[0] - e1[0] * e2[2];
+  const double cz = e1[0] * e2[1] - e1[1] * e2[0];
+  const double n2 = (cx * cx + cy * cy) + cz * cz;
+  const double area = sqrt(n2) * 0.5 * 4294967296.0;
+  if (!(area < 9223372036854775808.0)) return -1;      // NaN, infinite or 2^63 and more
+  return static_cast<long long>(rint(area));
 }
 
 }  // namespace dvmvs

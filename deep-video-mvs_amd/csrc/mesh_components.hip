@@ -1,7 +1,7 @@
 // Connected components of a triangle mesh and their removal by size (gfx950).  Both reproduce their host definitions bit for bit
 // (dvmvs/components.py::mesh_components, filter_components; include/dvmvs_hip.h).  Everything that decides a result is an integer; the one
-// float computation, a face's quantised area, stays inside its thread and is surface_sample.hip's ss_face_area restated (contract(off) for
-// the whole file).  Integer sums are exact, so no order of the atomics can show.
+// float computation, a face's quantised area, stays inside its thread and is the quantised_face_area of dvmvs_device.h that
+// surface_sample.hip uses (contract(off) there and for this whole file).  Integer sums are exact, so no order of the atomics can show.
 //   dvmvs_mesh_components_fwd : faces int32 [F,3] (verts fp32 [V,3]) -> labels int32 [V], face_labels int32 [F], face_count int32 [V],
 //                               area int64 [V], result int64 [2] = {n_components, status}
 //   dvmvs_mesh_filter_count   : those + the thresholds -> counts int64 [3] = {V', F', status}
@@ -32,9 +32,9 @@
 // Filtering.  Whether root r is kept is a function of face_count[r], area[r] and the thresholds; with keep_largest also of the winner, found
 // by integer atomic passes after mf_best_init_kernel: mf_best_kernel<0> (max area) -> <1> (max face count among those) -> <2> (min label
 // among those).  mf_flag_count_kernel counts kept faces and kept vertices per 1024 (a vertex is kept when its root is: a
-// component with a face has no vertex outside its faces), mf_scan_blocks_kernel (one workgroup) scans the workgroup totals and writes
-// counts.  emit: mf_emit_verts_kernel (order-preserving compaction with block_exclusive_scan; the new index of every vertex goes to the
-// workspace) -> mf_emit_faces_kernel.
+// component with a face has no vertex outside its faces), mf_scan_blocks_kernel (one workgroup) scans the workgroup totals (scan_totals of
+// dvmvs_device.h) and writes counts.  emit: mf_emit_verts_kernel (order-preserving compaction with block_exclusive_scan; the new index of
+// every vertex goes to the workspace) -> mf_emit_faces_kernel.
 #include "dvmvs_device.h"
 
 #pragma clang fp contract(off)
@@ -155,31 +155,6 @@ __global__ __launch_bounds__(kCcBlock) void cc_flatten_kernel(const int* __restr
   labels[i] = v;
 }
 
-// A_f of the definition (surface_sample.hip's ss_face_area, for a face that is known to be valid); -1 for an area that is not finite or
-// does not fit (an error)
-__device__ inline long long cc_face_area(const float* __restrict__ verts, int ia, int ib, int ic) {
-  double a[3], e1[3], e2[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    a[d] = static_cast<double>(verts[static_cast<size_t>(ia) * 3 + d]);
-    e1[d] = static_cast<double>(verts[static_cast<size_t>(ib) * 3 + d]) - a[d];
-    e2[d] = static_cast<double>(verts[static_cast<size_t>(ic) * 3 + d]) - a[d];
-  }
-  const double cx = e1[1] * e2[2] - e1[2] * e2[1];
-  const double cy = e1[2] * e2[0] - e1[0] * e2[2];
-  const double cz = e1[0] * e2[1] - e1[1] * e2[0];
-  const double n2 = (cx * cx + cy * cy) + cz * cz;
-  const double area = sqrt(n2) * 0.5 * 4294967296.0;
-  if (!(area < 9223372036854775808.0)) return -1;      // NaN, infinite or 2^63 and more
-  return static_cast<long long>(rint(area));
-}
-
-__device__ inline u64 wave_sum(u64 x) {
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) x += __shfl_xor(x, m, kWave);
-  return x;
-}
-
 // Workgroup b takes the faces [1024 b, 1024 b + 1024), thread t the faces 1024 b + 256 e + t: in step e a wave holds 64 consecutive faces.
 __global__ __launch_bounds__(kCcBlock) void cc_count_kernel(const float* __restrict__ verts, long long V, const int* __restrict__ faces, long long F,
                                                             const int* __restrict__ labels, int* __restrict__ face_labels,
@@ -203,7 +178,7 @@ __global__ __launch_bounds__(kCcBlock) void cc_count_kernel(const float* __restr
         int r = labels[ia];
         if (r < 0 || r >= V) r = -1;                   // never, for the labels of the flatten launch
         if (r >= 0 && verts) {
-          long long area = cc_face_area(verts, ia, ib, ic);
+          long long area = quantised_face_area(verts, ia, ib, ic);
           if (area < 0) {
             area = 0;
             bad = true;
@@ -371,37 +346,11 @@ __global__ __launch_bounds__(kCcBlock) void mf_flag_count_kernel(const int* __re
   if (threadIdx.x == 0) (is_face ? ftotals : vtotals)[b] = total;
 }
 
-// One workgroup: totals[b] <- the sum of the totals before b, returns the sum of all
-__device__ inline int mf_scan_totals(int* __restrict__ totals, int nblocks, int* s) {
-  const int t = threadIdx.x;
-  const int chunk = (nblocks + kCcScanThreads - 1) / kCcScanThreads;
-  const int begin = min(t * chunk, nblocks), end = min(begin + chunk, nblocks);
-  int v = 0;
-  for (int b = begin; b < end; ++b) v += totals[b];
-  s[t] = v;
-  __syncthreads();
-  for (int off = 1; off < kCcScanThreads; off <<= 1) {     // Hillis-Steele inclusive scan
-    const int a = t >= off ? s[t - off] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  int o = s[t] - v;
-  for (int b = begin; b < end; ++b) {
-    const int c = totals[b];
-    totals[b] = o;
-    o += c;
-  }
-  const int all = s[kCcScanThreads - 1];
-  __syncthreads();                                     // (s is used again)
-  return all;
-}
-
 __global__ __launch_bounds__(kCcScanThreads) void mf_scan_blocks_kernel(int* __restrict__ ftotals, int fblocks, int* __restrict__ vtotals, int vblocks,
                                                                         const long long* __restrict__ result, long long* __restrict__ counts) {
   __shared__ int s[kCcScanThreads];
-  const int kept_faces = mf_scan_totals(ftotals, fblocks, s);
-  const int kept_verts = mf_scan_totals(vtotals, vblocks, s);
+  const int kept_faces = scan_totals<kCcScanThreads>(ftotals, fblocks, s);
+  const int kept_verts = scan_totals<kCcScanThreads>(vtotals, vblocks, s);
   if (threadIdx.x == 0) {
     const long long status = result[1];
     counts[0] = status ? 0 : kept_verts;

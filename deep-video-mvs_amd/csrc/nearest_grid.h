@@ -1,7 +1,8 @@
 // The uniform grid over a point cloud that csrc/nearest_points.hip builds, for the files that search it (nearest_points.hip: the nearest
 // target; point_neighbours.hip: the k nearest and the targets within a radius).  Here: the header the build leaves at the workspace's
 // start, the cell function (the SAME fp32 statements for targets, queries and the box's far corner), the layouts of the two workspaces,
-// the ordered wave sum of the one-workgroup reductions, and the binning of a query cloud (defined in nearest_points.hip with its kernels).
+// and the binning of a query cloud (defined in nearest_points.hip with its kernels).  The ordered wave sum of the one-workgroup reductions
+// is dvmvs_device.h's wave_sum.
 // The grid, its search bound and their fp32 margins are described at the head of nearest_points.hip.
 #pragma once
 #include "dvmvs_device.h"
@@ -37,15 +38,6 @@ __device__ inline int nn_cell(const NnHeader& h, float x, float y, float z, int&
   cy = nn_cell_axis(y, h.mn[1], h.mx[1], h.inv_h, h.dim[1]);
   cz = nn_cell_axis(z, h.mn[2], h.mx[2], h.inv_h, h.dim[2]);
   return (cx * h.dim[1] + cy) * h.dim[2] + cz;
-}
-
-// xor butterfly over the wave: every lane ends with the same value (a + b and b + a are the same bits)
-__device__ inline void nn_wave_sum(double& s, unsigned long long& c) {
-#pragma unroll
-  for (int m = kWave / 2; m >= 1; m >>= 1) {
-    s += __shfl_xor(s, m, kWave);
-    c += __shfl_xor(c, m, kWave);
-  }
 }
 
 inline size_t nn_align(size_t bytes) { return (bytes + 255) / 256 * 256; }

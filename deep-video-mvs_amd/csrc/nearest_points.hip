@@ -14,7 +14,7 @@
 //   1. nn_bbox_kernel     per-workgroup min / max of the coordinates (min and max do not depend on the order either)
 //   2. nn_header_kernel   one workgroup: the box, the cell edge h and the grid dimensions -> NnHeader at the workspace's start
 //   3. memset + nn_count_kernel   points per cell (integer atomics)
-//   4. nn_scan_*          exclusive scan of the cell counts over three launches (1024 cells per workgroup, one workgroup for the totals; block_exclusive_scan of dvmvs_device.h)
+//   4. nn_scan_*          exclusive scan of the cell counts over three launches (1024 cells per workgroup, one workgroup for the totals; block_exclusive_scan and scan_totals of dvmvs_device.h)
 //   5. nn_scatter_kernel  point -> slot atomicAdd(cell's cursor): sorted copy {x, y, z, original index}; the cursors end as the cells' ENDS
 // The order of the points inside a cell depends on the order the atomics arrive in; the results do not (minimum, smallest index).
 //
@@ -44,7 +44,7 @@
 // Preconditions, not checked on the device: finite coordinates.  (A NaN cannot make an access go out of bounds: fmin / fmax drop it and
 // the cell index is clamped; the distances are then meaningless.)
 #include "dvmvs_device.h"
-#include "nearest_grid.h"      // NnHeader, nn_cell, the workspace layouts, nn_wave_sum: shared with point_neighbours.hip
+#include "nearest_grid.h"      // NnHeader, nn_cell, the workspace layouts: shared with point_neighbours.hip
 
 #pragma clang fp contract(off)
 
@@ -181,25 +181,7 @@ __global__ __launch_bounds__(kNnBlock) void nn_scan_totals_kernel(const int* __r
 // One workgroup: totals[b] <- the sum of the totals before b.
 __global__ __launch_bounds__(kNnScanThreads) void nn_scan_blocks_kernel(int* __restrict__ totals, int nblocks) {
   __shared__ int s[kNnScanThreads];
-  const int t = threadIdx.x;
-  const int chunk = (nblocks + kNnScanThreads - 1) / kNnScanThreads;
-  const int begin = min(t * chunk, nblocks), end = min(begin + chunk, nblocks);
-  int v = 0;
-  for (int b = begin; b < end; ++b) v += totals[b];
-  s[t] = v;
-  __syncthreads();
-  for (int off = 1; off < kNnScanThreads; off <<= 1) {     // Hillis-Steele inclusive scan
-    const int a = t >= off ? s[t - off] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  int o = s[t] - v;
-  for (int b = begin; b < end; ++b) {
-    const int c = totals[b];
-    totals[b] = o;
-    o += c;
-  }
+  scan_totals<kNnScanThreads>(totals, nblocks, s);
 }
 
 // cells[c] <- the number of points in the cells before c (the cell's first slot, and the scatter's cursor)
@@ -317,7 +299,8 @@ __global__ __launch_bounds__(kNnMetricThreads) void nn_metrics_kernel(const floa
       s += static_cast<double>(v);
       c += v < threshold ? 1u : 0u;
     }
-    nn_wave_sum(s, c);
+    s = wave_sum(s);
+    c = wave_sum(c);
     if (t % kWave == 0) {
       s_sum[side][t / kWave] = s;
       s_cnt[side][t / kWave] = c;

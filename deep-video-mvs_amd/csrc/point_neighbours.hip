@@ -194,7 +194,8 @@ __global__ __launch_bounds__(kNnBlock) void pn_mean_kernel(const float* __restri
 // the sum over the workgroup in the fixed order, in every thread (each adds the 16 wave sums in order itself: the same bits everywhere)
 __device__ inline void pn_block_sum(double& s, unsigned long long& c, double* s_sum, unsigned long long* s_cnt) {
   const int t = threadIdx.x;
-  nn_wave_sum(s, c);
+  s = wave_sum(s);
+  c = wave_sum(c);
   __syncthreads();                                           // the previous use of the arrays is over
   if (t % kWave == 0) {
     s_sum[t / kWave] = s;

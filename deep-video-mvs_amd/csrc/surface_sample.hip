@@ -37,24 +37,11 @@ constexpr long long kSsTooLarge = 1LL << 31;            // floor(total area / 2^
 constexpr int kVxMinGroups = 256;
 constexpr int kVxMaxCells = 1 << 21;
 
-// A_f of the definition; -1 for an area that is not finite or does not fit (an error)
+// A_f of the definition: 0 for a face with an index outside [0, V); -1 for an area that is not finite or does not fit (an error)
 __device__ inline long long ss_face_area(const float* __restrict__ verts, long long V, const int* __restrict__ faces, long long f) {
   const int ia = faces[f * 3], ib = faces[f * 3 + 1], ic = faces[f * 3 + 2];
   if (ia < 0 || ib < 0 || ic < 0 || ia >= V || ib >= V || ic >= V) return 0;
-  double a[3], e1[3], e2[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    a[d] = static_cast<double>(verts[static_cast<size_t>(ia) * 3 + d]);
-    e1[d] = static_cast<double>(verts[static_cast<size_t>(ib) * 3 + d]) - a[d];
-    e2[d] = static_cast<double>(verts[static_cast<size_t>(ic) * 3 + d]) - a[d];
-  }
-  const double cx = e1[1] * e2[2] - e1[2] * e2[1];
-  const double cy = e1[2] * e2[0] - e1[0] * e2[2];
-  const double cz = e1[0] * e2[1] - e1[1] * e2[0];
-  const double n2 = (cx * cx + cy * cy) + cz * cz;
-  const double area = sqrt(n2) * 0.5 * 4294967296.0;
-  if (!(area < 9223372036854775808.0)) return -1;      // NaN, infinite or 2^63 and more
-  return static_cast<long long>(rint(area));
+  return quantised_face_area(verts, ia, ib, ic);
 }
 
 // cum[f] <- A_f; totals[block] <- the sum of the block's A_f (wraps when it does not fit); high[block] <- floor(the exact sum / 2^32),
@@ -92,30 +79,14 @@ __global__ __launch_bounds__(kSsScanThreads) void ss_scan_blocks_kernel(long lon
                                                                         int nblocks, long long D, long long* __restrict__ counts) {
   __shared__ long long s[kSsScanThreads], s_hi[kSsScanThreads], s_lo[kSsScanThreads];
   const int t = threadIdx.x;
-  const int chunk = (nblocks + kSsScanThreads - 1) / kSsScanThreads;
-  const int begin = min(t * chunk, nblocks), end = min(begin + chunk, nblocks);
-  long long v = 0, hi = 0, lo = 0;
-  for (int b = begin; b < end; ++b) {
-    v += totals[b];
+  long long hi = 0, lo = 0;
+  for (int b = t; b < nblocks; b += kSsScanThreads) {      // (before the scan overwrites the totals)
     hi += min(high[b], kSsTooLarge);                 // (capped: 2^18 blocks of 2^31 cannot overflow)
     lo += totals[b] & 0xffffffffLL;
   }
-  s[t] = v;
   s_hi[t] = hi;
   s_lo[t] = lo;
-  __syncthreads();
-  for (int off = 1; off < kSsScanThreads; off <<= 1) {     // Hillis-Steele inclusive scan
-    const long long a = t >= off ? s[t - off] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  long long o = s[t] - v;
-  for (int b = begin; b < end; ++b) {
-    const long long c = totals[b];
-    totals[b] = o;
-    o += c;
-  }
+  const long long total = scan_totals<kSsScanThreads>(totals, nblocks, s);      // (its barriers publish s_hi and s_lo as well)
   if (t == kSsScanThreads - 1) {
     long long all_hi = 0, all_lo = 0;
     for (int i = 0; i < kSsScanThreads; ++i) {
@@ -123,7 +94,7 @@ __global__ __launch_bounds__(kSsScanThreads) void ss_scan_blocks_kernel(long lon
       all_lo += s_lo[i];
     }
     const bool bad = all_hi + (all_lo >> 32) >= kSsTooLarge;
-    const long long total = s[t], half = D >> 1;
+    const long long half = D >> 1;
     counts[0] = bad || total <= half ? 0 : (total - half - 1) / D + 1;
     counts[1] = bad ? 1 : 0;
     counts[2] = bad ? 0 : total;
@@ -317,27 +288,9 @@ __global__ __launch_bounds__(kSsBlock) void vx_head_kernel(const float* __restri
 __global__ __launch_bounds__(kSsScanThreads) void vx_scan_blocks_kernel(int* __restrict__ totals, int nblocks, const VxHeader* __restrict__ hdr,
                                                                         long long* __restrict__ counts) {
   __shared__ int s[kSsScanThreads];
-  const int t = threadIdx.x;
-  const int chunk = (nblocks + kSsScanThreads - 1) / kSsScanThreads;
-  const int begin = min(t * chunk, nblocks), end = min(begin + chunk, nblocks);
-  int v = 0;
-  for (int b = begin; b < end; ++b) v += totals[b];
-  s[t] = v;
-  __syncthreads();
-  for (int off = 1; off < kSsScanThreads; off <<= 1) {     // Hillis-Steele inclusive scan
-    const int a = t >= off ? s[t - off] : 0;
-    __syncthreads();
-    s[t] += a;
-    __syncthreads();
-  }
-  int o = s[t] - v;
-  for (int b = begin; b < end; ++b) {
-    const int c = totals[b];
-    totals[b] = o;
-    o += c;
-  }
-  if (t == kSsScanThreads - 1) {
-    counts[0] = s[t];
+  const int heads = scan_totals<kSsScanThreads>(totals, nblocks, s);
+  if (threadIdx.x == 0) {
+    counts[0] = heads;
     counts[1] = hdr->status;
   }
 }

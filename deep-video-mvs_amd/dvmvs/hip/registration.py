@@ -14,21 +14,37 @@ from dvmvs.hip.ops._common import check_tensors, launch, out_or_new, ptr
 
 STATUS_NAMES = ("running", "converged", "too few correspondences", "iteration limit")
 STATUS_RUNNING, STATUS_CONVERGED, STATUS_TOO_FEW, STATUS_LIMIT = range(4)
+PLANE_STATUS_NAMES = STATUS_NAMES + ("degenerate geometry",)
+STATUS_DEGENERATE = 4
 MAX_ITERATIONS = 1024
-# the head of the state block in 8-byte words (include/dvmvs_hip.h): T | iterations | status | moments, then three arrays per iteration
-_WORD_ITERATIONS, _WORD_STATUS, _WORD_MOMENTS, _HEAD_WORDS = 16, 17, 18, 36
+# the head of the state block in 8-byte words (include/dvmvs_hip.h): T | iterations | status | moments up to the variant's head words
+_WORD_ITERATIONS, _WORD_STATUS, _WORD_MOMENTS = 16, 17, 18
+# a variant of the loop: the op's name (its symbols are dvmvs_<name>_workspace_bytes and dvmvs_<name>_fwd), the head words of its state
+# block (18 + its 18 or 30 moments) and the arrays of max_iterations entries that follow the head
+_POINT = ("icp", 36, ("inliers", "fitness", "rmse"))
+_PLANE = ("icp_plane", 48, ("inliers", "fitness", "rmse", "rmse_point"))
+
+
+def _state(variant, device, N, max_iterations):
+    name = variant[0]
+    N, max_iterations = int(N), int(max_iterations)
+    nbytes = getattr(_capi.lib(), f"dvmvs_{name}_workspace_bytes")(N, max_iterations)
+    if nbytes == 0:
+        raise ValueError(f"dvmvs::{name}: {N} points over {max_iterations} iterations are outside what the kernels take (1 .. 2^28 points, "
+                         f"1 .. {MAX_ITERATIONS} iterations)")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
 
 
 def icp_workspace(device, N, max_iterations):
     """A state block for one registration of ``N`` source points over at most ``max_iterations`` iterations: a float64 device tensor of
     ``dvmvs_icp_workspace_bytes(N, max_iterations)`` bytes, uninitialised (the call writes what it reads).  It is a FRESH block, not a
     per-device one: the transform and the record that ``icp`` returns are views of it."""
-    N, max_iterations = int(N), int(max_iterations)
-    nbytes = _capi.lib().dvmvs_icp_workspace_bytes(N, max_iterations)
-    if nbytes == 0:
-        raise ValueError(f"dvmvs::icp: {N} points over {max_iterations} iterations are outside what the kernels take (1 .. 2^28 points, "
-                         f"1 .. {MAX_ITERATIONS} iterations)")
-    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+    return _state(_POINT, device, N, max_iterations)
+
+
+def icp_plane_workspace(device, N, max_iterations):
+    """``icp_workspace`` for ``icp_plane``: ``dvmvs_icp_plane_workspace_bytes(N, max_iterations)`` bytes, a fresh float64 device tensor."""
+    return _state(_PLANE, device, N, max_iterations)
 
 
 def _cloud(name, label, t, device=None):
@@ -51,6 +67,48 @@ def _host_matrix(name, init):
     return init
 
 
+def _settings(name, max_distance, tolerance, max_iterations):
+    max_distance, tolerance, max_iterations = float(max_distance), float(tolerance), int(max_iterations)
+    if not max_distance > 0.0 or not tolerance >= 0.0:
+        raise ValueError(f"dvmvs::{name}: max_distance must be positive and tolerance not negative (neither NaN), got {max_distance}, {tolerance}")
+    if not 1 <= max_iterations <= MAX_ITERATIONS:
+        raise ValueError(f"dvmvs::{name}: max_iterations must be in 1 .. {MAX_ITERATIONS}, got {max_iterations}")
+    return max_distance, tolerance, max_iterations
+
+
+def _grid(name, grid, target):
+    """The target's grid: built here, or the caller's after a check of its size."""
+    from dvmvs.hip.ops import reconstruction
+    if grid is None:
+        return reconstruction.nearest_build(target)
+    M = int(target.shape[0])
+    check_tensors(name, grid, dtype=torch.uint8, label="grid", device=target.device, contiguous=True)
+    if grid.numel() < _capi.lib().dvmvs_nearest_workspace_bytes(M):
+        raise ValueError(f"dvmvs::{name}: grid is smaller than the workspace of a {M}-point target")
+    return grid
+
+
+def _register(variant, source, target, normals, max_distance, options, max_iterations, tolerance, init, grid):
+    """Enqueues the loop of ``variant`` on clouds and settings that have been checked: ``normals`` and ``options`` are the arguments of its
+    launcher after ``target`` and after ``max_distance``.  Returns ``(T, info)``, views of a fresh state block."""
+    name, head_words, records = variant
+    dev, N, M = source.device, int(source.shape[0]), int(target.shape[0])
+    init = _host_matrix(name, init)
+    grid = _grid(name, grid, target)
+    scratch = _workspace.grown("nearest_query", dev, _capi.lib().dvmvs_nearest_query_workspace_bytes(N, M), torch.uint8)
+    state = _state(variant, dev, N, max_iterations)
+    init_ptr = None if init is None else init.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    launch(f"dvmvs_{name}_fwd", dev, ptr(source), N, ptr(target), *normals, M, ptr(grid), ptr(scratch), scratch.numel(), max_distance, *options,
+           max_iterations, tolerance, init_ptr, ptr(state), state.numel() * 8)
+    words = state.view(torch.int64)
+    info = {"iterations": words[_WORD_ITERATIONS], "status": words[_WORD_STATUS]}
+    for r, key in enumerate(records):                            # inliers are int64, the others float64
+        first = head_words + r * max_iterations
+        info[key] = (words if key == "inliers" else state)[first:first + max_iterations]
+    info["moments"] = state[_WORD_MOMENTS:head_words]
+    return state[:16].view(4, 4), info
+
+
 def icp(source: Tensor, target: Tensor, max_distance: float, init=None, max_iterations: int = 30, with_scale: bool = False,
         tolerance: float = 1e-6, grid: Optional[Tensor] = None):
     """Registers ``source`` (float32 [N,3]) to ``target`` (float32 [M,3], both on one GPU, finite) by trimmed ICP: returns ``(T, info)``,
@@ -63,49 +121,10 @@ def icp(source: Tensor, target: Tensor, max_distance: float, init=None, max_iter
     inliers, or at the limit.  ``init``: a HOST 4x4 (array, nested list or CPU tensor) to start from instead of the identity.  ``grid``:
     the workspace of ``ops.nearest_build(target)`` when the caller has it (it is not changed).  The arithmetic, including the order of
     every sum, is fixed (include/dvmvs_hip.h): ``dvmvs.errors.register_points`` gives the same bits."""
-    from dvmvs.hip.ops import reconstruction
     source = _cloud("icp", "source", source)
-    dev = source.device
-    target = _cloud("icp", "target", target, dev)
-    N, M = int(source.shape[0]), int(target.shape[0])
-    max_distance, tolerance, max_iterations = float(max_distance), float(tolerance), int(max_iterations)
-    if not max_distance > 0.0 or not tolerance >= 0.0:
-        raise ValueError(f"dvmvs::icp: max_distance must be positive and tolerance not negative (neither NaN), got {max_distance}, {tolerance}")
-    if not 1 <= max_iterations <= MAX_ITERATIONS:
-        raise ValueError(f"dvmvs::icp: max_iterations must be in 1 .. {MAX_ITERATIONS}, got {max_iterations}")
-    init = _host_matrix("icp", init)
-    if grid is None:
-        grid = reconstruction.nearest_build(target)
-    else:
-        check_tensors("icp", grid, dtype=torch.uint8, label="grid", device=dev, contiguous=True)
-        if grid.numel() < _capi.lib().dvmvs_nearest_workspace_bytes(M):
-            raise ValueError(f"dvmvs::icp: grid is smaller than the workspace of a {M}-point target")
-    scratch = _workspace.grown("nearest_query", dev, _capi.lib().dvmvs_nearest_query_workspace_bytes(N, M), torch.uint8)
-    state = icp_workspace(dev, N, max_iterations)
-    init_ptr = None if init is None else init.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    launch("dvmvs_icp_fwd", dev, ptr(source), N, ptr(target), M, ptr(grid), ptr(scratch), scratch.numel(), max_distance, int(bool(with_scale)),
-           max_iterations, tolerance, init_ptr, ptr(state), state.numel() * 8)
-    words = state.view(torch.int64)
-    a, b, c = _HEAD_WORDS, _HEAD_WORDS + max_iterations, _HEAD_WORDS + 2 * max_iterations
-    info = {"iterations": words[_WORD_ITERATIONS], "status": words[_WORD_STATUS], "inliers": words[a:b], "fitness": state[b:c],
-            "rmse": state[c:c + max_iterations], "moments": state[_WORD_MOMENTS:_HEAD_WORDS]}
-    return state[:16].view(4, 4), info
-
-
-PLANE_STATUS_NAMES = STATUS_NAMES + ("degenerate geometry",)
-STATUS_DEGENERATE = 4
-# the head of the point-to-plane state block: T | iterations | status | 30 moments, then four arrays per iteration
-_PLANE_HEAD_WORDS = 48
-
-
-def icp_plane_workspace(device, N, max_iterations):
-    """``icp_workspace`` for ``icp_plane``: ``dvmvs_icp_plane_workspace_bytes(N, max_iterations)`` bytes, a fresh float64 device tensor."""
-    N, max_iterations = int(N), int(max_iterations)
-    nbytes = _capi.lib().dvmvs_icp_plane_workspace_bytes(N, max_iterations)
-    if nbytes == 0:
-        raise ValueError(f"dvmvs::icp_plane: {N} points over {max_iterations} iterations are outside what the kernels take (1 .. 2^28 "
-                         f"points, 1 .. {MAX_ITERATIONS} iterations)")
-    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+    target = _cloud("icp", "target", target, source.device)
+    max_distance, tolerance, max_iterations = _settings("icp", max_distance, tolerance, max_iterations)
+    return _register(_POINT, source, target, (), max_distance, (int(bool(with_scale)),), max_iterations, tolerance, init, grid)
 
 
 def icp_plane(source: Tensor, target: Tensor, target_normals: Tensor, max_distance: float, init=None, max_iterations: int = 30,
@@ -118,36 +137,12 @@ def icp_plane(source: Tensor, target: Tensor, target_normals: Tensor, max_distan
     fewer than 6 inliers, at the limit, or with status 4 where the paired geometry (a single plane, two planes) leaves a freedom open, in
     which case T is left as it was.  Nothing is read by the call.  ``init`` and ``grid`` as in ``icp``.  The arithmetic is fixed
     (include/dvmvs_hip.h): ``dvmvs.errors.register_points_plane`` gives the same bits."""
-    from dvmvs.hip.ops import reconstruction
     source = _cloud("icp_plane", "source", source)
-    dev = source.device
-    target = _cloud("icp_plane", "target", target, dev)
-    N, M = int(source.shape[0]), int(target.shape[0])
-    check_tensors("icp_plane", target_normals, label="target_normals", shape=(M, 3), device=dev)
+    target = _cloud("icp_plane", "target", target, source.device)
+    check_tensors("icp_plane", target_normals, label="target_normals", shape=(int(target.shape[0]), 3), device=source.device)
     target_normals = target_normals.contiguous()
-    max_distance, tolerance, max_iterations = float(max_distance), float(tolerance), int(max_iterations)
-    if not max_distance > 0.0 or not tolerance >= 0.0:
-        raise ValueError(f"dvmvs::icp_plane: max_distance must be positive and tolerance not negative (neither NaN), got {max_distance}, "
-                         f"{tolerance}")
-    if not 1 <= max_iterations <= MAX_ITERATIONS:
-        raise ValueError(f"dvmvs::icp_plane: max_iterations must be in 1 .. {MAX_ITERATIONS}, got {max_iterations}")
-    init = _host_matrix("icp_plane", init)
-    if grid is None:
-        grid = reconstruction.nearest_build(target)
-    else:
-        check_tensors("icp_plane", grid, dtype=torch.uint8, label="grid", device=dev, contiguous=True)
-        if grid.numel() < _capi.lib().dvmvs_nearest_workspace_bytes(M):
-            raise ValueError(f"dvmvs::icp_plane: grid is smaller than the workspace of a {M}-point target")
-    scratch = _workspace.grown("nearest_query", dev, _capi.lib().dvmvs_nearest_query_workspace_bytes(N, M), torch.uint8)
-    state = icp_plane_workspace(dev, N, max_iterations)
-    init_ptr = None if init is None else init.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    launch("dvmvs_icp_plane_fwd", dev, ptr(source), N, ptr(target), ptr(target_normals), M, ptr(grid), ptr(scratch), scratch.numel(),
-           max_distance, max_iterations, tolerance, init_ptr, ptr(state), state.numel() * 8)
-    words = state.view(torch.int64)
-    a, I = _PLANE_HEAD_WORDS, max_iterations
-    info = {"iterations": words[_WORD_ITERATIONS], "status": words[_WORD_STATUS], "inliers": words[a:a + I], "fitness": state[a + I:a + 2 * I],
-            "rmse": state[a + 2 * I:a + 3 * I], "rmse_point": state[a + 3 * I:a + 4 * I], "moments": state[_WORD_MOMENTS:_PLANE_HEAD_WORDS]}
-    return state[:16].view(4, 4), info
+    max_distance, tolerance, max_iterations = _settings("icp_plane", max_distance, tolerance, max_iterations)
+    return _register(_PLANE, source, target, (ptr(target_normals),), max_distance, (), max_iterations, tolerance, init, grid)
 
 
 def transform_points(points: Tensor, T: Tensor, out: Optional[Tensor] = None) -> Tensor:

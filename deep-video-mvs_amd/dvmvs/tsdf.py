@@ -1115,39 +1115,29 @@ def apply_transform(verts, transform):
 def _aligned_score(volume, align_distance, align_scale, align_plane=None, **score):
     """``score_against`` with its row on the host; with ``align_distance`` also the entries ``_errors3d.npz`` gains.  Row, transform and
     record come down as ONE float64 tensor (a float32 row is exact in float64).  ``align_plane``: None, or ``score_against``'s
-    point-to-plane keywords."""
+    point-to-plane keywords; the entries then include the point RMSE and the status name."""
     if align_distance is None:
         result = volume.score_against(**score)
         return (result[0].cpu().numpy(),) + tuple(result[1:]) + ({},)
     score = {"return_sizes": False, "sample_density": None, "voxel": None, "visible_from": None, **score}
-    if align_plane is not None:
-        return _aligned_score_plane(volume, align_distance, align_plane, score)
-    result, info = volume._score_against(align_distance=align_distance, align_scale=align_scale, return_transform=True, **score)
+    plane = align_plane is not None
+    result, info = volume._score_against(align_distance=align_distance, align_scale=False if plane else align_scale,
+                                         return_transform=True, **(align_plane or {}), **score)
     last = (info["iterations"] - 1).clamp(min=0).reshape(1)      # (selected on the device: indexing with a 0-d tensor would read it)
-    down = torch.cat([result[0].double(), result[-1].reshape(-1), info["iterations"].double().reshape(1), info["status"].double().reshape(1),
-                      info["fitness"].index_select(0, last), info["rmse"].index_select(0, last)]).cpu().numpy()
+    record = ("fitness", "rmse", "rmse_point") if plane else ("fitness", "rmse")
+    down = torch.cat([result[0].double(), result[-1].reshape(-1), info["iterations"].double().reshape(1), info["status"].double().reshape(1)]
+                     + [info[key].index_select(0, last) for key in record]).cpu().numpy()
     extra = {"transform": down[6:22].reshape(4, 4), "align_iterations": np.int64(down[22]), "align_status": np.int64(down[23]),
              "align_fitness": np.float64(down[24]), "align_rmse": np.float64(down[25])}
-    from dvmvs.errors import REGISTRATION_STATUS
-    print("Registered the surface to the ground truth within {} m{}: {} after {} iterations, fitness {:.4f}, rmse {:.5f} m".format(
-        align_distance, " with scale" if align_scale else "", REGISTRATION_STATUS[int(down[23])], int(down[22]), down[24], down[25]))
-    return (down[:6].astype(np.float32),) + tuple(result[1:-1]) + (extra,)
-
-
-def _aligned_score_plane(volume, align_distance, align_plane, score):
-    """``_aligned_score`` with the point-to-plane registration: the same single download, with the point RMSE and the status name."""
-    from dvmvs.errors import REGISTRATION_PLANE_STATUS
-    result, info = volume._score_against(align_distance=align_distance, align_scale=False, return_transform=True, **align_plane, **score)
-    last = (info["iterations"] - 1).clamp(min=0).reshape(1)
-    down = torch.cat([result[0].double(), result[-1].reshape(-1), info["iterations"].double().reshape(1), info["status"].double().reshape(1),
-                      info["fitness"].index_select(0, last), info["rmse"].index_select(0, last),
-                      info["rmse_point"].index_select(0, last)]).cpu().numpy()
-    name = REGISTRATION_PLANE_STATUS[int(down[23])]
-    extra = {"transform": down[6:22].reshape(4, 4), "align_iterations": np.int64(down[22]), "align_status": np.int64(down[23]),
-             "align_fitness": np.float64(down[24]), "align_rmse": np.float64(down[25]), "align_rmse_point": np.float64(down[26]),
-             "align_status_name": np.array(name)}
-    print("Registered the surface to the ground truth within {} m, point to plane: {} after {} iterations, fitness {:.4f}, plane rmse {:.5f} m, "
-          "point rmse {:.5f} m".format(align_distance, name, int(down[22]), down[24], down[25], down[26]))
+    from dvmvs.errors import REGISTRATION_PLANE_STATUS, REGISTRATION_STATUS
+    name = (REGISTRATION_PLANE_STATUS if plane else REGISTRATION_STATUS)[int(down[23])]
+    if plane:                                                    # with the point RMSE and the status name
+        extra.update(align_rmse_point=np.float64(down[26]), align_status_name=np.array(name))
+        print("Registered the surface to the ground truth within {} m, point to plane: {} after {} iterations, fitness {:.4f}, plane rmse {:.5f} "
+              "m, point rmse {:.5f} m".format(align_distance, name, int(down[22]), down[24], down[25], down[26]))
+    else:
+        print("Registered the surface to the ground truth within {} m{}: {} after {} iterations, fitness {:.4f}, rmse {:.5f} m".format(
+            align_distance, " with scale" if align_scale else "", name, int(down[22]), down[24], down[25]))
     return (down[:6].astype(np.float32),) + tuple(result[1:-1]) + (extra,)
 
 

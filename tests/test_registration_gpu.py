@@ -57,10 +57,11 @@ def assert_record(got_T, got, want_T, want, label):
 
 
 # ---- one iteration ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 255, 256, 257, 1000, 4099])
+@pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 255, 256, 257, 1000, 4099, 66561])
 def test_moments_of_one_iteration(hip_device, N):
     """One iteration from a T_0 that moves the points; max_distance trims none, about half and all of the pairs; the source starts 4 bytes
-    off a 16-byte boundary; the call runs on a side stream."""
+    off a 16-byte boundary; the call runs on a side stream.  N = 66561 gives 66 partial rows: lanes 0 and 1 of the solve add two each, and
+    the last row holds one point."""
     from dvmvs.hip import registration
     rng = np.random.default_rng(3000 + N)
     target = rng.normal(size=(500, 3)).astype(np.float32)

@@ -49,7 +49,8 @@ def test_single_triangle(hip_device):
     assert assert_samples(hip_device, verts, np.array([[2, 0, 1]], np.int32), 777.0, 3) > 5000
 
 
-@pytest.mark.parametrize("F", [1, 255, 256, 257, 1023, 1024, 1025, 70000])
+# the last two: 1024 and 1025 workgroup totals, so every thread of the one-workgroup scan has a total, then chunks of two with a short last one
+@pytest.mark.parametrize("F", [1, 255, 256, 257, 1023, 1024, 1025, 70000, 1024 * 1024, 1024 * 1024 + 1])
 def test_small_triangles_across_the_scan_blocks(hip_device, F):
     assert assert_samples(hip_device, *cases.small_triangles(F), 300.0) > 2 * F
 
@@ -112,9 +113,10 @@ def assert_voxels(dev, points, voxel):
     return len(want)
 
 
-@pytest.mark.parametrize("N", [1, 63, 64, 65, 1000, 50000])
+# the last: 1025 workgroup totals for the one-workgroup scan (chunks of two, the last one short), at a voxel that leaves most points alone
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 1000, 50000, 1024 * 1024 + 1])
 def test_gaussian_clouds(hip_device, N):
-    assert_voxels(hip_device, cases.gaussian(N, 3 if N == 50000 else N), 0.25)
+    assert_voxels(hip_device, cases.gaussian(N, 3 if N >= 50000 else N), 0.25 if N <= 50000 else 0.02)
 
 
 def test_coincident_points(hip_device):
