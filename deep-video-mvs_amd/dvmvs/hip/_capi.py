@@ -165,6 +165,12 @@ SIGNATURES = {
     "dvmvs_icp_plane_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, _c_int]),
     "dvmvs_icp_plane_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_size_t, ctypes.c_float,
                                      _c_int, _c_dbl, ctypes.POINTER(ctypes.c_double), _c_fp, ctypes.c_size_t, _c_stream]),
+    "dvmvs_implicit_band_fwd": (_c_int, [_c_fp, ctypes.c_longlong] + [ctypes.c_float] * 4 + [_c_int] * 3 + [ctypes.c_float, _c_fp, _c_stream]),
+    "dvmvs_implicit_nodes_fwd": (_c_int, [_c_fp, ctypes.c_longlong] + [ctypes.c_float] * 4 + [_c_int] * 3 + [_c_fp, _c_stream]),
+    "dvmvs_implicit_values_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_int, ctypes.c_float, _c_int,
+                                           _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_implicit_trim_fwd": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_int, _c_int, _c_int, _c_fp, _c_fp,
+                                         _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -201,6 +207,8 @@ ADDED_WITHIN_ABI_POINT_NEIGHBOURS = ("dvmvs_knn_fwd", "dvmvs_radius_count_fwd", 
 ADDED_WITHIN_ABI_POINT_NORMALS = ("dvmvs_point_normals_fwd",)
 # ... and the fourteenth (registering a point cloud to another with normals by point-to-plane ICP)
 ADDED_WITHIN_ABI_REGISTRATION_PLANE = ("dvmvs_icp_plane_workspace_bytes", "dvmvs_icp_plane_fwd")
+# ... and the fifteenth (the implicit signed distance of an oriented point cloud on a voxel grid, and the trimming of its mesh)
+ADDED_WITHIN_ABI_IMPLICIT = ("dvmvs_implicit_band_fwd", "dvmvs_implicit_nodes_fwd", "dvmvs_implicit_values_fwd", "dvmvs_implicit_trim_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -222,7 +230,8 @@ def lib():
         added = (ADDED_WITHIN_ABI + ADDED_WITHIN_ABI_DEPTH_ERRORS + ADDED_WITHIN_ABI_TSDF_RAYCAST + ADDED_WITHIN_ABI_TSDF_FUSE
                  + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER
                  + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE + ADDED_WITHIN_ABI_MESH_COMPONENTS
-                 + ADDED_WITHIN_ABI_POINT_NEIGHBOURS + ADDED_WITHIN_ABI_POINT_NORMALS + ADDED_WITHIN_ABI_REGISTRATION_PLANE)
+                 + ADDED_WITHIN_ABI_POINT_NEIGHBOURS + ADDED_WITHIN_ABI_POINT_NORMALS + ADDED_WITHIN_ABI_REGISTRATION_PLANE
+                 + ADDED_WITHIN_ABI_IMPLICIT)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

@@ -807,10 +807,10 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         evaluate_3d=False, threshold_3d=0.05, filter_consistency=False, consistency_views=2, consistency_sources=4, consistency_pixel=1.0,
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, evaluate_3d_align_plane=False,
-        evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, groundtruth_transform=None,
-        point_normals_neighbours=None, point_normals_max_distance=None, clean_points_neighbours=None, clean_points_ratio=2.0,
-        clean_points_max_distance=None, clean_points_radius=None, clean_points_min_neighbours=None, clean_mesh_area=None,
-        clean_mesh_faces=None, clean_mesh_largest=False):
+        evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, point_mesh_voxel=None, point_mesh_radius=None,
+        point_mesh_neighbours=32, point_mesh_min_neighbours=3, groundtruth_transform=None, point_normals_neighbours=None,
+        point_normals_max_distance=None, clean_points_neighbours=None, clean_points_ratio=2.0, clean_points_max_distance=None,
+        clean_points_radius=None, clean_points_min_neighbours=None, clean_mesh_area=None, clean_mesh_faces=None, clean_mesh_largest=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
     predictions (``keyframe_<dataset>_<system>_predictions_<scene>*.npz`` in ``prediction_folder``) into a TSDF volume and writes
     the mesh; optionally the same from the ground-truth depth maps.  Images and depth PNGs are read with the package's own
@@ -894,11 +894,22 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     the point came from (``dvmvs.consistency.fused_point_views``).  The cloud with its normals is written ADDITIONALLY as
     ``<mesh name>_pointcloud_normals.ply`` (``TSDFFusion.pcwrite_normals``), without the points that have no valid normal (fewer than
     three neighbours within the distance, or all of them in one place), and the share of valid points is printed; every other file is
-    what it is without these flags, byte for byte."""
+    what it is without these flags, byte for byte.
+
+    ``point_mesh_voxel`` (metres) with ``point_mesh_radius`` (metres; None: 2.5 voxels), ``point_mesh_neighbours`` (1 .. 32) and
+    ``point_mesh_min_neighbours``, needing ``filter_consistency``, ``save_point_cloud`` and ``point_normals_neighbours``: the cloud that
+    ``_pointcloud_normals.ply`` holds is meshed on the device (``dvmvs.implicit.mesh_points_device``: the implicit moving-least-squares
+    signed distance of the oriented points on a grid of ``point_mesh_voxel``, with weights that reach zero at ``point_mesh_radius``, then
+    marching cubes, without the crossings at the edge of the band around the points) and written ADDITIONALLY as
+    ``<mesh name>_pointcloud_mesh.ply`` (``TSDFFusion.meshwrite``; normals and colours are those of the nearest point); with
+    ``clean_mesh_*`` that mesh goes through the same component filter.  Every other file is what it is without these flags, byte for
+    byte."""
     clean = _clean_filter(clean_mesh_area, clean_mesh_faces, clean_mesh_largest)
     clean_points = _clean_points_filter(save_point_cloud, clean_points_neighbours, clean_points_ratio, clean_points_max_distance,
                                         clean_points_radius, clean_points_min_neighbours)
     point_normals = _point_normals_settings(save_point_cloud, point_normals_neighbours, point_normals_max_distance)
+    point_mesh = _point_mesh_settings(filter_consistency, save_point_cloud, point_normals, point_mesh_voxel, point_mesh_radius,
+                                      point_mesh_neighbours, point_mesh_min_neighbours)
     if save_point_cloud and not filter_consistency:
         raise ValueError("save_point_cloud needs filter_consistency: the point cloud is made of the pixels the filter keeps")
     protocol_3d = evaluate_3d_density is not None or evaluate_3d_voxel is not None or groundtruth_mesh is not None
@@ -992,13 +1003,14 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         volume_bounds = TSDFFusion.calculate_volume_bounds(keyframe_predictions, keyframe_poses, scaled_K)
     volume_bounds *= 1.05      # margin for errors in the bounds
 
-    point_cloud = clean_point_cloud = normals_point_cloud = None
+    point_cloud = clean_point_cloud = normals_point_cloud = point_cloud_mesh = None
     if filter_consistency:
         system_name = f"{system_name}+consistent"
         if keyframe_predictions:
-            keyframe_predictions, point_cloud, clean_point_cloud, normals_point_cloud = _filter_keyframes(
+            keyframe_predictions, point_cloud, clean_point_cloud, normals_point_cloud, point_cloud_mesh = _filter_keyframes(
                 keyframe_predictions, keyframe_images if save_point_cloud else None, keyframe_poses, scaled_K, keyframe_segments,
-                consistency_views, consistency_sources, consistency_pixel, consistency_relative, device, clean_points, point_normals)
+                consistency_views, consistency_sources, consistency_pixel, consistency_relative, device, clean_points, point_normals,
+                None if point_mesh is None else point_mesh + (clean,))
 
     if clean is not None:
         system_name = f"{system_name}+clean"
@@ -1037,6 +1049,12 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
             TSDFFusion.pcwrite_normals(system_mesh_name + "_pointcloud_normals.ply",
                                        *(normals_point_cloud if normals_point_cloud is not None
                                          else (np.zeros((0, 6), np.float32), np.zeros((0, 3), np.float32))))
+        if point_mesh is not None:
+            print("Saving mesh of the point cloud to", system_mesh_name + "_pointcloud_mesh.ply")
+            TSDFFusion.meshwrite(system_mesh_name + "_pointcloud_mesh.ply",
+                                 *(point_cloud_mesh if point_cloud_mesh is not None
+                                   else (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32), np.zeros((0, 3), np.float32),
+                                         np.zeros((0, 3), np.uint8))))
     if evaluate_3d:
         if protocol_3d:
             visible_from = None
@@ -1055,11 +1073,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
 
 
 def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sources, pixel_threshold, relative_threshold, device,
-                      clean_points=None, point_normals=None):
+                      clean_points=None, point_normals=None, point_mesh=None):
     """The keyframe predictions filtered by consistency (a list of host arrays, as they came) and, with ``images``, the fused point cloud
     [P,6] xyzrgb on the host, with ``clean_points`` (an ``OutlierFilter``) also the rows of it that the filter keeps, chosen on the
-    device, and with ``point_normals`` (``(neighbours, max_distance)``) also ``(xyzrgb [Q,6], normals [Q,3])``: the points of the cleaned
-    cloud (of the fused one without ``clean_points``) that have a valid normal, oriented toward the camera centre of their keyframe."""
+    device, with ``point_normals`` (``(neighbours, max_distance)``) also ``(xyzrgb [Q,6], normals [Q,3])``: the points of the cleaned
+    cloud (of the fused one without ``clean_points``) that have a valid normal, oriented toward the camera centre of their keyframe, and
+    with ``point_mesh`` (``(voxel, radius, neighbours, min_neighbours, clean)``) also the mesh of those points and normals
+    (``mesh_points_device``) as the four host arrays of ``TSDFFusion.meshwrite``."""
     from dvmvs.consistency import filter_depths, fused_point_cloud, fused_point_views, nearest_sources
     depths = torch.as_tensor(np.stack(predictions).astype(np.float32), device=device)
     cameras = torch.as_tensor(np.stack(poses).astype(np.float32), device=device)
@@ -1069,7 +1089,7 @@ def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sour
     valid = torch.isfinite(depths) & (depths > 0)
     print("Consistency filter: kept {:.1f} % of the valid pixels of {} keyframes".format(
         100.0 * float((kept > 0).sum()) / max(int(valid.sum()), 1), len(predictions)))
-    cloud = clean_cloud = normals_cloud = None
+    cloud = clean_cloud = normals_cloud = cloud_mesh = None
     if images is not None:
         averaged, _, points = filter_depths(depths, K, cameras, sources, average=True, with_count=False, with_points=True, **thresholds)
         cloud = fused_point_cloud(averaged, points, np.stack(images))
@@ -1089,8 +1109,15 @@ def _filter_keyframes(predictions, images, poses, K, segments, min_views, n_sour
             normals_cloud = (oriented[valid].cpu().numpy(), normals[valid].cpu().numpy())
             print("Point normals: {:.1f} % of the {} points have a valid normal".format(
                 100.0 * len(normals_cloud[0]) / max(int(oriented.shape[0]), 1), int(oriented.shape[0])))
+            if point_mesh is not None and len(normals_cloud[0]) > 0:
+                from dvmvs.implicit import mesh_points_device
+                voxel, radius, neighbours, min_neighbours, clean = point_mesh
+                cloud_mesh = tuple(a.cpu().numpy() for a in mesh_points_device(oriented[valid], normals[valid], voxel, radius, neighbours,
+                                                                                min_neighbours, clean=clean))
+                print("Point mesh: {} vertices and {} faces from {} points".format(len(cloud_mesh[0]), len(cloud_mesh[1]),
+                                                                                   len(normals_cloud[0])))
         cloud = cloud.cpu().numpy()
-    return list(kept.cpu().numpy()), cloud, clean_cloud, normals_cloud
+    return list(kept.cpu().numpy()), cloud, clean_cloud, normals_cloud, cloud_mesh
 
 
 def load_transform(filename):
@@ -1210,6 +1237,30 @@ def _point_normals_settings(save_point_cloud, neighbours, max_distance):
     if not save_point_cloud:
         raise ValueError("point_normals_neighbours estimates the normals of the cloud of save_point_cloud: it needs save_point_cloud")
     return int(neighbours), np.inf if max_distance is None else float(max_distance)
+
+
+def _point_mesh_settings(filter_consistency, save_point_cloud, point_normals, voxel, radius, neighbours, min_neighbours):
+    """``(voxel, radius, neighbours, min_neighbours)`` of ``run``'s four ``point_mesh_*`` settings (``radius`` 2.5 voxels when not given), None
+    when ``point_mesh_voxel`` is not given; each refusal names its flag."""
+    def number(value):
+        return not isinstance(value, bool) and isinstance(value, (int, float, np.integer, np.floating))
+    if voxel is not None and not (number(voxel) and 0.0 < float(voxel) < np.inf):
+        raise ValueError(f"point_mesh_voxel must be a positive voxel size in metres, got {voxel!r}")
+    if radius is not None and not (number(radius) and 0.0 < float(radius) < np.inf):
+        raise ValueError(f"point_mesh_radius must be a positive distance in metres, got {radius!r}")
+    if not (number(neighbours) and float(neighbours).is_integer() and 1 <= int(neighbours) <= 32):
+        raise ValueError(f"point_mesh_neighbours must be a whole number of neighbours in [1, 32], got {neighbours!r}")
+    if not (number(min_neighbours) and float(min_neighbours).is_integer() and 1 <= int(min_neighbours) < 2 ** 31):
+        raise ValueError(f"point_mesh_min_neighbours must be a whole number of neighbours, at least 1, got {min_neighbours!r}")
+    if voxel is None:
+        if radius is not None or int(neighbours) != 32 or int(min_neighbours) != 3:
+            raise ValueError("point_mesh_radius, point_mesh_neighbours and point_mesh_min_neighbours say how point_mesh_voxel meshes: they need "
+                             "point_mesh_voxel")
+        return None
+    if not (filter_consistency and save_point_cloud and point_normals is not None):
+        raise ValueError("point_mesh_voxel meshes the cloud with normals of point_normals_neighbours: it needs filter_consistency, "
+                         "save_point_cloud and point_normals_neighbours")
+    return float(voxel), 2.5 * float(voxel) if radius is None else float(radius), int(neighbours), int(min_neighbours)
 
 
 def _clean_entries(volume, clean):
@@ -1346,6 +1397,16 @@ def build_parser():
     parser.add_argument("--point_normals_max_distance", default=None, type=float,
                         help="with --point_normals_neighbours: neighbours are searched within this distance only, metres (bounds the search; "
                              "a point with fewer than three inside it gets no normal and is left out of the file)")
+    parser.add_argument("--point_mesh_voxel", default=None, type=float,
+                        help="with --filter_consistency --save_point_cloud --point_normals_neighbours: mesh the point cloud with normals on "
+                             "the device (implicit moving-least-squares signed distance on a grid of this voxel size, metres, then marching "
+                             "cubes); the mesh is written additionally as <mesh name>_pointcloud_mesh.ply")
+    parser.add_argument("--point_mesh_radius", default=None, type=float,
+                        help="with --point_mesh_voxel: the distance at which a point's weight reaches zero, metres (default: 2.5 voxels)")
+    parser.add_argument("--point_mesh_neighbours", default=32, type=int,
+                        help="with --point_mesh_voxel: at most this many nearest points within the radius shape a node (1 .. 32)")
+    parser.add_argument("--point_mesh_min_neighbours", default=3, type=int,
+                        help="with --point_mesh_voxel: a node with fewer points with a normal within the radius carries no surface")
     parser.add_argument("--clean_points_neighbours", default=None, type=int,
                         help="with --save_point_cloud: statistical outlier removal of the fused cloud on the device, over this many nearest "
                              "neighbours (1 .. 32); the result is written additionally as <mesh name>_pointcloud_clean.ply")

@@ -71,7 +71,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_point_normals_fwd (oriented normals of points from rows of nearest neighbours); no earlier signature
  * changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_icp_plane_* (registering a point cloud to another with normals by point-to-plane ICP); no earlier
- * signature changed, the number stays 11 by the same rule. */
+ * signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_implicit_* (the implicit moving-least-squares signed distance of an oriented point cloud on a voxel grid,
+ * and the trimming of the mesh that marching cubes makes of it); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -1149,6 +1151,48 @@ int dvmvs_outlier_statistics_fwd(const float* dist, const int* index, long long 
 int dvmvs_point_normals_fwd(const float* points, long long N, const float* target, long long M, const int* index, int k,
                             const float* viewpoints, long long V, const int* view, float* normals, float* curvature, unsigned char* valid,
                             dvmvs_stream_t stream);
+
+/*
+ * Implicit moving-least-squares (IMLS) signed distance of an oriented point cloud on a voxel grid, and the trimming of the mesh that
+ * marching cubes makes of it (ABI 11, later addition; csrc/implicit_surface.hip).  The reference project has nothing for this: the
+ * definition is this project's own (dvmvs/implicit.py is its host form).
+ *   points [M,3], normals [M,3]  fp32, FINITE (a precondition, not checked); a normal of (0,0,0) marks a point without one
+ *   grid              origin (three fp32 numbers, finite), voxel > 0 finite, X, Y, Z >= 1 nodes, z fastest, at most 2^31 nodes.  Node
+ *                     (i, j, k) lies at x_c = fl(fl(fl(i_c) * voxel) + origin_c) in fp32, the multiply and the add rounded separately.
+ *   radius            fp32, finite, > 0: where the weights reach zero, and the max_distance of the search
+ * dvmvs_implicit_band_fwd: sets mask [X,Y,Z] uint8 to 1 at a SUPERSET of the nodes that have at least one candidate under the fp32 test
+ *   of dvmvs_knn_fwd(nodes, points, ..., max_distance = radius) (derivation: csrc/implicit_surface.hip); other bytes are left as they
+ *   were (the caller zeroes the mask).  How many more nodes are marked changes no result.  Points outside the grid mark what lies inside
+ *   it; no address is formed from an index outside [0, dim).  Many lanes store the same constant byte: a benign race.
+ * dvmvs_implicit_nodes_fwd: nodes [A,3] fp32, the positions of the nodes with the linear indices linear [A] int64 ((i * Y + j) * Z + k,
+ *   each inside the grid: a precondition).
+ * dvmvs_implicit_values_fwd: index [A,k] int32, 1 <= k <= 32: row a as dvmvs_knn_fwd(nodes, points, k, radius, 0) wrote it.  All
+ *   arithmetic is fp64 from the fp32 inputs, +, -, *, / only, each operation correctly rounded, no FMA contraction.  Node a, over its row
+ *   in slot order: a slot is USED when 0 <= j < M and normals[j] != (0,0,0) (a slot outside [0, M) never becomes an address).
+ *   h2 = fp64(radius) fp64(radius).  For each used slot: e = x - points[j] (exact); d2 = (e_x e_x + e_y e_y) + e_z e_z; t = 1 - d2 / h2,
+ *   and t < 0 becomes 0 (the slot still counts); w = (t t) t; s = (n_x e_x + n_y e_y) + n_z e_z; num += w s, den += w, both from 0.0.
+ *   The node is VALID when at least min_neighbours (>= 1) slots were used and den > 0: then volume[linear[a]] = fp32(num / den) and
+ *   valid[linear[a]] = 1.  Nothing is written for another node: the caller pre-fills volume [total] with fp32(radius), a positive fill,
+ *   and valid [total] uint8 with 0.  A linear index outside [0, total) is skipped.  One node per lane and nothing crosses lanes, so the
+ *   outputs are bit-identical run to run, on any stream, however the nodes are split into calls, and equal to the host form.
+ * dvmvs_implicit_trim_fwd: verts [V,3] fp32 in index space (of marching cubes with origin 0 and voxel size 1) and faces [F,3] int32 ->
+ *   keep_vertex [V] uint8: 1 when the nodes floor(pos) and ceil(pos) (componentwise) are inside the grid and both valid;
+ *   keep_face [F] uint8: 1 when its three vertices are inside [0, V) and kept.  Two launches.
+ * Every entry enqueues on the given stream, reads nothing on the host, and with nothing to do (M, A or V and F of 0) returns 0.
+ * DVMVS_EINVAL for a null or misaligned pointer (4 bytes; linear 8; the uint8 arrays none), a negative count, M < 1 (values), k outside
+ * [1,32], min_neighbours < 1, total < 1, a radius or voxel that is not finite and > 0, an origin that is not finite, a dimension < 1;
+ * DVMVS_EUNSUPPORTED above 2^28 points or candidate nodes of one call, 2^31 nodes, 2^31 - 1 vertices or faces.  Nothing is enqueued in
+ * either case.
+ */
+int dvmvs_implicit_band_fwd(const float* points, long long M, float origin_x, float origin_y, float origin_z, float voxel, int X, int Y,
+                            int Z, float radius, unsigned char* mask, dvmvs_stream_t stream);
+int dvmvs_implicit_nodes_fwd(const long long* linear, long long A, float origin_x, float origin_y, float origin_z, float voxel, int X,
+                             int Y, int Z, float* nodes, dvmvs_stream_t stream);
+int dvmvs_implicit_values_fwd(const float* nodes, long long A, const float* points, const float* normals, long long M, const int* index,
+                              int k, float radius, int min_neighbours, const long long* linear, long long total, float* volume,
+                              unsigned char* valid, dvmvs_stream_t stream);
+int dvmvs_implicit_trim_fwd(const float* verts, long long V, const int* faces, long long F, const unsigned char* valid, int X, int Y,
+                            int Z, unsigned char* keep_vertex, unsigned char* keep_face, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
