@@ -17,11 +17,24 @@ RESIDUAL_NONE, RESIDUAL_SAME, RESIDUAL_NEAREST_UP2 = 0, 1, 2
 # ----------------------------------------------------------------------------------------------------------------------
 # hidden-state warp
 # ----------------------------------------------------------------------------------------------------------------------
+def _check_hidden_warp(name, image_src, depth_dst, src_trans_dst, camera_matrix, dst=None):
+    """The kernel indexes depth, transform and intrinsics by the SOURCE's batch and map size: all of them (and the destination) must
+    have it.  Every malformed argument is reported before a misplaced one, and nothing is launched."""
+    check_tensors(name, image_src, label="image_src", shape=(None, None, None, None), on_gpu=False)
+    B, C, H, W = image_src.shape
+    check_tensors(name, depth_dst, label="depth_dst", shape=(B, 1, H, W), on_gpu=False)
+    check_tensors(name, src_trans_dst, label="src_trans_dst", shape=(B, 4, 4), on_gpu=False)
+    check_tensors(name, camera_matrix, label="camera_matrix", shape=(B, 3, 3), on_gpu=False)
+    if dst is not None:
+        check_tensors(name, dst, label="dst", shape=(B, C, H, W), on_gpu=False)
+    check_tensors(name, image_src, depth_dst, src_trans_dst, camera_matrix, *(() if dst is None else (dst,)))
+    return B, C, H, W
+
+
 @custom_op("hidden_warp", fake=lambda image_src, depth_dst, src_trans_dst, camera_matrix, zero_invalid: torch.empty_like(image_src))
 def hidden_warp(image_src: Tensor, depth_dst: Tensor, src_trans_dst: Tensor, camera_matrix: Tensor,
                 zero_invalid: bool) -> Tensor:
-    check_tensors("hidden_warp", image_src, depth_dst, src_trans_dst, camera_matrix)
-    B, C, H, W = image_src.shape
+    B, C, H, W = _check_hidden_warp("hidden_warp", image_src, depth_dst, src_trans_dst, camera_matrix)
     image_src = image_src.contiguous()
     out = torch.empty_like(image_src)
     launch("dvmvs_hidden_warp_fwd", image_src.device, ptr(image_src), ptr(depth_dst.contiguous()), ptr(src_trans_dst.contiguous()),
@@ -50,9 +63,8 @@ torch.library.register_autograd("dvmvs::hidden_warp", _hidden_warp_backward, set
 
 
 def hidden_warp_into(image_src: Tensor, depth_dst: Tensor, src_trans_dst: Tensor, camera_matrix: Tensor, zero_invalid: bool, dst: Tensor) -> Tensor:
-    check_tensors("hidden_warp_into", image_src, depth_dst, src_trans_dst, camera_matrix, dst)
-    B, C, H, W = image_src.shape
-    if not (image_src.is_contiguous() and dst.is_contiguous() and tuple(dst.shape) == (B, C, H, W)):
+    B, C, H, W = _check_hidden_warp("hidden_warp_into", image_src, depth_dst, src_trans_dst, camera_matrix, dst)
+    if not (image_src.is_contiguous() and dst.is_contiguous()):
         raise ValueError("dvmvs::hidden_warp_into: source and destination must be contiguous [B,C,H,W]")
     launch("dvmvs_hidden_warp_fwd", image_src.device, ptr(image_src), ptr(depth_dst.contiguous()), ptr(src_trans_dst.contiguous()),
            ptr(camera_matrix.contiguous()), ptr(dst), B, C, H, W, int(bool(zero_invalid)))

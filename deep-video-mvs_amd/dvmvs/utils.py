@@ -180,6 +180,13 @@ def warp_frame_depth(image_src, depth_dst, src_trans_dst, camera_matrix, normali
         raise ValueError(f"Input src_trans_dst must have a shape (B, 4, 4). Got: {src_trans_dst.shape}.")
     if camera_matrix.dim() != 3 or tuple(camera_matrix.shape[-2:]) != (3, 3):
         raise ValueError(f"Input camera_matrix must have a shape (B, 3, 3). Got: {camera_matrix.shape}.")
+    # depth, transform and intrinsics are read per item and per pixel of image_src: one batch, one map size (grid_sample raises too)
+    B, _, H, W = image_src.shape
+    if tuple(depth_dst.shape) != (B, 1, H, W):
+        raise ValueError(f"Input depth_dst must have the shape ({B}, 1, {H}, {W}) of image_src's batch and map. Got: {depth_dst.shape}")
+    if src_trans_dst.shape[0] != B or camera_matrix.shape[0] != B:
+        raise ValueError(f"Inputs src_trans_dst and camera_matrix must have image_src's batch size {B}. "
+                         f"Got: {src_trans_dst.shape} and {camera_matrix.shape}.")
     if normalize_points or sampling_mode != "bilinear":
         raise NotImplementedError("the HIP hidden-state warp implements normalize_points=False, sampling_mode='bilinear' "
                                   "(the only configuration the depth networks use)")

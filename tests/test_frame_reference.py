@@ -1,12 +1,21 @@
 """tests/frame_reference.py pinned on the CPU, so that the GPU tests of the frame-path kernels (tests/test_frame_kernels_gpu.py) do not
 rest on an unchecked reference: its float32 results are the plain ATen expressions the older tests use (bit for bit where those are
 single ops) and what the product's CPU modules compute, its float64 results are the same algebra, and four answers are computed by
-hand."""
+hand.  The references of the recurrent chain (gates, gates on partial sums, hidden-state warp: tests/test_state_kernels_gpu.py) are the
+oracle bit for bit in float32 and ATen's LayerNorm / CELU / grid_sample in float64; the warp cases of tests/state_cases.py are proven
+here to hold the geometry classes they are built for."""
+import math
+import os
+
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import dvmvs_oracle as orc
 import frame_reference as fr
+import state_cases as sc
+import synthetic as syn
 
 
 def _rand(*shape, seed=0, scale=1.0):
@@ -166,3 +175,114 @@ def test_gradients_are_autograd_of_the_aten_ops():
     assert torch.equal(gx, x64.grad) and torch.equal(gw, w64.grad)
     gx32, gw32 = fr.gradients(lambda a, b, dtype: fr.depthwise(a, b, None, 2, dtype=dtype), (x, w), gd)
     assert gx32.dtype == torch.float32 and float((gx32.double() - gx).abs().max()) <= 1e-5 and float((gw32.double() - gw).abs().max()) <= 1e-4
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the recurrent chain: float32 = the oracle bit for bit, float64 = ATen's own ops, the fixtures of tests/golden
+# ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("H,W", sc.GATE_MAPS)
+def test_lstm_gates_is_the_oracle_and_aten(H, W):
+    B, hid = 3, 5
+    cc, c = sc.gate_inputs(B, hid, H, W, seed=100 + H * W)
+    h, cn = fr.lstm_gates(cc, c)
+    eh, ec = orc.lstm_gates(cc, c)
+    assert h.dtype == torch.float32 and torch.equal(h, eh) and torch.equal(cn, ec)
+    # float64: torch's own LayerNorm, CELU and sigmoid
+    cc64, c64 = cc.double(), c.double()
+    i, f, o, g = torch.split(cc64, hid, dim=1)
+    c_next = F.layer_norm(torch.sigmoid(f) * c64 + torch.sigmoid(i) * F.celu(F.layer_norm(g, [H, W], eps=1e-5)), [H, W], eps=1e-5)
+    h64, cn64 = fr.lstm_gates(cc, c, dtype=torch.float64)
+    assert h64.dtype == torch.float64
+    assert float((cn64 - c_next).abs().max()) <= 1e-12 and float((h64 - torch.sigmoid(o) * F.celu(c_next)).abs().max()) <= 1e-12
+
+
+@pytest.mark.parametrize("kind", ["narrow", "saturated"])
+def test_lstm_gates_hard_values_are_the_oracle(kind):
+    cc, c = sc.hard_gate_inputs(kind, 2, 5, 8, 10, seed=400)
+    for got, exp in zip(fr.lstm_gates(cc, c), orc.lstm_gates(cc, c)):
+        assert torch.isfinite(got).all() and torch.equal(got, exp)
+
+
+def test_lstm_gates_known_answer():
+    """A 1x2 plane, one channel, by hand: LN(g = (1, 3)) = (-a, a) with a = 1 / sqrt(1 + 1e-5); i = f = o = 0 make every sigmoid 1/2
+    and c = 0, so z = celu(LN g) / 2 = (expm1(-a), a) / 2, c' = LN(z) and h' = celu(c') / 2."""
+    a = 1.0 / math.sqrt(1.0 + 1e-5)
+    z = torch.tensor([math.expm1(-a), a], dtype=torch.float64) / 2
+    want_c = (z - z.mean()) / torch.sqrt(((z - z.mean()) ** 2).mean() + 1e-5)
+    want_h = 0.5 * torch.where(want_c > 0, want_c, torch.expm1(want_c))
+    cc = torch.tensor([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 3.0]).view(1, 4, 1, 2)
+    h, cn = fr.lstm_gates(cc, torch.zeros(1, 1, 1, 2), dtype=torch.float64)
+    assert float((cn.view(-1) - want_c).abs().max()) <= 1e-14 and float((h.view(-1) - want_h).abs().max()) <= 1e-14
+    assert float(cn.view(-1)[0]) < 0 < float(cn.view(-1)[1])
+
+
+@pytest.mark.parametrize("S", [1, 2, 5, 6, 16])
+def test_lstm_gates_partials_add_in_ascending_order(S):
+    parts, c = _rand(S, 2, 20, 8, 10, seed=30 + S, scale=1.5 / S ** 0.5), _rand(2, 5, 8, 10, seed=31)
+    total = parts[0].clone()
+    for s in range(1, S):
+        total += parts[s]
+    for got, exp in zip(fr.lstm_gates_partials(parts, c), orc.lstm_gates(total, c)):
+        assert torch.equal(got, exp)
+    for got, exp in zip(fr.lstm_gates_partials(parts, c, dtype=torch.float64), fr.lstm_gates(parts.double().sum(0), c, dtype=torch.float64)):
+        assert got.dtype == torch.float64 and float((got - exp).abs().max()) <= 1e-12
+    if S == 1:
+        assert all(torch.equal(a, b) for a, b in zip(fr.lstm_gates_partials(parts, c), fr.lstm_gates(parts[0], c)))
+
+
+@pytest.mark.parametrize("kind", sc.WARP_KINDS)
+@pytest.mark.parametrize("shape", sc.WARP_SHAPES + [sc.WARP_GRID_STRIDE_SHAPE])
+def test_hidden_warp_is_the_oracle_and_grid_sample(shape, kind):
+    """float32: oracle.warp_hidden_state bit for bit, masked and not.  float64: F.grid_sample fed the same normalised grid.  And the
+    case holds its geometry class and the |z| > 0.05 precondition (what tests/test_state_kernels_gpu.py relies on)."""
+    B, C, H, W = shape
+    C = min(C, 3)
+    depth, T, K = sc.warp_case(kind, B, H, W, seed=900 + H * W)
+    src = _rand(B, C, H, W, seed=40)
+    for mask in (False, True):
+        out, ix, iy, z = fr.hidden_warp(src, depth, T, K, mask)
+        assert out.dtype == torch.float32 and ix.dtype == iy.dtype == z.dtype == torch.float64 and tuple(z.shape) == (B, H, W)
+        assert torch.equal(out, orc.warp_hidden_state(src, depth, T, K, zero_invalid=mask))
+    sc.check_warp_case(kind, depth, ix, iy, z, H, W)
+    out64, ix64, iy64, z64 = fr.hidden_warp(src, depth, T, K, False, dtype=torch.float64)
+    assert torch.equal(ix64, ix) and torch.equal(iy64, iy) and torch.equal(z64, z)
+    grid, _ = fr.warp_grid(depth, T, K, torch.float64)
+    aten = F.grid_sample(src.double(), grid, mode="bilinear", padding_mode="zeros", align_corners=True)
+    assert float((out64 - aten).abs().max()) <= 1e-12
+    masked64 = fr.hidden_warp(src, depth, T, K, True, dtype=torch.float64)[0]
+    gone = (depth <= torch.tensor(0.01, dtype=torch.float32)).expand(B, C, H, W)
+    assert float(masked64[gone].abs().max() if gone.any() else 0.0) == 0.0 and torch.equal(masked64[~gone], out64[~gone])
+    if kind != "shift" and kind != "borders":        # 0 and 0.01f are masked, the next float is not
+        zero, edge, above = sc.special_depths()
+        assert bool(gone[(depth == edge).expand_as(gone)].all()) and not bool(gone[(depth == above).expand_as(gone)].any())
+
+
+def test_hidden_warp_shift_known_answer():
+    """A pure shift by (1.5, -0.5) pixels: out(y, x) = the mean of the four source pixels around (x + 1.5, y - 0.5), missing ones 0."""
+    depth, T, K = sc.warp_case("shift", 1, 4, 5, seed=1)
+    src = torch.arange(20.0).view(1, 1, 4, 5)
+    out = fr.hidden_warp(src, depth, T, K, dtype=torch.float64)[0][0, 0]
+    padded = F.pad(src.double()[0, 0], (0, 3, 1, 0))                 # one zero row above, three zero columns to the right
+    want = (padded[0:4, 1:6] + padded[0:4, 2:7] + padded[1:5, 1:6] + padded[1:5, 2:7]) / 4
+    assert float((out - want).abs().max()) <= 1e-5
+
+
+def test_recurrent_fixtures_of_the_reference_run(golden_dir):
+    """tests/golden/hidden_warp.npz and lstm_gates.npz (captured from the reference) within the tolerances tests/test_hip_parity.py
+    uses for the kernels: 5e-6 for the warp, 1e-5 for the gates."""
+    z = np.load(os.path.join(golden_dir, "hidden_warp.npz"))
+    lK = syn.scaled_K(syn.full_K(), 32.0)
+    _, _, h0, c0 = syn.analytic_lstm_inputs()
+    t = lambda k: torch.from_numpy(z[k])      # noqa: E731
+    for depth, T, mask, want in (("depth", "T", False, "warped"), ("depth_masked", "T", True, "warped_masked"), ("depth", "T_far", False, "warped_far")):
+        for dtype in (torch.float32, torch.float64):
+            got = fr.hidden_warp(h0, t(depth), t(T), lK, mask, dtype=dtype)[0]
+            assert float((got.double() - t(want).double()).abs().max()) < 5e-6, (want, dtype)
+    z = np.load(os.path.join(golden_dir, "lstm_gates.npz"))
+    o = np.arange(2048, dtype=np.float64).reshape(-1, 1, 1)
+    yy, xx = np.arange(8, dtype=np.float64).reshape(1, -1, 1), np.arange(10, dtype=np.float64).reshape(1, 1, -1)
+    cc = torch.from_numpy((2.0 * np.sin(0.013 * o + 0.7 * yy + 0.3 * xx) + 0.5 * np.cos(0.05 * o * xx)).astype(np.float32)).unsqueeze(0)
+    for dtype in (torch.float32, torch.float64):
+        h, c = fr.lstm_gates(cc, c0, dtype=dtype)
+        assert float((h.double() - torch.from_numpy(z["h_next"]).double()).abs().max()) < 1e-5
+        assert float((c.double() - torch.from_numpy(z["c_next"]).double()).abs().max()) < 1e-5

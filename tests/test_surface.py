@@ -106,6 +106,43 @@ def test_hot_path_has_no_cpu_fallback():
         LSTMFusion()(torch.randn(1, 512, 8, 10), None, None, eye4, torch.zeros(1, 1, 8, 10), eye3)
 
 
+def test_hidden_warp_refuses_mismatched_batch_and_map_sizes():
+    """The kernel indexes depth, transform and intrinsics by the SOURCE's batch and map size, so a [2,C,H,W] source with a batch-1
+    depth, transform or camera matrix would read past their ends: ``ops.hidden_warp_into`` (a plain function) and
+    ``utils.warp_frame_depth`` raise ValueError for it -- on CPU tensors before the no-CPU error, so nothing is ever launched -- while
+    a well-formed call on CPU tensors still ends in the no-CPU error."""
+    from dvmvs import utils
+    from dvmvs.hip import ops
+    B, C, H, W = 2, 3, 4, 5
+    good = dict(image_src=torch.zeros(B, C, H, W), depth_dst=torch.ones(B, 1, H, W), src_trans_dst=torch.eye(4).repeat(B, 1, 1),
+                camera_matrix=torch.eye(3).repeat(B, 1, 1))
+    wrong = {
+        "depth_dst": [torch.ones(1, 1, H, W), torch.ones(B, 1, H, W + 1), torch.ones(B, 1, H - 1, W), torch.ones(B, 2, H, W), torch.ones(B, H, W)],
+        "src_trans_dst": [torch.eye(4)[None], torch.eye(4).repeat(3, 1, 1), torch.eye(3).repeat(B, 1, 1), torch.eye(4)],
+        "camera_matrix": [torch.eye(3)[None], torch.eye(3).repeat(3, 1, 1), torch.eye(4).repeat(B, 1, 1), torch.eye(3)],
+    }
+    dst = torch.full((B, C, H, W), -7.0)
+    for name, tensors in wrong.items():
+        for t in tensors:
+            args = dict(good, **{name: t})
+            with pytest.raises(ValueError, match=name):
+                ops.hidden_warp_into(*args.values(), True, dst)
+            with pytest.raises(ValueError, match=name):
+                utils.warp_frame_depth(*args.values())
+    for bad_dst in (torch.zeros(1, C, H, W), torch.zeros(B, C + 1, H, W), torch.zeros(B, C, H * W)):
+        with pytest.raises(ValueError, match="dst"):
+            ops.hidden_warp_into(*good.values(), True, bad_dst)
+    with pytest.raises(ValueError, match="image_src"):
+        ops.hidden_warp_into(good["image_src"][0], *list(good.values())[1:], True, dst)
+    with pytest.raises(ValueError, match="depth_dst"):       # a wrong dtype is reported like a wrong shape
+        ops.hidden_warp_into(*dict(good, depth_dst=good["depth_dst"].double()).values(), True, dst)
+    assert bool((dst == -7.0).all())
+    with pytest.raises(RuntimeError, match="MI355X"):
+        ops.hidden_warp_into(*good.values(), True, dst)
+    with pytest.raises(RuntimeError, match="MI355X"):
+        utils.warp_frame_depth(*good.values())
+
+
 def test_op_shape_inference_with_meta_tensors():
     """register_fake implementations (what torch.compile / shape propagation sees)."""
     from dvmvs.hip import ops
