@@ -12,6 +12,7 @@ from dvmvs import implicit as _host
 from dvmvs.hip import neighbours as _neighbours
 from dvmvs.hip.ops._common import check_tensors, launch, ptr
 from dvmvs.hip.ops.reconstruction import nearest_build, nearest_query
+from dvmvs.hip.volume import marching_cubes
 from dvmvs.implicit import DEFAULT_MIN_NEIGHBOURS, DEFAULT_NEIGHBOURS
 
 MAX_POINTS = 1 << 28
@@ -167,7 +168,6 @@ def mesh_points(cloud: Tensor, normals: Tensor, voxel: float, radius: float, nei
         origin, _, dims = _checked(name, _host._grid, bounds[0], voxel, bounds[1])
     grid = nearest_build(points)
     volume, valid = implicit_volume(points, normals, origin, voxel, dims, radius, neighbours, min_neighbours, grid)
-    from dvmvs.tsdf import marching_cubes
     verts_index, faces, _, _ = marching_cubes(volume, 0.0, None, (0.0, 0.0, 0.0), 1.0)
     verts_index, faces, _ = trim_mesh(verts_index, faces, valid)
     verts = verts_index * torch.tensor(float(voxel), dtype=torch.float32, device=device)          # two rounded float32 steps

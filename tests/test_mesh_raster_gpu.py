@@ -231,7 +231,8 @@ def test_visible_mesh_in_chunks(hip_device, monkeypatch):
     from dvmvs import tsdf
     verts, faces, K, P, H, W = R.room_mesh()
     whole = tsdf.visible_mesh(verts, faces, K, P, H, W, min_views=2)[1]
-    monkeypatch.setattr(tsdf, "VISIBLE_MESH_CHUNK", 3)
+    from dvmvs.tsdf import mesh_views
+    monkeypatch.setattr(mesh_views, "VISIBLE_MESH_CHUNK", 3)          # the module that owns it: visible_mesh reads it there
     assert torch.equal(tsdf.visible_mesh(verts, faces, K, P, H, W, min_views=2)[1], whole)
     assert 0 < len(whole) < len(faces)
 
