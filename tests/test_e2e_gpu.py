@@ -532,7 +532,7 @@ def test_lookahead_random_schedules_are_bit_identical(hip_device, seed):
 
 
 def test_planning_a_frame_ahead_is_bit_identical(hip_device):
-    """DepthEngine.plan_ahead: the announced next frame's parameter block (pose algebra, sweep configuration, work list) is evaluated
+    """ParameterBlock.plan_ahead (dvmvs/parameter_block.py): the announced next frame's parameter block (pose algebra, sweep configuration, work list) is evaluated
     on a second host thread during this frame's graph launch.  Same functions on the same inputs: depth equals, bit for bit, an engine
     that evaluates every block inside its own step -- through a tracking loss, a wrong announcement and a missing one."""
     dev = hip_device

@@ -1,4 +1,4 @@
-"""CPU tests of host-side logic of the frame engine that needs no device (dvmvs/engine.py): the queue that turns a step's input copies into one
+"""CPU tests of host-side logic of the frame engine that needs no device (dvmvs/frame_host.py, dvmvs/engine.py): the queue that turns a step's input copies into one
 launch (CopyQueue), the key of a frame's graph (FrameBody.key), the test for "the announced frame arrived" (DepthEngine._prepared_level), the feature
 cache (FeatureCache) and the validation of the fork point.  The copy queue's device entry (dvmvs_copy_batch) is tested on the GPU in
 tests/test_sweep_mfma_gpu.py; here the batching op is replaced by a recorder so that the ORDER and GROUPING of the copies can be checked:
@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from dvmvs import engine as engine_module
+from dvmvs import frame_host
 from dvmvs.engine import CopyQueue, DepthEngine, FeatureCache, FrameBody
 
 
@@ -36,8 +37,7 @@ class _Recorder:
 
 def _open_queue(monkeypatch):
     rec = _Recorder()
-    monkeypatch.setattr(engine_module, "_ops", rec)
-    monkeypatch.setattr(engine_module, "_BATCH_COPIES", True)
+    monkeypatch.setattr(frame_host, "_ops", rec)
     queue = CopyQueue()
     queue.open()
     return queue, rec

@@ -3,7 +3,7 @@
 At N = 8 every rank runs the engine's host path once per frame -- the reference's fp32 pose algebra (~40 small torch operations), the sweep's
 launch plan, the parameter block build, and a graph launch -- and the frame is co-bound by it (0.74 ms of host time against 0.78 ms of device
 time per frame at N = 1).  The GPUs do not share anything; the host cores do.  This test runs the HOST half of ``DepthEngine.step`` (the very
-function the engine calls, ``_evaluate_frame_parameters``, on the keyframe poses of the sample scene, + the mirror copy + a stubbed launch that
+function the engine calls, ``ParameterBlock.evaluate``, on the keyframe poses of the sample scene, + the mirror copy + a stubbed launch that
 sleeps without the interpreter lock, as hipGraphLaunch does) in 1 and in 8 processes at once, one torch thread each as ``bench.py`` configures
 them per rank, and reports the per-step host time.  No device involved: the scaling of the host part is what is measured.
 Reference loop: /root/reference/dvmvs/fusionnet/run-testing.py:151-204 (its pose algebra: utils.py:51-56, :121, convlstm.py:30)."""
@@ -26,12 +26,10 @@ def _host_loop(rank, queue, barrier, core):
     import torch
     torch.set_num_threads(1)
     import synthetic as syn
-    from dvmvs.engine import DepthEngine
-    eng = DepthEngine.__new__(DepthEngine)
-    eng.sequences, eng.height, eng.width, eng.n_depth_levels, eng.min_depth, eng.max_depth = 1, 256, 320, 64, 0.25, 20.0
-    eng.pose_algebra, eng.sweep_work_list, eng.sweep_mfma, eng.lstm = "reference", True, True, object()      # (fusionnet: the two relative poses as well)
-    eng._param_offsets, total = DepthEngine._parameter_layout(1, 256, 320, 64)
-    mirror, staging = torch.zeros(total), torch.zeros(total)
+    from dvmvs.parameter_block import ParameterBlock
+    block = ParameterBlock(sequences=1, height=256, width=320, n_depth_levels=64, min_depth=0.25, max_depth=20.0, pose_algebra="reference",
+                           sweep_work_list=True, sweep_mfma=True, is_fusionnet=True)      # (fusionnet: the two relative poses as well)
+    mirror, staging = block.mirror, torch.zeros(block.total)
     poses = torch.from_numpy(syn.sample_poses()).float()
     lines = syn.keyframe_index_lines(2)
     full_K = syn.full_K()
@@ -39,14 +37,14 @@ def _host_loop(rank, queue, barrier, core):
     no_previous = torch.zeros(1, dtype=torch.bool)
     for k in range(5):      # warm-up: library load, LAPACK, allocator
         r, ms = lines[k]
-        eng._evaluate_frame_parameters(mirror, 2, poses[r:r + 1], [poses[m:m + 1] for m in ms], full_K, previous, no_previous, 0, True, None)
+        block.evaluate(mirror, 2, poses[r:r + 1], [poses[m:m + 1] for m in ms], full_K, previous, no_previous, 0, True, None)
     barrier.wait()
     t0 = time.perf_counter()
     busy = 0.0
     for k in range(STEPS):
         r, ms = lines[(5 + k + 31 * rank) % len(lines)]
         t1 = time.perf_counter()
-        committed, variant, _ = eng._evaluate_frame_parameters(mirror, 2, poses[r:r + 1], [poses[m:m + 1] for m in ms], full_K, previous, no_previous, k & 1, True, None)
+        committed, variant, _ = block.evaluate(mirror, 2, poses[r:r + 1], [poses[m:m + 1] for m in ms], full_K, previous, no_previous, k & 1, True, None)
         staging.copy_(mirror)
         busy += time.perf_counter() - t1
         time.sleep(LAUNCH_STUB_SECONDS)      # the graph launch: the interpreter lock is released, the core is not needed

@@ -43,7 +43,7 @@ def main():
         cur, alt = d["sets"][0], d["sets"][1]
         alt["full_in"][:, 33:36].copy_(syn.e2e_image(12).to(dev))
         # the other buffer set gets a copy of this frame's sweep parameters and measurement features (timing only)
-        params, off = engine._static["params"], engine._param_offsets
+        params, off = engine._block.params, engine._block.offsets
         for name in ("Hm", "kt", "sweep_items"):
             (o0, n), (o1, _) = off[name], off[name + "1"]
             params[o1:o1 + n].copy_(params[o0:o0 + n])
@@ -68,9 +68,9 @@ def main():
                 main_stream.wait_stream(side)
             return body
 
-        feat = lambda b: (lambda: engine._reference_features_direct(b))
-        enc = lambda b: (lambda: engine._sweep_encoder_direct(b, 2, 2))
-        dec = lambda b: (lambda: engine._lstm_decoder_direct(b, True))
+        feat = lambda b: (lambda: engine._frame._reference_features_direct(b))
+        enc = lambda b: (lambda: engine._frame._sweep_encoder_direct(b, 2, 2))
+        dec = lambda b: (lambda: engine._frame._lstm_decoder_direct(b, True))
         both = lambda f, g: (lambda: (f(), g()))
         rows = [
             ("A  feature extraction (MnasNet + FPN)", feat(alt)),
