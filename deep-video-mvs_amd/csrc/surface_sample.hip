@@ -3,6 +3,8 @@
 //   dvmvs_surface_sample_count / _emit     : verts fp32 [V,3], faces int32 [F,3], density, seed -> points fp32 [N,3] (face int32 [N])
 //   dvmvs_voxel_keys                       : points fp32 [N,3], 1 / voxel -> key int64 [N]
 //   dvmvs_voxel_downsample_count / _emit   : the keys and indices after a stable sort -> points fp32 [M,3] (count int32 [M])
+//   dvmvs_voxel_downsample_runs            : host only: where the count step left the run starts and the points in sorted order (for
+//                                            csrc/mesh_simplify.hip, whose clusters are these voxels)
 //
 // Everything that decides a result is an integer (areas quantised to 2^-32 m^2, their prefix sums, keys, ranks) or a float operation whose
 // operands and order the definition fixes: no float atomics, no float value crosses threads, nothing is contracted into an FMA
@@ -462,4 +464,16 @@ extern "C" int dvmvs_voxel_downsample_emit(long long N, long long M, const void*
                      static_cast<hipStream_t>(stream), reinterpret_cast<const float*>(ws + l.sorted_off), N,
                      reinterpret_cast<const int*>(ws + l.starts_off), M, out, count);
   return launch_status();
+}
+
+extern "C" int dvmvs_voxel_downsample_runs(long long N, const void* workspace, const int** starts, const float** sorted_points) {
+  using namespace dvmvs;
+  if (!workspace || !starts || !sorted_points || N < 1) return DVMVS_EINVAL;
+  if (misaligned(workspace, 16)) return DVMVS_EINVAL;
+  if (N > kSsMaxPoints) return DVMVS_EUNSUPPORTED;
+  const VxLayout l = vx_layout(N);
+  const char* ws = static_cast<const char*>(workspace);
+  *starts = reinterpret_cast<const int*>(ws + l.starts_off);
+  *sorted_points = reinterpret_cast<const float*>(ws + l.sorted_off);
+  return 0;
 }

@@ -20,7 +20,8 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, evaluate_3d_align_plane=False,
         evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, point_mesh_voxel=None, point_mesh_radius=None,
-        point_mesh_neighbours=32, point_mesh_min_neighbours=3, groundtruth_transform=None, point_normals_neighbours=None,
+        point_mesh_neighbours=32, point_mesh_min_neighbours=3, simplify_mesh_voxel=None, simplify_mesh_average=False,
+        groundtruth_transform=None, point_normals_neighbours=None,
         point_normals_max_distance=None, clean_points_neighbours=None, clean_points_ratio=2.0, clean_points_max_distance=None,
         clean_points_radius=None, clean_points_min_neighbours=None, clean_mesh_area=None, clean_mesh_faces=None, clean_mesh_largest=False):
     """The reconstruction script's main program (run-tsdf-reconstruction.py:477-636): fuses a scene's saved keyframe depth
@@ -89,6 +90,15 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     side is never cleaned, and ``render_keyframes`` ray-casts the VOLUME, which cleaning a mesh does not touch: its depth maps are what
     they are without these flags (under the ``+clean`` name).  Without these flags every file is what it is without them, byte for byte.
 
+    ``simplify_mesh_voxel`` (metres) with ``simplify_mesh_average``: the system's mesh, after ``clean_mesh_*`` where those are given, goes
+    through ``dvmvs.simplify.simplify_mesh`` on the device: one vertex per occupied cell of that edge, placed where the summed plane
+    quadrics of the faces around it are smallest, so that edges and corners stay sharp; with ``simplify_mesh_average`` at the cell mean
+    (``SimplifySettings``).  The system's files are then written under ``<system_name>+simple`` (after ``+consistent`` and ``+clean``), its
+    ``.ply`` files, the progressive ones included, are the simplified meshes, and ``evaluate_3d`` scores the simplified surface;
+    ``_errors3d.npz`` then also holds ``simplify_voxel``, ``simplify_average`` and ``simplify_faces`` int64 [2], the faces after and
+    before the simplification.  The ground-truth side is never simplified, ``render_keyframes`` ray-casts the volume, and the mesh of
+    ``point_mesh_voxel`` is not simplified.  Without these flags every file is what it is without them, byte for byte.
+
     ``clean_points_neighbours`` (a count, 1 .. 32) with ``clean_points_ratio`` and ``clean_points_max_distance`` (metres),
     ``clean_points_radius`` (metres) with ``clean_points_min_neighbours`` (each needs ``save_point_cloud``): the fused point cloud goes
     through ``dvmvs.outliers.filter_outliers`` on the device before it comes down (``OutlierFilter``).  The first removes the points whose
@@ -141,7 +151,7 @@ class Settings:
     dataset_name: str
     scene_name: str
     system_name: str                   # as given: it names the prediction file and the keyframe index
-    output_name: str                   # with "+consistent" and "+clean" where those apply: it names every file that is written
+    output_name: str                   # with "+consistent", "+clean" and "+simple" where those apply: it names every file that is written
     voxel_size: float
     max_depth: float
     use_groundtruth_to_anchor: bool
@@ -165,6 +175,7 @@ class Settings:
     visible_min_views: Optional[int]   # evaluate_3d_visible: the views that must see a ground-truth face; None without it
     align: dict                        # _aligned_score's keywords: align_distance, align_scale, align_plane (None or score_against's keywords)
     clean: object                      # ComponentFilter of clean_mesh_*, or None
+    simplify: object                   # SimplifySettings of simplify_mesh_*, or None
     clean_points: object               # OutlierFilter of clean_points_*, or None
     point_normals: Optional[tuple]     # (neighbours, max_distance) of point_normals_*, or None
     point_mesh: Optional[tuple]        # (voxel, radius, neighbours, min_neighbours) of point_mesh_*, or None
@@ -174,6 +185,7 @@ def _settings(arguments):
     """The ``Settings`` of ``run``'s arguments (a dict by name).  Every refusal that needs no file is made here, and names its flag."""
     a = SimpleNamespace(**arguments)
     clean = _clean_filter(a.clean_mesh_area, a.clean_mesh_faces, a.clean_mesh_largest)
+    simplify = _simplify_settings(a.simplify_mesh_voxel, a.simplify_mesh_average)
     clean_points = _clean_points_filter(a.save_point_cloud, a.clean_points_neighbours, a.clean_points_ratio, a.clean_points_max_distance,
                                         a.clean_points_radius, a.clean_points_min_neighbours)
     point_normals = _point_normals_settings(a.save_point_cloud, a.point_normals_neighbours, a.point_normals_max_distance)
@@ -209,7 +221,8 @@ def _settings(arguments):
         raise ValueError("groundtruth_transform moves the mesh of groundtruth_mesh: it needs groundtruth_mesh")
     if a.evaluate_3d_align is not None and not float(a.evaluate_3d_align) > 0.0:
         raise ValueError(f"evaluate_3d_align must be a positive distance, got {a.evaluate_3d_align}")
-    output_name = a.system_name + ("+consistent" if a.filter_consistency else "") + ("+clean" if clean is not None else "")
+    output_name = a.system_name + ("+consistent" if a.filter_consistency else "") + ("+clean" if clean is not None else "") + (
+        "+simple" if simplify is not None else "")
     return Settings(
         reconstruction_folder=a.reconstruction_folder, prediction_folder=a.prediction_folder, data_folder=a.data_folder,
         dataset_name=a.dataset_name, scene_name=a.scene_name, system_name=a.system_name, output_name=output_name, voxel_size=a.voxel_size,
@@ -223,7 +236,7 @@ def _settings(arguments):
         fuse_groundtruth_3d=a.evaluate_3d and a.groundtruth_mesh is None,
         visible_min_views=int(a.evaluate_3d_min_views) if a.evaluate_3d_visible else None,
         align={"align_distance": a.evaluate_3d_align, "align_scale": a.evaluate_3d_align_scale, "align_plane": align_plane},
-        clean=clean, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh)
+        clean=clean, simplify=simplify, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh)
 
 
 def _number(value):
@@ -248,6 +261,20 @@ def _clean_filter(clean_mesh_area, clean_mesh_faces, clean_mesh_largest):
     except ValueError as e:
         raise ValueError(f"clean_mesh_area / clean_mesh_faces: {e}") from None
     return clean
+
+
+def _simplify_settings(simplify_mesh_voxel, simplify_mesh_average):
+    """The ``SimplifySettings`` of ``run``'s two settings, None when no voxel is given; each refusal names its flag."""
+    if not isinstance(simplify_mesh_average, bool):
+        raise ValueError(f"simplify_mesh_average must be a bool, got {simplify_mesh_average!r}")
+    if simplify_mesh_voxel is None:
+        if simplify_mesh_average:
+            raise ValueError("simplify_mesh_average says how simplify_mesh_voxel places a cell's vertex: it needs simplify_mesh_voxel")
+        return None
+    if not _number(simplify_mesh_voxel) or not 0.0 < float(simplify_mesh_voxel) < np.inf:
+        raise ValueError(f"simplify_mesh_voxel must be a positive, finite cell edge in metres, got {simplify_mesh_voxel!r}")
+    from dvmvs.simplify import SimplifySettings
+    return SimplifySettings(float(simplify_mesh_voxel), "average" if simplify_mesh_average else "quadric")
 
 
 def _clean_points_filter(save_point_cloud, neighbours, ratio, max_distance, radius, min_neighbours):
@@ -518,7 +545,7 @@ def _fuse_system(settings, scene, images, predictions, volume_bounds):
     volume = TSDFVolume(volume_bounds, voxel_size=settings.voxel_size, device=settings.device)
     mesh_name = _mesh_name(settings, settings.output_name)
     TSDFFusion.integrate(volume, images, predictions, scene.keyframe_poses, scene.scaled_K, mesh_name, settings.save_progressive,
-                         clean=settings.clean)
+                         simplify=settings.simplify, clean=settings.clean)
     return volume, mesh_name
 
 
@@ -554,6 +581,17 @@ def _clean_entries(volume, clean):
             "clean_faces": np.array([kept, total], dtype=np.int64)}
 
 
+def _simplify_entries(volume, clean, simplify):
+    """What ``_errors3d.npz`` gains with a ``SimplifySettings``: its settings and the faces of the system's mesh after and before it."""
+    if simplify is None:
+        return {}
+    kept = int(volume.mesh_tensors(simplify=simplify, clean=clean)[1].shape[0])
+    total = int(volume.mesh_tensors(clean=clean)[1].shape[0])
+    print("Mesh simplified with cells of {} m ({}): {} of {} faces left".format(simplify.voxel, simplify.contraction, kept, total))
+    return {"simplify_voxel": np.float64(simplify.voxel), "simplify_average": np.bool_(simplify.contraction == "average"),
+            "simplify_faces": np.array([kept, total], dtype=np.int64)}
+
+
 def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
     """Scores the fused surface against the ground truth on the device (``groundtruth``: its vertices; with ``protocol_3d`` a mesh, device
     verts and faces, with face sampling and / or voxel down-sampling of both sides, and with ``visible_min_views`` only the part of the mesh
@@ -565,6 +603,8 @@ def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
         score.update(sample_density=density, voxel=voxel)
     if clean is not None:
         score["clean"] = clean
+    if settings.simplify is not None:
+        score["simplify"] = settings.simplify
     if settings.visible_min_views is not None:
         if not scene.keyframe_poses:
             raise ValueError("evaluate_3d_visible: the scene has no keyframe to take the visibility from")
@@ -576,7 +616,7 @@ def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
         print("Ground truth restricted to what {} keyframes saw: {} of {} faces".format(len(scene.keyframe_poses), kept[0][0], kept[0][1]))
         extra = {"visible_faces": np.int64(kept[0][0]), "total_faces": np.int64(kept[0][1])}
     if settings.protocol_3d:
-        sizes = (int(volume.vertices(clean=clean).shape[0]), int(groundtruth[0].shape[0]))
+        sizes = (int(volume.vertices(simplify=settings.simplify, clean=clean).shape[0]), int(groundtruth[0].shape[0]))
         print("3-D metrics at {} m over {} predicted and {} ground-truth points (density {}, voxel {}; {} and {} vertices): {}".format(
             threshold, points[0], points[1], density, voxel, sizes[0], sizes[1], metrics))
         extra = {"sample_density": np.float64(np.nan if density is None else density), "voxel": np.float64(np.nan if voxel is None else voxel),
@@ -585,7 +625,8 @@ def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
         sizes = points
         print("3-D metrics at {} m over {} predicted and {} ground-truth vertices: {}".format(threshold, sizes[0], sizes[1], metrics))
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS), counts=np.array(sizes, dtype=np.int64),
-                        threshold=np.float32(threshold), **extra, **aligned, **_clean_entries(volume, clean))
+                        threshold=np.float32(threshold), **extra, **aligned, **_clean_entries(volume, clean),
+                        **_simplify_entries(volume, clean, settings.simplify))
 
 
 def _render_keyframes(settings, scene, volume):
@@ -704,6 +745,11 @@ def build_parser():
                         help="with --point_mesh_voxel: at most this many nearest points within the radius shape a node (1 .. 32)")
     parser.add_argument("--point_mesh_min_neighbours", default=3, type=int,
                         help="with --point_mesh_voxel: a node with fewer points with a normal within the radius carries no surface")
+    parser.add_argument("--simplify_mesh_voxel", default=None, type=float,
+                        help="simplify the system's mesh on the device (after --clean_mesh_*): one vertex per occupied cell of this edge, "
+                             "metres, placed by the quadrics of the faces around it; files are written under <system>+simple")
+    parser.add_argument("--simplify_mesh_average", action="store_true",
+                        help="with --simplify_mesh_voxel: a cell's vertex is the mean of its vertices instead of the quadric minimiser")
     parser.add_argument("--clean_points_neighbours", default=None, type=int,
                         help="with --save_point_cloud: statistical outlier removal of the fused cloud on the device, over this many nearest "
                              "neighbours (1 .. 32); the result is written additionally as <mesh name>_pointcloud_clean.ply")

@@ -12,6 +12,15 @@ def fold_color(color_im):
     return np.floor(c[..., 2] * np.float32(65536.0) + c[..., 1] * np.float32(256.0) + c[..., 0]).astype(np.float32)
 
 
+def mesh_stages(simplify, clean):
+    """``(simplify, clean)`` of a method that takes both.  ``simplify`` stands before ``clean`` in the signatures, where ``clean`` alone
+    stood before: a ``ComponentFilter`` that arrives in its place, given by position, is the ``clean`` it always was."""
+    from dvmvs.components import ComponentFilter
+    if isinstance(simplify, ComponentFilter) and clean is None:
+        return None, simplify
+    return simplify, clean
+
+
 class TSDFVolume:
     """Voxel volume over ``vol_bnds`` ([[x0, x1], [y0, y1], [z0, z1]] in metres) with ``voxel_size`` edges.  tsdf starts at 1,
     weight and colour at 0; truncation = 5 voxels, as in the reference."""
@@ -134,11 +143,24 @@ class TSDFVolume:
             mesh = filter_components_device(mesh[0], mesh[1], clean, mesh[2], mesh[3])
         return mesh
 
-    def get_mesh(self, clean=None):
+    def _surface(self, color, simplify, clean):
+        """``_extract``, and with ``simplify`` (a ``dvmvs.simplify.SimplifySettings``) what it leaves through ``simplify_mesh`` on the
+        device; without it, ``_extract`` and nothing else."""
+        simplify, clean = mesh_stages(simplify, clean)
+        mesh = self._extract(color, clean)
+        if simplify is not None:
+            from dvmvs.simplify import simplify_mesh_device, simplify_settings
+            simplify_settings(simplify)
+            mesh = simplify_mesh_device(mesh[0], mesh[1], simplify, mesh[2], mesh[3])
+        return mesh
+
+    def get_mesh(self, simplify=None, clean=None):
         """(verts [V,3] float32 in world units, faces [F,3] int32, normals [V,3] float32, colours [V,3] uint8 RGB) of the zero
         iso-surface, as numpy arrays (run-tsdf-reconstruction.py:334-351); extracted on the device by ``marching_cubes``.  ``clean``: a
-        ``dvmvs.components.ComponentFilter``; the mesh then goes through ``filter_components`` on the device before it is downloaded."""
-        verts, faces, norms, colors = self._extract(True, clean)
+        ``dvmvs.components.ComponentFilter``; the mesh then goes through ``filter_components`` on the device before it is downloaded.
+        ``simplify``: a ``dvmvs.simplify.SimplifySettings``; the mesh, cleaned first where ``clean`` is given, then goes through
+        ``simplify_mesh`` on the device: one vertex per occupied cell of ``simplify.voxel`` metres, normals and colours merged alongside."""
+        verts, faces, norms, colors = self._surface(True, simplify, clean)
         return verts.cpu().numpy(), faces.cpu().numpy(), norms.cpu().numpy(), colors.cpu().numpy()
 
     def get_point_cloud(self):
@@ -146,29 +168,31 @@ class TSDFVolume:
         verts, _, _, colors = self.get_mesh()
         return np.hstack([verts, colors])
 
-    def vertices(self, clean=None):
+    def vertices(self, simplify=None, clean=None):
         """The vertices of the zero iso-surface (``get_mesh()[0]``) as a float32 [V,3] DEVICE tensor: nothing but ``marching_cubes``'
-        two counts is read by the host (with ``clean``, as ``get_mesh`` takes it, also ``filter_components``' counts)."""
-        return self._extract(False, clean)[0]
+        two counts is read by the host (with ``clean``, as ``get_mesh`` takes it, also ``filter_components``' counts; with ``simplify``, as
+        ``get_mesh`` takes it, also ``simplify_mesh``'s)."""
+        return self._surface(False, simplify, clean)[0]
 
-    def mesh_tensors(self, clean=None):
+    def mesh_tensors(self, simplify=None, clean=None):
         """``(verts float32 [V,3], faces int32 [F,3])`` of the zero iso-surface as DEVICE tensors, as ``marching_cubes`` leaves them (with
-        ``clean``, as ``get_mesh`` takes it: as ``filter_components`` leaves them)."""
-        return self._extract(False, clean)[:2]
+        ``clean``, as ``get_mesh`` takes it: as ``filter_components`` leaves them; with ``simplify``, as ``get_mesh`` takes it: as
+        ``simplify_mesh`` leaves them)."""
+        return self._surface(False, simplify, clean)[:2]
 
-    def surface_points(self, sample_density=None, voxel=None, clean=None):
+    def surface_points(self, sample_density=None, voxel=None, simplify=None, clean=None):
         """The point set the 3-D metrics take from this volume's surface, as a float32 [N,3] DEVICE tensor: the vertices of the zero
         iso-surface; with ``sample_density`` (points per square metre) instead ``dvmvs.hip.ops.surface_sample`` of its faces; with ``voxel``
         (metres) then ``dvmvs.hip.ops.voxel_downsample`` of that (``dvmvs.errors.prepare_points`` is the host definition of both).  The
         vertices and faces stay on the device; each step reads its output's size once.  ``clean``: as ``get_mesh`` takes it; the points are
-        then those of the cleaned mesh."""
+        then those of the cleaned mesh; ``simplify``: as ``get_mesh`` takes it; the points are then those of the simplified mesh."""
         from dvmvs.errors import prepare_points_device
-        verts, faces = self.mesh_tensors(clean)
+        verts, faces = self.mesh_tensors(simplify=simplify, clean=clean)
         return prepare_points_device(verts, faces, sample_density, voxel)
 
     def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None, clean=None,
-                      align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, align_distance=None, align_scale=False,
-                      return_transform=False):
+                      simplify=None, align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, align_distance=None,
+                      align_scale=False, return_transform=False):
         """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
         DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
         ``dvmvs.errors.compute_reconstruction_errors_device`` without a download.  ``reference``: another ``TSDFVolume``, [M,3] points as a
@@ -193,6 +217,10 @@ class TSDFVolume:
         ``filter_components`` on the device before its vertices are taken or its faces sampled, so that floaters do not count against
         accuracy and precision; the reference is never cleaned (a ``TSDFVolume`` reference included).
 
+        ``simplify``: a ``dvmvs.simplify.SimplifySettings``.  The PREDICTION's mesh, after ``clean``, goes through ``simplify_mesh`` on the
+        device before its vertices are taken or its faces sampled: the score is that of the simplified surface.  The reference is never
+        simplified.
+
         ``align_distance`` (metres): before it is scored, the prediction's point set is registered to the reference's by trimmed ICP
         with that inlier distance and moved by the result (``dvmvs.hip.registration.icp``; ``dvmvs.errors.register_points`` is the host
         definition), so that a residual pose offset does not decide the score; ``align_scale`` lets the registration also find a scale.
@@ -207,4 +235,4 @@ class TSDFVolume:
         from dvmvs.tsdf.scoring import score_volume      # (scoring sits above this module: it needs TSDFVolume to tell a volume reference)
         return score_volume(self, reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
                             return_transform, clean=clean, align_plane=align_plane, align_normal_neighbours=align_normal_neighbours,
-                            align_normal_distance=align_normal_distance)[0]
+                            align_normal_distance=align_normal_distance, simplify=simplify)[0]

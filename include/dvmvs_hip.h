@@ -73,7 +73,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_icp_plane_* (registering a point cloud to another with normals by point-to-plane ICP); no earlier
  * signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_implicit_* (the implicit moving-least-squares signed distance of an oriented point cloud on a voxel grid,
- * and the trimming of the mesh that marching cubes makes of it); no earlier signature changed, the number stays 11 by the same rule. */
+ * and the trimming of the mesh that marching cubes makes of it); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_mesh_simplify_* and dvmvs_voxel_downsample_runs (simplifying a triangle mesh by vertex clustering with
+ * quadric error representatives); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -1068,6 +1070,62 @@ int dvmvs_mesh_filter_emit(const float* verts, const int* faces, const float* no
                            long long min_area_units, long long min_faces, int keep_largest, void* workspace, size_t workspace_bytes,
                            long long V_out, long long F_out, float* verts_out, int* faces_out, float* normals_out, unsigned char* colors_out,
                            int* vertex_index, int* face_index, dvmvs_stream_t stream);
+
+/*
+ * Simplifying a triangle mesh by vertex clustering with quadric error representatives (ABI 11, later addition; csrc/mesh_simplify.hip).
+ * The reference project has nothing for this: the definition is this project's own (dvmvs/simplify.py is its host form and states every
+ * step; Lindstrom 2000 is the method, Open3D's simplify_vertex_clustering the usual tool).
+ *   verts [V,3] fp32, faces [F,3] int32 (normals [V,3] fp32, colors [V,3] uint8), contiguous, 4-byte aligned; V in [1, 2^28], F in [0, 2^28].
+ * Arithmetic: fp64 from the fp32 inputs with +, -, *, / and sqrt only, every operation correctly rounded, nothing contracted.
+ *   1. The clusters are the voxels of dvmvs_voxel_keys(verts, V, fp32(1 / voxel)) in ascending key order, the cluster mean m_c is
+ *      dvmvs_voxel_downsample_emit's point (fp64 sum in ascending vertex index, one division, one rounding).
+ *   2. The quadric of cluster c: over its incidences (f, j), face f valid (three indices in [0, V)) and corner j in c, in ascending
+ *      3 f + j: o = fp64(m_c), p_k = fp64(verts[faces[f][k]]) - o, e1 = p_1 - p_0, e2 = p_2 - p_0, n = (e1y e2z - e1z e2y, e1z e2x -
+ *      e1x e2z, e1x e2y - e1y e2x), d = -((nx p0x + ny p0y) + nz p0z); A_cd += n_c n_d (the upper triangle), b_c += d n_c, from 0.0.
+ *   3. With average = 0: the cyclic Jacobi of dvmvs_point_normals_fwd on A (pairs (0,1), (0,2), (1,2), a zero A_pq skipped, at most 16
+ *      sweeps, stop before a sweep when the three off-diagonals are exactly zero) -> l_0..2 and the columns v_0..2; l_max = l_0, replaced by
+ *      l_1 when l_1 > l_max, then by l_2 likewise; column i is kept when l_i > 1e-3 l_max; x = (0, 0, 0), and per kept column in column
+ *      order x_k += (-(((v_0i b_0 + v_1i b_1) + v_2i b_2) / l_i)) v_ki.  When l_max > 0 and |x_k| <= voxel for every k (false for a NaN)
+ *      the cluster's vertex is fp32(o + x), otherwise m_c.  With average = 1 it is m_c.  `voxel` is fp64(fp32(the cell edge)).
+ *   4. normals': the fp64 sum of the members' normals in ascending vertex index, each component divided by len = sqrt((xx + yy) + zz),
+ *      rounded to fp32; zeros unless 0 < len < inf.  colors': per channel rint(fp64(sum) / n), halves to even.
+ *   5. A face is kept when it is valid, its three clusters differ, and no face of smaller index has the same clusters up to rotation.
+ *   6. The clusters that kept faces use keep their order and are renumbered; the faces are re-indexed and keep their order.
+ * Call sequence for one mesh, every call on one stream, `voxel_workspace` the block of the voxel entries and `workspace` this block's:
+ *   dvmvs_voxel_keys(verts, V, ...) -> a stable sort of the keys (sorted_keys, sorted_index int64 [V]) -> dvmvs_voxel_downsample_count
+ *   (-> voxel_counts int64 [2] on the device) -> dvmvs_mesh_simplify_keys (-> incidence_keys int32 [3F]: the cluster of corner j of
+ *   face f at 3 f + j, INT_MAX for an invalid face; third int32 [F] and pair int64 [F]: of the rotation of the face's clusters that
+ *   puts the smallest first, (x, y, z), z and (x << 28) | y; INT_MAX and INT64_MAX for a face that step 5 drops for its own corners) ->
+ *   stable sorts of incidence_keys (incidence_sorted, incidence_order int64 [3F]) and of third (third_order int64 [F]) ->
+ *   dvmvs_mesh_simplify_pair_keys (out[s] = pair[third_order[s]]) -> a stable sort of out (pair_sorted, pair_order int64 [F]) ->
+ *   dvmvs_mesh_simplify_count -> counts [3] int64 = {V', F', status}: status 1 when dvmvs_voxel_keys found a cell index of 2^21 or
+ *   more or a coordinate that is not finite (V' = F' = 0 then) -> dvmvs_mesh_simplify_emit with V_out = V', F_out = F':
+ *   verts_out [V',3], faces_out [F',3], normals_out / colors_out (each NULL when the count call had no such input), vertex_cluster [V]
+ *   int32 (the output vertex of every input vertex, -1 where its cluster kept no face) and face_index [F'] int32 (the old index of
+ *   every output face); each of the last two may be NULL.
+ * One thread owns a cluster and walks its members and its incidences serially; no float atomics, no float value crosses threads: the
+ * results are bit-identical run to run.  No index read from memory becomes an address before it is checked against its array's size.
+ * dvmvs_mesh_simplify_workspace_bytes: host only; 0 for V or F outside [0, 2^28].  The block is 16-byte aligned.
+ * dvmvs_voxel_downsample_runs (csrc/surface_sample.hip; host only, enqueues nothing): where dvmvs_voxel_downsample_count left, in its
+ * workspace for N points, the first sorted slot of every voxel (starts int32 [M]) and the points in sorted order (fp32 [N,3]).
+ * Every entry returns DVMVS_EINVAL for a null or misaligned pointer that a non-empty side needs, V < 1, F < 0, a voxel that is not positive
+ * and finite, average not 0 / 1, V_out or F_out outside [0, V] / [0, F], a workspace that is too small; DVMVS_EUNSUPPORTED for V or F
+ * above 2^28.  Nothing is enqueued in either case.
+ */
+size_t dvmvs_mesh_simplify_workspace_bytes(long long V, long long F);
+int dvmvs_voxel_downsample_runs(long long N, const void* workspace, const int** starts, const float** sorted_points);
+int dvmvs_mesh_simplify_keys(const int* faces, long long V, long long F, const long long* sorted_index, const void* voxel_workspace,
+                             const long long* voxel_counts, void* workspace, size_t workspace_bytes, int* incidence_keys, int* third,
+                             long long* pair, dvmvs_stream_t stream);
+int dvmvs_mesh_simplify_pair_keys(const long long* pair, const long long* third_order, long long F, long long* out, dvmvs_stream_t stream);
+int dvmvs_mesh_simplify_count(const float* verts, const float* normals, const unsigned char* colors, long long V, const int* faces,
+                              long long F, double voxel, int average, const long long* sorted_index, const void* voxel_workspace,
+                              const long long* voxel_counts, const int* incidence_sorted, const long long* incidence_order,
+                              const int* third, const long long* third_order, const long long* pair_sorted, const long long* pair_order,
+                              void* workspace, size_t workspace_bytes, long long* counts, dvmvs_stream_t stream);
+int dvmvs_mesh_simplify_emit(long long V, long long F, void* workspace, size_t workspace_bytes, long long V_out, long long F_out,
+                             float* verts_out, int* faces_out, float* normals_out, unsigned char* colors_out, int* vertex_cluster,
+                             int* face_index, dvmvs_stream_t stream);
 
 /*
  * The k nearest neighbours of points, neighbours within a radius, and statistical outlier scores (ABI 11, later addition;
