@@ -180,6 +180,14 @@ SIGNATURES = {
                                   + [ctypes.c_size_t, _c_fp, _c_stream]),
     "dvmvs_mesh_simplify_emit": (_c_int, [ctypes.c_longlong, ctypes.c_longlong, _c_fp, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_longlong]
                                  + [_c_fp] * 6 + [_c_stream]),
+    "dvmvs_mesh_smooth_workspace_bytes": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_longlong]),
+    "dvmvs_mesh_smooth_keys": (_c_int, [_c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_mesh_smooth_rows": (_c_int, [_c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_fp, ctypes.c_size_t, _c_stream]),
+    "dvmvs_mesh_smooth_rows_export": (_c_int, [ctypes.c_longlong, ctypes.c_longlong, _c_fp, ctypes.c_size_t, _c_fp, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_mesh_smooth_steps": (_c_int, [_c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_dbl, _c_dbl, _c_int, _c_int, _c_fp,
+                                         ctypes.c_size_t, _c_fp, _c_stream]),
+    "dvmvs_mesh_smooth_normals": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_size_t,
+                                           _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -221,6 +229,9 @@ ADDED_WITHIN_ABI_IMPLICIT = ("dvmvs_implicit_band_fwd", "dvmvs_implicit_nodes_fw
 # ... and the sixteenth (simplifying a triangle mesh by vertex clustering with quadric error representatives)
 ADDED_WITHIN_ABI_MESH_SIMPLIFY = ("dvmvs_mesh_simplify_workspace_bytes", "dvmvs_voxel_downsample_runs", "dvmvs_mesh_simplify_keys",
                                   "dvmvs_mesh_simplify_pair_keys", "dvmvs_mesh_simplify_count", "dvmvs_mesh_simplify_emit")
+# ... and the seventeenth (smoothing a triangle mesh by the Laplacian and Taubin filters; vertex normals from the faces)
+ADDED_WITHIN_ABI_MESH_SMOOTH = ("dvmvs_mesh_smooth_workspace_bytes", "dvmvs_mesh_smooth_keys", "dvmvs_mesh_smooth_rows",
+                                "dvmvs_mesh_smooth_rows_export", "dvmvs_mesh_smooth_steps", "dvmvs_mesh_smooth_normals")
 
 _lib = None
 _lock = threading.Lock()
@@ -243,7 +254,7 @@ def lib():
                  + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER
                  + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE + ADDED_WITHIN_ABI_MESH_COMPONENTS
                  + ADDED_WITHIN_ABI_POINT_NEIGHBOURS + ADDED_WITHIN_ABI_POINT_NORMALS + ADDED_WITHIN_ABI_REGISTRATION_PLANE
-                 + ADDED_WITHIN_ABI_IMPLICIT + ADDED_WITHIN_ABI_MESH_SIMPLIFY)
+                 + ADDED_WITHIN_ABI_IMPLICIT + ADDED_WITHIN_ABI_MESH_SIMPLIFY + ADDED_WITHIN_ABI_MESH_SMOOTH)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

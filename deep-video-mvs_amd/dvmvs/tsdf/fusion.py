@@ -66,13 +66,13 @@ class TSDFFusion:
     pcwrite_normals = staticmethod(ply.pcwrite_normals)
 
     @staticmethod
-    def integrate(tsdf_volume, images, depths, poses, K, mesh_name, save_progressive, simplify=None, clean=None):
+    def integrate(tsdf_volume, images, depths, poses, K, mesh_name, save_progressive, simplify=None, smooth=None, clean=None):
         """Fuses every (image, depth, pose) with weight 1 and writes ``<mesh_name>_complete.ply`` (with ``save_progressive``,
         also ``<mesh_name>_frame_<i>.ply`` after each frame), like the reconstruction script (:442-462).  ``clean`` (a
         ``dvmvs.components.ComponentFilter``) and ``simplify`` (a ``dvmvs.simplify.SimplifySettings``) are handed to every ``get_mesh`` whose mesh is written, the progressive
-        ones included."""
+        ones included; so is ``smooth`` (a ``dvmvs.smooth.SmoothSettings``)."""
         from dvmvs.tsdf.volume import mesh_stages
-        simplify, clean = mesh_stages(simplify, clean)
+        simplify, smooth, clean = mesh_stages(simplify, smooth, clean)
         n = len(images)
         start = time.time()
         for i in range(n):
@@ -80,11 +80,11 @@ class TSDFFusion:
             tsdf_volume.integrate(images[i], depths[i], K, poses[i], obs_weight=1.0)
             if save_progressive:
                 print("Saving for progressive visuals...")
-                TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *tsdf_volume.get_mesh(clean=clean, simplify=simplify))
+                TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *tsdf_volume.get_mesh(clean=clean, smooth=smooth, simplify=simplify))
         torch.cuda.synchronize(tsdf_volume.device)
         print("Average FPS: {:.2f}".format(n / max(time.time() - start, 1e-9)))
         print("Saving mesh to", mesh_name)
-        TSDFFusion.meshwrite(mesh_name + "_complete.ply", *tsdf_volume.get_mesh(clean=clean, simplify=simplify))
+        TSDFFusion.meshwrite(mesh_name + "_complete.ply", *tsdf_volume.get_mesh(clean=clean, smooth=smooth, simplify=simplify))
 
 
 class LiveFusion:

@@ -21,6 +21,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, evaluate_3d_align_plane=False,
         evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, point_mesh_voxel=None, point_mesh_radius=None,
         point_mesh_neighbours=32, point_mesh_min_neighbours=3, simplify_mesh_voxel=None, simplify_mesh_average=False,
+        smooth_mesh_iterations=None, smooth_mesh_laplacian=False, smooth_mesh_lambda=None, smooth_mesh_mu=None, smooth_mesh_fixed_boundary=False,
         groundtruth_transform=None, point_normals_neighbours=None,
         point_normals_max_distance=None, clean_points_neighbours=None, clean_points_ratio=2.0, clean_points_max_distance=None,
         clean_points_radius=None, clean_points_min_neighbours=None, clean_mesh_area=None, clean_mesh_faces=None, clean_mesh_largest=False):
@@ -99,6 +100,18 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     before the simplification.  The ground-truth side is never simplified, ``render_keyframes`` ray-casts the volume, and the mesh of
     ``point_mesh_voxel`` is not simplified.  Without these flags every file is what it is without them, byte for byte.
 
+    ``smooth_mesh_iterations`` (a count, 0 .. 1024) with ``smooth_mesh_laplacian``, ``smooth_mesh_lambda``, ``smooth_mesh_mu`` and
+    ``smooth_mesh_fixed_boundary``: the system's mesh, after ``clean_mesh_*`` and before ``simplify_mesh_*`` where those are given, goes
+    through ``dvmvs.smooth.smooth_mesh`` on the device: that many iterations of Taubin's filter (a step with ``smooth_mesh_lambda``,
+    default 0.5, then one with ``smooth_mesh_mu``, default -0.53, which does not shrink the surface), with ``smooth_mesh_laplacian`` of the
+    plain Laplacian filter (a step with lambda), with ``smooth_mesh_fixed_boundary`` without moving the vertices on an open edge
+    (``SmoothSettings``); the normals are recomputed from the smoothed faces.  The system's files are then written under
+    ``<system_name>+smooth`` (after ``+clean``, before ``+simple``), its ``.ply`` files, the progressive ones included, are the smoothed
+    meshes, and ``evaluate_3d`` scores the smoothed surface; ``_errors3d.npz`` then also holds ``smooth_iterations``, ``smooth_method``,
+    ``smooth_lambda``, ``smooth_mu`` and ``smooth_fixed_boundary``.  The ground-truth side is never smoothed, ``render_keyframes``
+    ray-casts the volume, and the mesh of ``point_mesh_voxel`` is not smoothed (its implicit surface is smooth already).  Without these
+    flags every file is what it is without them, byte for byte.
+
     ``clean_points_neighbours`` (a count, 1 .. 32) with ``clean_points_ratio`` and ``clean_points_max_distance`` (metres),
     ``clean_points_radius`` (metres) with ``clean_points_min_neighbours`` (each needs ``save_point_cloud``): the fused point cloud goes
     through ``dvmvs.outliers.filter_outliers`` on the device before it comes down (``OutlierFilter``).  The first removes the points whose
@@ -151,7 +164,7 @@ class Settings:
     dataset_name: str
     scene_name: str
     system_name: str                   # as given: it names the prediction file and the keyframe index
-    output_name: str                   # with "+consistent", "+clean" and "+simple" where those apply: it names every file that is written
+    output_name: str                   # with "+consistent", "+clean", "+smooth", "+simple" where those apply: it names every file that is written
     voxel_size: float
     max_depth: float
     use_groundtruth_to_anchor: bool
@@ -176,6 +189,7 @@ class Settings:
     align: dict                        # _aligned_score's keywords: align_distance, align_scale, align_plane (None or score_against's keywords)
     clean: object                      # ComponentFilter of clean_mesh_*, or None
     simplify: object                   # SimplifySettings of simplify_mesh_*, or None
+    smooth: object                     # SmoothSettings of smooth_mesh_*, or None
     clean_points: object               # OutlierFilter of clean_points_*, or None
     point_normals: Optional[tuple]     # (neighbours, max_distance) of point_normals_*, or None
     point_mesh: Optional[tuple]        # (voxel, radius, neighbours, min_neighbours) of point_mesh_*, or None
@@ -186,6 +200,8 @@ def _settings(arguments):
     a = SimpleNamespace(**arguments)
     clean = _clean_filter(a.clean_mesh_area, a.clean_mesh_faces, a.clean_mesh_largest)
     simplify = _simplify_settings(a.simplify_mesh_voxel, a.simplify_mesh_average)
+    smooth = _smooth_settings(a.smooth_mesh_iterations, a.smooth_mesh_laplacian, a.smooth_mesh_lambda, a.smooth_mesh_mu,
+                              a.smooth_mesh_fixed_boundary)
     clean_points = _clean_points_filter(a.save_point_cloud, a.clean_points_neighbours, a.clean_points_ratio, a.clean_points_max_distance,
                                         a.clean_points_radius, a.clean_points_min_neighbours)
     point_normals = _point_normals_settings(a.save_point_cloud, a.point_normals_neighbours, a.point_normals_max_distance)
@@ -222,7 +238,7 @@ def _settings(arguments):
     if a.evaluate_3d_align is not None and not float(a.evaluate_3d_align) > 0.0:
         raise ValueError(f"evaluate_3d_align must be a positive distance, got {a.evaluate_3d_align}")
     output_name = a.system_name + ("+consistent" if a.filter_consistency else "") + ("+clean" if clean is not None else "") + (
-        "+simple" if simplify is not None else "")
+        "+smooth" if smooth is not None else "") + ("+simple" if simplify is not None else "")
     return Settings(
         reconstruction_folder=a.reconstruction_folder, prediction_folder=a.prediction_folder, data_folder=a.data_folder,
         dataset_name=a.dataset_name, scene_name=a.scene_name, system_name=a.system_name, output_name=output_name, voxel_size=a.voxel_size,
@@ -236,7 +252,7 @@ def _settings(arguments):
         fuse_groundtruth_3d=a.evaluate_3d and a.groundtruth_mesh is None,
         visible_min_views=int(a.evaluate_3d_min_views) if a.evaluate_3d_visible else None,
         align={"align_distance": a.evaluate_3d_align, "align_scale": a.evaluate_3d_align_scale, "align_plane": align_plane},
-        clean=clean, simplify=simplify, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh)
+        clean=clean, simplify=simplify, smooth=smooth, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh)
 
 
 def _number(value):
@@ -275,6 +291,36 @@ def _simplify_settings(simplify_mesh_voxel, simplify_mesh_average):
         raise ValueError(f"simplify_mesh_voxel must be a positive, finite cell edge in metres, got {simplify_mesh_voxel!r}")
     from dvmvs.simplify import SimplifySettings
     return SimplifySettings(float(simplify_mesh_voxel), "average" if simplify_mesh_average else "quadric")
+
+
+def _smooth_settings(iterations, laplacian, lam, mu, fixed_boundary):
+    """The ``SmoothSettings`` of ``run``'s five settings, None when no iteration count is given; each refusal names its flag."""
+    for flag, value in (("smooth_mesh_laplacian", laplacian), ("smooth_mesh_fixed_boundary", fixed_boundary)):
+        if not isinstance(value, bool):
+            raise ValueError(f"{flag} must be a bool, got {value!r}")
+    if iterations is None:
+        if laplacian or lam is not None or mu is not None or fixed_boundary:
+            raise ValueError("smooth_mesh_laplacian, smooth_mesh_lambda, smooth_mesh_mu and smooth_mesh_fixed_boundary say how "
+                             "smooth_mesh_iterations smooths: they need smooth_mesh_iterations")
+        return None
+    if not _number(iterations) or not float(iterations).is_integer() or not 0 <= int(iterations) <= 1024:
+        raise ValueError(f"smooth_mesh_iterations must be a whole number of iterations in [0, 1024], got {iterations!r}")
+    if lam is not None and not (_number(lam) and 0.0 < float(lam) <= 1.0):
+        raise ValueError(f"smooth_mesh_lambda must be a factor in (0, 1], got {lam!r}")
+    if mu is not None and laplacian:
+        raise ValueError("smooth_mesh_mu is the second factor of Taubin's filter: it excludes smooth_mesh_laplacian")
+    from dvmvs.smooth import SmoothSettings, smooth_settings
+    defaults = SmoothSettings(0)
+    lam = defaults.lam if lam is None else float(lam)
+    if mu is not None and not (_number(mu) and -1.0 <= float(mu) < -lam):
+        raise ValueError(f"smooth_mesh_mu must be a factor in [-1, -smooth_mesh_lambda) = [-1, {-lam}), got {mu!r}")
+    smooth = SmoothSettings(int(iterations), "laplacian" if laplacian else "taubin", lam, defaults.mu if mu is None else float(mu),
+                            "fixed" if fixed_boundary else "free")
+    try:
+        smooth_settings(smooth)
+    except ValueError as e:
+        raise ValueError(f"smooth_mesh_lambda / smooth_mesh_mu: {e}") from None
+    return smooth
 
 
 def _clean_points_filter(save_point_cloud, neighbours, ratio, max_distance, radius, min_neighbours):
@@ -545,7 +591,7 @@ def _fuse_system(settings, scene, images, predictions, volume_bounds):
     volume = TSDFVolume(volume_bounds, voxel_size=settings.voxel_size, device=settings.device)
     mesh_name = _mesh_name(settings, settings.output_name)
     TSDFFusion.integrate(volume, images, predictions, scene.keyframe_poses, scene.scaled_K, mesh_name, settings.save_progressive,
-                         simplify=settings.simplify, clean=settings.clean)
+                         simplify=settings.simplify, smooth=settings.smooth, clean=settings.clean)
     return volume, mesh_name
 
 
@@ -581,11 +627,21 @@ def _clean_entries(volume, clean):
             "clean_faces": np.array([kept, total], dtype=np.int64)}
 
 
-def _simplify_entries(volume, clean, simplify):
+def _smooth_entries(smooth):
+    """What ``_errors3d.npz`` gains with a ``SmoothSettings``: its settings."""
+    if smooth is None:
+        return {}
+    print("Mesh smoothed by {} iterations of the {} filter (lambda {}, mu {}, boundary {})".format(smooth.iterations, smooth.method, smooth.lam,
+                                                                                                  smooth.mu, smooth.boundary))
+    return {"smooth_iterations": np.int64(smooth.iterations), "smooth_method": np.array(smooth.method), "smooth_lambda": np.float64(smooth.lam),
+            "smooth_mu": np.float64(smooth.mu), "smooth_fixed_boundary": np.bool_(smooth.boundary == "fixed")}
+
+
+def _simplify_entries(volume, clean, simplify, smooth=None):
     """What ``_errors3d.npz`` gains with a ``SimplifySettings``: its settings and the faces of the system's mesh after and before it."""
     if simplify is None:
         return {}
-    kept = int(volume.mesh_tensors(simplify=simplify, clean=clean)[1].shape[0])
+    kept = int(volume.mesh_tensors(simplify=simplify, smooth=smooth, clean=clean)[1].shape[0])
     total = int(volume.mesh_tensors(clean=clean)[1].shape[0])
     print("Mesh simplified with cells of {} m ({}): {} of {} faces left".format(simplify.voxel, simplify.contraction, kept, total))
     return {"simplify_voxel": np.float64(simplify.voxel), "simplify_average": np.bool_(simplify.contraction == "average"),
@@ -605,6 +661,8 @@ def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
         score["clean"] = clean
     if settings.simplify is not None:
         score["simplify"] = settings.simplify
+    if settings.smooth is not None:
+        score["smooth"] = settings.smooth
     if settings.visible_min_views is not None:
         if not scene.keyframe_poses:
             raise ValueError("evaluate_3d_visible: the scene has no keyframe to take the visibility from")
@@ -616,7 +674,7 @@ def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
         print("Ground truth restricted to what {} keyframes saw: {} of {} faces".format(len(scene.keyframe_poses), kept[0][0], kept[0][1]))
         extra = {"visible_faces": np.int64(kept[0][0]), "total_faces": np.int64(kept[0][1])}
     if settings.protocol_3d:
-        sizes = (int(volume.vertices(simplify=settings.simplify, clean=clean).shape[0]), int(groundtruth[0].shape[0]))
+        sizes = (int(volume.vertices(simplify=settings.simplify, smooth=settings.smooth, clean=clean).shape[0]), int(groundtruth[0].shape[0]))
         print("3-D metrics at {} m over {} predicted and {} ground-truth points (density {}, voxel {}; {} and {} vertices): {}".format(
             threshold, points[0], points[1], density, voxel, sizes[0], sizes[1], metrics))
         extra = {"sample_density": np.float64(np.nan if density is None else density), "voxel": np.float64(np.nan if voxel is None else voxel),
@@ -626,7 +684,7 @@ def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
         print("3-D metrics at {} m over {} predicted and {} ground-truth vertices: {}".format(threshold, sizes[0], sizes[1], metrics))
     np.savez_compressed(mesh_name + "_errors3d.npz", arr_0=row, names=np.array(RECONSTRUCTION_METRICS), counts=np.array(sizes, dtype=np.int64),
                         threshold=np.float32(threshold), **extra, **aligned, **_clean_entries(volume, clean),
-                        **_simplify_entries(volume, clean, settings.simplify))
+                        **_smooth_entries(settings.smooth), **_simplify_entries(volume, clean, settings.simplify, settings.smooth))
 
 
 def _render_keyframes(settings, scene, volume):
@@ -750,6 +808,17 @@ def build_parser():
                              "metres, placed by the quadrics of the faces around it; files are written under <system>+simple")
     parser.add_argument("--simplify_mesh_average", action="store_true",
                         help="with --simplify_mesh_voxel: a cell's vertex is the mean of its vertices instead of the quadric minimiser")
+    parser.add_argument("--smooth_mesh_iterations", default=None, type=int,
+                        help="smooth the system's mesh on the device (after --clean_mesh_*, before --simplify_mesh_*): this many "
+                             "iterations of Taubin's filter; normals are recomputed; files are written under <system>+smooth")
+    parser.add_argument("--smooth_mesh_laplacian", action="store_true",
+                        help="with --smooth_mesh_iterations: the plain Laplacian filter (it shrinks the surface) instead of Taubin's")
+    parser.add_argument("--smooth_mesh_lambda", default=None, type=float,
+                        help="with --smooth_mesh_iterations: the factor of the smoothing step, in (0, 1] (default 0.5)")
+    parser.add_argument("--smooth_mesh_mu", default=None, type=float,
+                        help="with --smooth_mesh_iterations: the factor of Taubin's second step, in [-1, -lambda) (default -0.53)")
+    parser.add_argument("--smooth_mesh_fixed_boundary", action="store_true",
+                        help="with --smooth_mesh_iterations: the vertices on an open edge of the mesh do not move")
     parser.add_argument("--clean_points_neighbours", default=None, type=int,
                         help="with --save_point_cloud: statistical outlier removal of the fused cloud on the device, over this many nearest "
                              "neighbours (1 .. 32); the result is written additionally as <mesh name>_pointcloud_clean.ply")

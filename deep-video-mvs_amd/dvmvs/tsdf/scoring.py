@@ -8,7 +8,8 @@ from dvmvs.tsdf.volume import TSDFVolume
 
 
 def score_volume(volume, reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
-                 return_transform, clean=None, align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, simplify=None):
+                 return_transform, clean=None, align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, simplify=None,
+                 smooth=None):
     """``TSDFVolume.score_against`` of ``volume``: ``(what it returns, the registration's record or None)``; the record is
     ``dvmvs.hip.registration.icp``'s (with ``align_plane``: ``icp_plane``'s) ``info`` (device tensors)."""
     from dvmvs.errors import _check_alignment, _check_plane, _score_device, prepare_points_device
@@ -49,10 +50,10 @@ def score_volume(volume, reference, threshold, return_sizes, sample_density, vox
     if prepare:
         if gt_faces is not None:
             gt_faces = torch.as_tensor(gt_faces, device=volume.device).to(torch.int32)
-        pred = volume.surface_points(sample_density, voxel, clean=clean, simplify=simplify)
+        pred = volume.surface_points(sample_density, voxel, clean=clean, simplify=simplify, smooth=smooth)
         gt = prepare_points_device(gt.contiguous(), gt_faces, sample_density, voxel)
     else:
-        pred = volume.vertices(clean=clean, simplify=simplify)
+        pred = volume.vertices(clean=clean, simplify=simplify, smooth=smooth)
     if pred.shape[0] == 0 or gt.shape[0] == 0:
         raise ValueError(f"score_against: a surface without a vertex cannot be scored ({pred.shape[0]} predicted, {gt.shape[0]} reference)")
     row, transform, info = _score_device(pred, gt.contiguous(), threshold, None, None, None, None, None, align_distance, align_scale, None,

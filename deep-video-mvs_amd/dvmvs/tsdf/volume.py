@@ -12,13 +12,26 @@ def fold_color(color_im):
     return np.floor(c[..., 2] * np.float32(65536.0) + c[..., 1] * np.float32(256.0) + c[..., 0]).astype(np.float32)
 
 
-def mesh_stages(simplify, clean):
-    """``(simplify, clean)`` of a method that takes both.  ``simplify`` stands before ``clean`` in the signatures, where ``clean`` alone
-    stood before: a ``ComponentFilter`` that arrives in its place, given by position, is the ``clean`` it always was."""
+def mesh_stages(*stages):
+    """``(simplify, clean)`` of a method's two arguments, or ``(simplify, smooth, clean)`` of its three, as they stand in the signatures.
+    ``simplify`` stands before ``clean``, where ``clean`` alone stood before, and ``smooth`` now stands between them, so a settings object
+    given by position may arrive in another stage's slot: a ``ComponentFilter`` is the ``clean`` it always was, a ``SimplifySettings`` the
+    ``simplify`` and a ``SmoothSettings`` the ``smooth``, wherever they arrive.  Anything else stays in its slot, for the stage's own
+    check to refuse; two values for one stage are a ``ValueError``."""
     from dvmvs.components import ComponentFilter
-    if isinstance(simplify, ComponentFilter) and clean is None:
-        return None, simplify
-    return simplify, clean
+    from dvmvs.simplify import SimplifySettings
+    from dvmvs.smooth import SmoothSettings
+    names = {2: ("simplify", "clean"), 3: ("simplify", "smooth", "clean")}[len(stages)]
+    types = {"simplify": SimplifySettings, "smooth": SmoothSettings, "clean": ComponentFilter}
+    placed = {}
+    for slot, value in zip(names, stages):
+        if value is None:
+            continue
+        stage = next((name for name in names if isinstance(value, types[name])), slot)
+        if stage in placed:
+            raise ValueError(f"two values for the stage {stage}: {placed[stage]!r} and {value!r}")
+        placed[stage] = value
+    return tuple(placed.get(name) for name in names)
 
 
 class TSDFVolume:
@@ -143,24 +156,32 @@ class TSDFVolume:
             mesh = filter_components_device(mesh[0], mesh[1], clean, mesh[2], mesh[3])
         return mesh
 
-    def _surface(self, color, simplify, clean):
-        """``_extract``, and with ``simplify`` (a ``dvmvs.simplify.SimplifySettings``) what it leaves through ``simplify_mesh`` on the
-        device; without it, ``_extract`` and nothing else."""
-        simplify, clean = mesh_stages(simplify, clean)
+    def _surface(self, color, simplify, smooth, clean):
+        """``_extract``; with ``smooth`` (a ``dvmvs.smooth.SmoothSettings``) what it leaves through ``smooth_mesh`` on the device; with
+        ``simplify`` (a ``dvmvs.simplify.SimplifySettings``) what that leaves through ``simplify_mesh`` on the device: extract -> clean ->
+        smooth -> simplify.  Without the two, ``_extract`` and nothing else."""
+        simplify, smooth, clean = mesh_stages(simplify, smooth, clean)
         mesh = self._extract(color, clean)
+        if smooth is not None:
+            from dvmvs.smooth import smooth_mesh_device, smooth_settings
+            smooth_settings(smooth)
+            mesh = smooth_mesh_device(mesh[0], mesh[1], smooth, mesh[2], mesh[3])
         if simplify is not None:
             from dvmvs.simplify import simplify_mesh_device, simplify_settings
             simplify_settings(simplify)
             mesh = simplify_mesh_device(mesh[0], mesh[1], simplify, mesh[2], mesh[3])
         return mesh
 
-    def get_mesh(self, simplify=None, clean=None):
+    def get_mesh(self, simplify=None, smooth=None, clean=None):
         """(verts [V,3] float32 in world units, faces [F,3] int32, normals [V,3] float32, colours [V,3] uint8 RGB) of the zero
         iso-surface, as numpy arrays (run-tsdf-reconstruction.py:334-351); extracted on the device by ``marching_cubes``.  ``clean``: a
         ``dvmvs.components.ComponentFilter``; the mesh then goes through ``filter_components`` on the device before it is downloaded.
         ``simplify``: a ``dvmvs.simplify.SimplifySettings``; the mesh, cleaned first where ``clean`` is given, then goes through
-        ``simplify_mesh`` on the device: one vertex per occupied cell of ``simplify.voxel`` metres, normals and colours merged alongside."""
-        verts, faces, norms, colors = self._surface(True, simplify, clean)
+        ``simplify_mesh`` on the device: one vertex per occupied cell of ``simplify.voxel`` metres, normals and colours merged alongside.
+        ``smooth``: a ``dvmvs.smooth.SmoothSettings``; the mesh, after ``clean`` and before ``simplify``, goes through ``smooth_mesh`` on
+        the device: the Laplacian or Taubin filter moves the vertices, the normals are recomputed from the smoothed faces, faces and
+        colours stay."""
+        verts, faces, norms, colors = self._surface(True, simplify, smooth, clean)
         return verts.cpu().numpy(), faces.cpu().numpy(), norms.cpu().numpy(), colors.cpu().numpy()
 
     def get_point_cloud(self):
@@ -168,30 +189,31 @@ class TSDFVolume:
         verts, _, _, colors = self.get_mesh()
         return np.hstack([verts, colors])
 
-    def vertices(self, simplify=None, clean=None):
+    def vertices(self, simplify=None, smooth=None, clean=None):
         """The vertices of the zero iso-surface (``get_mesh()[0]``) as a float32 [V,3] DEVICE tensor: nothing but ``marching_cubes``'
         two counts is read by the host (with ``clean``, as ``get_mesh`` takes it, also ``filter_components``' counts; with ``simplify``, as
-        ``get_mesh`` takes it, also ``simplify_mesh``'s)."""
-        return self._surface(False, simplify, clean)[0]
+        ``get_mesh`` takes it, also ``simplify_mesh``'s; ``smooth``, as ``get_mesh`` takes it, reads nothing)."""
+        return self._surface(False, simplify, smooth, clean)[0]
 
-    def mesh_tensors(self, simplify=None, clean=None):
+    def mesh_tensors(self, simplify=None, smooth=None, clean=None):
         """``(verts float32 [V,3], faces int32 [F,3])`` of the zero iso-surface as DEVICE tensors, as ``marching_cubes`` leaves them (with
         ``clean``, as ``get_mesh`` takes it: as ``filter_components`` leaves them; with ``simplify``, as ``get_mesh`` takes it: as
-        ``simplify_mesh`` leaves them)."""
-        return self._surface(False, simplify, clean)[:2]
+        ``simplify_mesh`` leaves them; with ``smooth``, as ``get_mesh`` takes it: smoothed between the two)."""
+        return self._surface(False, simplify, smooth, clean)[:2]
 
-    def surface_points(self, sample_density=None, voxel=None, simplify=None, clean=None):
+    def surface_points(self, sample_density=None, voxel=None, simplify=None, smooth=None, clean=None):
         """The point set the 3-D metrics take from this volume's surface, as a float32 [N,3] DEVICE tensor: the vertices of the zero
         iso-surface; with ``sample_density`` (points per square metre) instead ``dvmvs.hip.ops.surface_sample`` of its faces; with ``voxel``
         (metres) then ``dvmvs.hip.ops.voxel_downsample`` of that (``dvmvs.errors.prepare_points`` is the host definition of both).  The
         vertices and faces stay on the device; each step reads its output's size once.  ``clean``: as ``get_mesh`` takes it; the points are
-        then those of the cleaned mesh; ``simplify``: as ``get_mesh`` takes it; the points are then those of the simplified mesh."""
+        then those of the cleaned mesh; ``simplify``: as ``get_mesh`` takes it; the points are then those of the simplified mesh;
+        ``smooth``: as ``get_mesh`` takes it; the points are then those of the smoothed mesh."""
         from dvmvs.errors import prepare_points_device
-        verts, faces = self.mesh_tensors(simplify=simplify, clean=clean)
+        verts, faces = self.mesh_tensors(simplify=simplify, smooth=smooth, clean=clean)
         return prepare_points_device(verts, faces, sample_density, voxel)
 
     def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None, clean=None,
-                      simplify=None, align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, align_distance=None,
+                      simplify=None, smooth=None, align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, align_distance=None,
                       align_scale=False, return_transform=False):
         """The 3-D reconstruction metrics of this volume's surface (the prediction) against ``reference`` (the ground truth): a float32 [6]
         DEVICE tensor in the order of ``dvmvs.errors.RECONSTRUCTION_METRICS`` (acc, comp, chamfer, precision, recall, fscore), computed by
@@ -221,6 +243,9 @@ class TSDFVolume:
         device before its vertices are taken or its faces sampled: the score is that of the simplified surface.  The reference is never
         simplified.
 
+        ``smooth``: a ``dvmvs.smooth.SmoothSettings``.  The PREDICTION's mesh, after ``clean`` and before ``simplify``, goes through
+        ``smooth_mesh`` on the device: the score is that of the smoothed surface.  The reference is never smoothed.
+
         ``align_distance`` (metres): before it is scored, the prediction's point set is registered to the reference's by trimmed ICP
         with that inlier distance and moved by the result (``dvmvs.hip.registration.icp``; ``dvmvs.errors.register_points`` is the host
         definition), so that a residual pose offset does not decide the score; ``align_scale`` lets the registration also find a scale.
@@ -235,4 +260,4 @@ class TSDFVolume:
         from dvmvs.tsdf.scoring import score_volume      # (scoring sits above this module: it needs TSDFVolume to tell a volume reference)
         return score_volume(self, reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
                             return_transform, clean=clean, align_plane=align_plane, align_normal_neighbours=align_normal_neighbours,
-                            align_normal_distance=align_normal_distance, simplify=simplify)[0]
+                            align_normal_distance=align_normal_distance, simplify=simplify, smooth=smooth)[0]

@@ -75,7 +75,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_implicit_* (the implicit moving-least-squares signed distance of an oriented point cloud on a voxel grid,
  * and the trimming of the mesh that marching cubes makes of it); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_mesh_simplify_* and dvmvs_voxel_downsample_runs (simplifying a triangle mesh by vertex clustering with
- * quadric error representatives); no earlier signature changed, the number stays 11 by the same rule. */
+ * quadric error representatives); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_mesh_smooth_* (smoothing a triangle mesh by the Laplacian and Taubin filters; vertex normals from the
+ * faces); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -1126,6 +1128,57 @@ int dvmvs_mesh_simplify_count(const float* verts, const float* normals, const un
 int dvmvs_mesh_simplify_emit(long long V, long long F, void* workspace, size_t workspace_bytes, long long V_out, long long F_out,
                              float* verts_out, int* faces_out, float* normals_out, unsigned char* colors_out, int* vertex_cluster,
                              int* face_index, dvmvs_stream_t stream);
+
+/*
+ * Smoothing a triangle mesh (the umbrella Laplacian filter and Taubin's lambda / mu filter) and area-weighted vertex normals from the
+ * faces (ABI 11, later addition; csrc/mesh_smooth.hip).  The reference project has nothing for this: the definition is this project's own
+ * (dvmvs/smooth.py is its host form and states every step; Open3D's filter_smooth_laplacian, filter_smooth_taubin and
+ * compute_vertex_normals are the usual tools).
+ *   verts [V,3] fp32, faces [F,3] int32 (fallback [V,3] fp32), contiguous, 4-byte aligned; V in [1, 2^28], F in [0, 2^28].
+ * Arithmetic: fp64 from the fp32 inputs with +, -, *, / and sqrt only, every operation correctly rounded, nothing contracted.
+ *   1. A face counts when its three indices lie in [0, V) and are pairwise different; every other face takes no part.
+ *   2. Rows: N(v) is the set of distinct u that share a counting face with v, in ascending u.  A counting face (a, b, c) emits the
+ *      directed pairs (a,b), (b,a), (b,c), (c,b), (c,a), (a,c); boundary[v] is set when some pair (v, u) is emitted exactly once over all
+ *      counting faces (an edge of one face; not an edge of two faces, whatever their orientation, nor of three).
+ *   3. A step with factor s, all reads from the previous iterate: when n = |N(v)| is 0, or fixed_boundary and boundary[v], the
+ *      position's bits are copied; otherwise per component S = (((0.0 + x_u1) + x_u2) + ...) over N(v) in order, m = S / fp64(n),
+ *      x' = fp32(x_v + s * (m - x_v)).  The iterate between steps is fp32.
+ *   4. taubin = 0: `iterations` steps with lam.  taubin = 1: per iteration a step with lam, then one with mu.  No step: verts_out = verts.
+ *   5. Vertex normals: over the incidences (f, j) of a vertex, the counting faces f whose corner j it is, in ascending 3 f + j, the sum
+ *      from 0.0 of n_f = e1 x e2 = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), e1 = p1 - p0, e2 = p2 - p0 of the fp32
+ *      positions taken as fp64 (area-weighted, not normalised per face); len = sqrt((xx + yy) + zz); each component divided by len and
+ *      rounded to fp32; unless 0 < len < inf the row of `fallback`, or (0, 0, 0) where fallback is NULL.
+ * Coordinates that are not finite are outside the contract (the result is unspecified; nothing is addressed out of bounds).
+ * Call sequence for one mesh, every call on one stream, `workspace` this block's:
+ *   dvmvs_mesh_smooth_keys -> pair_keys int64 [6F]: (a << 32) | b of the six pairs of face f from 6 f, INT64_MAX for a face that does not
+ *   count; corner_keys int32 [3F]: the vertex of corner j of face f at 3 f + j, INT_MAX likewise (either may be NULL, not both) ->
+ *   a sort of pair_keys (values only; equal keys are identical) -> dvmvs_mesh_smooth_rows: offsets int32 [V+1], neighbours int32 [6F] (the
+ *   first offsets[V] are used: the host never needs that number) and the boundary flags, in the workspace -> dvmvs_mesh_smooth_steps:
+ *   ALL steps of the call, one launch per step, between two buffers of the workspace that hold the positions as 16-byte float4 (packed
+ *   = 1: as 12-byte fp32 x 3, a tool's comparison), the last step into verts_out [V,3]; verts is never written and may not be verts_out.
+ *   dvmvs_mesh_smooth_rows_export copies the rows out: offsets int64 [V+1], neighbours int32 [6F] (-1 past offsets[V]), boundary uint8 [V].
+ *   dvmvs_mesh_smooth_normals (needs no rows): corner_sorted int32 [3F] and corner_order int64 [3F] are a STABLE sort of corner_keys;
+ *   normals [V,3] may not be verts.
+ * One lane owns a vertex and walks its row or its incidences serially, in the order above; no float atomics, no float value crosses
+ * threads, no barrier across workgroups: the results are bit-identical run to run.  No index read from memory becomes an address before it
+ * is checked against its array's size.  Nothing is read back by the host anywhere in the sequence.
+ * dvmvs_mesh_smooth_workspace_bytes: host only; 0 for V or F outside [0, 2^28].  The block is 16-byte aligned.
+ * Every entry returns DVMVS_EINVAL for a null or misaligned pointer that a non-empty side needs, V < 1 (keys: V < 0), F < 0, iterations < 0,
+ * lam outside (0, 1], a mu that is not finite or, with taubin, outside [-1, -lam), a flag that is not 0 / 1, a workspace that is too small;
+ * DVMVS_EUNSUPPORTED for V or F above 2^28 or more than 1024 iterations.  Nothing is enqueued in either case.
+ */
+size_t dvmvs_mesh_smooth_workspace_bytes(long long V, long long F);
+int dvmvs_mesh_smooth_keys(const int* faces, long long V, long long F, long long* pair_keys, int* corner_keys, dvmvs_stream_t stream);
+int dvmvs_mesh_smooth_rows(const long long* pair_sorted, long long V, long long F, void* workspace, size_t workspace_bytes,
+                           dvmvs_stream_t stream);
+int dvmvs_mesh_smooth_rows_export(long long V, long long F, const void* workspace, size_t workspace_bytes, long long* offsets,
+                                  int* neighbours, unsigned char* boundary, dvmvs_stream_t stream);
+int dvmvs_mesh_smooth_steps(const float* verts, long long V, long long F, int iterations, int taubin, double lam, double mu,
+                            int fixed_boundary, int packed, void* workspace, size_t workspace_bytes, float* verts_out,
+                            dvmvs_stream_t stream);
+int dvmvs_mesh_smooth_normals(const float* verts, long long V, const int* faces, long long F, const int* corner_sorted,
+                              const long long* corner_order, const float* fallback, void* workspace, size_t workspace_bytes, float* normals,
+                              dvmvs_stream_t stream);
 
 /*
  * The k nearest neighbours of points, neighbours within a radius, and statistical outlier scores (ABI 11, later addition;
