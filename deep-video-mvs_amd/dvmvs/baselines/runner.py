@@ -317,11 +317,27 @@ def live_fusion_for_scene(scene_folder, size, voxel_size, max_depth, batch, devi
     return LiveFusion(bounds, voxel_size=voxel_size, max_depth=max_depth, batch=batch, device=device)
 
 
-def main(method, argv=None):
-    """``python -m dvmvs.baselines.{mvdepthnet,gpmvs,dpsnet} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]
-    [--device-preprocess] [--device-evaluate] [--fuse [--fuse_voxel_size M] [--fuse_max_depth M] [--fuse_batch N]]``."""
+def sparse_live_fusion(voxel_size, max_depth, batch, max_bricks, device="cuda"):
+    """The ``LiveFusion`` of ``--fuse --fuse_sparse``: no bounds, so nothing of the scene is read -- not its poses, not its intrinsics; the
+    frames go into a ``SparseTSDFVolume`` of ``max_bricks`` bricks that allocates what they touch."""
+    from dvmvs.tsdf import LiveFusion
+    return LiveFusion(None, voxel_size=voxel_size, max_depth=max_depth, batch=batch, device=device, max_bricks=max_bricks)
+
+
+def fusion_for_arguments(args, size):
+    """The ``LiveFusion`` that the parsed ``--fuse*`` flags ask for, or None: with ``--fuse_sparse`` without a look at the scene."""
+    if not args.fuse:
+        if args.fuse_sparse:
+            raise SystemExit("--fuse_sparse says how --fuse fuses: it needs --fuse")
+        return None
+    if args.fuse_sparse:
+        return sparse_live_fusion(args.fuse_voxel_size, args.fuse_max_depth, args.fuse_batch, args.fuse_bricks)
+    return live_fusion_for_scene(args.scene_folder, size, args.fuse_voxel_size, args.fuse_max_depth, args.fuse_batch)
+
+
+def build_parser(method):
+    """The parser of ``python -m dvmvs.baselines.<method>``."""
     import argparse
-    from dvmvs.utils import save_results
     parser = argparse.ArgumentParser(prog=f"python -m dvmvs.baselines.{method}")
     parser.add_argument("scene_folder")
     parser.add_argument("keyframe_index_file")
@@ -339,13 +355,22 @@ def main(method, argv=None):
     parser.add_argument("--fuse_voxel_size", default=0.025, type=float)
     parser.add_argument("--fuse_max_depth", default=5.0, type=float)
     parser.add_argument("--fuse_batch", default=8, type=int, help="frames fused per launch")
-    args = parser.parse_args(argv)
+    parser.add_argument("--fuse_sparse", action="store_true",
+                        help="with --fuse: fuse into a brick-hashed volume that needs no bounds, so the scene's poses are not read in advance")
+    parser.add_argument("--fuse_bricks", default=65536, type=int, help="with --fuse_sparse: the pool's capacity in bricks of 8 x 8 x 8 voxels")
+    return parser
+
+
+def main(method, argv=None):
+    """``python -m dvmvs.baselines.{mvdepthnet,gpmvs,dpsnet} SCENE_FOLDER INDEX_FILE [--weights DIR] [--without-ft] [--out DIR]
+    [--device-preprocess] [--device-evaluate] [--fuse [--fuse_voxel_size M] [--fuse_max_depth M] [--fuse_batch N]
+    [--fuse_sparse [--fuse_bricks N]]]``."""
+    from dvmvs.utils import save_results
+    args = build_parser(method).parse_args(argv)
     predict = {"mvdepthnet": predict_mvdepthnet, "gpmvs": predict_gpmvs, "dpsnet": predict_dpsnet}[method]
     size = (DPS_WIDTH, DPS_HEIGHT) if method == "dpsnet" else (WIDTH, HEIGHT)
     error_log = []
-    fuse = None
-    if args.fuse:
-        fuse = live_fusion_for_scene(args.scene_folder, size, args.fuse_voxel_size, args.fuse_max_depth, args.fuse_batch)
+    fuse = fusion_for_arguments(args, size)
     predictions, reference_depths, timer = predict(args.scene_folder, args.keyframe_index_file, args.weights, max_frames=args.max_frames,
                                                   device_preprocess=args.device_preprocess, device_evaluate=args.device_evaluate,
                                                   error_log=error_log, fuse=fuse)

@@ -188,6 +188,14 @@ SIGNATURES = {
                                          ctypes.c_size_t, _c_fp, _c_stream]),
     "dvmvs_mesh_smooth_normals": (_c_int, [_c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_size_t,
                                            _c_fp, _c_stream]),
+    "dvmvs_sparse_mark": (_c_int, [_c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float,
+                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int, _c_stream]),
+    "dvmvs_sparse_assign": (_c_int, [_c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, _c_stream]),
+    "dvmvs_sparse_integrate": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, _c_f3,
+                                        ctypes.c_float, _c_int, _c_stream]),
+    "dvmvs_sparse_gather": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                     _c_int, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -232,6 +240,8 @@ ADDED_WITHIN_ABI_MESH_SIMPLIFY = ("dvmvs_mesh_simplify_workspace_bytes", "dvmvs_
 # ... and the seventeenth (smoothing a triangle mesh by the Laplacian and Taubin filters; vertex normals from the faces)
 ADDED_WITHIN_ABI_MESH_SMOOTH = ("dvmvs_mesh_smooth_workspace_bytes", "dvmvs_mesh_smooth_keys", "dvmvs_mesh_smooth_rows",
                                 "dvmvs_mesh_smooth_rows_export", "dvmvs_mesh_smooth_steps", "dvmvs_mesh_smooth_normals")
+# ... and the eighteenth (a TSDF volume without bounds: a hash table of bricks over a pool)
+ADDED_WITHIN_ABI_SPARSE_VOLUME = ("dvmvs_sparse_mark", "dvmvs_sparse_assign", "dvmvs_sparse_integrate", "dvmvs_sparse_gather")
 
 _lib = None
 _lock = threading.Lock()
@@ -254,7 +264,7 @@ def lib():
                  + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER
                  + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE + ADDED_WITHIN_ABI_MESH_COMPONENTS
                  + ADDED_WITHIN_ABI_POINT_NEIGHBOURS + ADDED_WITHIN_ABI_POINT_NORMALS + ADDED_WITHIN_ABI_REGISTRATION_PLANE
-                 + ADDED_WITHIN_ABI_IMPLICIT + ADDED_WITHIN_ABI_MESH_SIMPLIFY + ADDED_WITHIN_ABI_MESH_SMOOTH)
+                 + ADDED_WITHIN_ABI_IMPLICIT + ADDED_WITHIN_ABI_MESH_SIMPLIFY + ADDED_WITHIN_ABI_MESH_SMOOTH + ADDED_WITHIN_ABI_SPARSE_VOLUME)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

@@ -17,6 +17,8 @@ same bytes, ``integrate``, ``calculate_volume_bounds``) and ``run`` is its main 
 The modules, each importing only those before it: ``dvmvs.hip.volume`` (the two bindings: ``marching_cubes`` and the per-frame
 integration), ``mesh_views`` (``render_mesh``, ``visible_mesh``, the camera tensors), ``volume`` (``TSDFVolume``, ``fold_color``), ``ply``
 (the PLY reader and writers), ``scoring`` (the work of ``TSDFVolume.score_against``, which that method imports when it is called),
+``sparse_volume`` (``SparseTSDFVolume``, the volume that needs no bounds: a hash table of bricks over a pool; ``dense()`` gives a
+``TSDFVolume``; ``dvmvs.tsdf.SparseTSDFVolume`` resolves to it on first use, so importing the package loads what it always loaded),
 ``fusion`` (``TSDFFusion``, ``LiveFusion``) and ``program`` (``run``, its stages and the parser).
 """
 from dvmvs.hip.volume import marching_cubes
@@ -27,3 +29,11 @@ from dvmvs.tsdf.volume import TSDFVolume, fold_color
 
 __all__ = ["fold_color", "marching_cubes", "render_mesh", "visible_mesh", "VISIBLE_MESH_CHUNK", "TSDFVolume", "TSDFFusion", "LiveFusion", "run",
            "build_parser", "main", "load_transform", "apply_transform"]
+
+
+def __getattr__(name):
+    """``dvmvs.tsdf.SparseTSDFVolume``: imported when it is first asked for (PEP 562)."""
+    if name == "SparseTSDFVolume":
+        from dvmvs.tsdf.sparse_volume import SparseTSDFVolume
+        return SparseTSDFVolume
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

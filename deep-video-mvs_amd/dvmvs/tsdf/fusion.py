@@ -109,10 +109,17 @@ class LiveFusion:
     them agree within ``pixel_threshold`` pixels and ``relative_threshold`` of the depth.  The source tables of every batch size up to
     ``batch`` go up once, in the constructor, so ``add`` and ``flush`` stay free of blocking copies and host reads.  CONSEQUENCE: a flush of
     a single pending frame (the tail of a scene, or ``batch=1``) has no neighbour to agree with and fuses nothing.  With the default 0
-    nothing is allocated or launched for the filter and the volume's bits are those of the unfiltered fusion."""
+    nothing is allocated or launched for the filter and the volume's bits are those of the unfiltered fusion.
+
+    ``vol_bnds=None``: the extent of the scene is not known, and the frames are fused into a ``SparseTSDFVolume`` (``sparse``; a lattice
+    from ``sparse_origin`` and a pool of ``max_bricks`` bricks of 8 x 8 x 8 voxels) instead, which allocates what the frames touch; frames
+    before a brick's birth are not applied to it -- the one stated difference from the dense volume, inherent to every hashed volume.
+    ``volume`` is then ``sparse.dense()``, a ``TSDFVolume`` over the allocated bricks, made when it is asked for (one host read) and kept
+    until the next ``add``.  The consistency filter works on the depth maps before fusion and is the same in both modes.  With bounds
+    given nothing differs from what it was: ``sparse`` is None."""
 
     def __init__(self, vol_bnds, voxel_size=0.025, max_depth=5.0, batch=8, device="cuda", min_consistent_views=0, consistency_sources=4,
-                 pixel_threshold=1.0, relative_threshold=0.01):
+                 pixel_threshold=1.0, relative_threshold=0.01, max_bricks=65536, sparse_origin=(0.0, 0.0, 0.0)):
         batch = int(batch)
         if batch < 1:
             raise ValueError(f"LiveFusion: batch must be at least 1, got {batch}")
@@ -129,8 +136,15 @@ class LiveFusion:
             raise ValueError("LiveFusion: max_depth is NaN")
         from dvmvs.dataset_loader import FrameUploader
         self.batch, self.max_depth = batch, float(max_depth)
-        self._volume = TSDFVolume(vol_bnds, voxel_size, device=device)
-        self.device = self._volume._tsdf.device      # with its index ("cuda" -> "cuda:0"): what a tensor's ``.device`` compares equal to
+        if vol_bnds is None:
+            from dvmvs.tsdf.sparse_volume import SparseTSDFVolume
+            self.sparse = SparseTSDFVolume(voxel_size, origin=sparse_origin, max_bricks=max_bricks, device=device)
+            self._volume = None                      # sparse.dense(), made by ``volume`` and dropped by ``add``
+            self.device = self.sparse.device
+        else:
+            self.sparse = None
+            self._volume = TSDFVolume(vol_bnds, voxel_size, device=device)
+            self.device = self._volume._tsdf.device  # with its index ("cuda" -> "cuda:0"): what a tensor's ``.device`` compares equal to
         self._uploader = FrameUploader(self.device, slots=8)
         self._depth = self._rgb = self._K = self._P = None
         self._weights, self._pending, self.frames = [], 0, 0
@@ -167,6 +181,8 @@ class LiveFusion:
             raise ValueError(f"LiveFusion.add: colour must be uint8 [{h},{w},3] like the depth, got {rgb_u8.dtype} {tuple(rgb_u8.shape)}")
         matrices = np.concatenate([np.asarray(K, dtype=np.float32).reshape(9), np.asarray(pose, dtype=np.float32).reshape(16)])
         self._rings(h, w)
+        if self.sparse is not None:
+            self._volume = None
         slot = self._pending
         self._depth[slot].copy_(depth.reshape(h, w), non_blocking=True)
         staged = matrices.view(np.uint8)             # 100 bytes first, so the floats are aligned; a host colour image goes behind them
@@ -198,10 +214,13 @@ class LiveFusion:
             depth, _, _ = ops.depth_consistency(depth, self._K[:n], self._P[:n], self._source_tables[n - 1, :n], self.pixel_threshold,
                                                 self.relative_threshold, self.min_consistent_views, average=False, with_count=False,
                                                 out=self._filtered[:n])
-        self._volume.integrate_frames(self._rgb[:n], depth, self._K[:n], self._P[:n], obs_weight=self._weights, max_depth=self.max_depth)
+        target = self.sparse if self.sparse is not None else self._volume
+        target.integrate_frames(self._rgb[:n], depth, self._K[:n], self._P[:n], obs_weight=self._weights, max_depth=self.max_depth)
         self._weights, self._pending = [], 0
 
     @property
     def volume(self):
         self.flush()
+        if self._volume is None:
+            self._volume = self.sparse.dense()
         return self._volume

@@ -20,7 +20,9 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         consistency_relative=0.01, save_point_cloud=False, evaluate_3d_density=None, evaluate_3d_voxel=None, groundtruth_mesh=None,
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, evaluate_3d_align_plane=False,
         evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, point_mesh_voxel=None, point_mesh_radius=None,
-        point_mesh_neighbours=32, point_mesh_min_neighbours=3, simplify_mesh_voxel=None, simplify_mesh_average=False,
+        point_mesh_neighbours=32, point_mesh_min_neighbours=3,
+        sparse_volume=False, sparse_volume_bricks=65536,      # (here, not last: the places of the parameters behind them are pinned by tests)
+        simplify_mesh_voxel=None, simplify_mesh_average=False,
         smooth_mesh_iterations=None, smooth_mesh_laplacian=False, smooth_mesh_lambda=None, smooth_mesh_mu=None, smooth_mesh_fixed_boundary=False,
         groundtruth_transform=None, point_normals_neighbours=None,
         point_normals_max_distance=None, clean_points_neighbours=None, clean_points_ratio=2.0, clean_points_max_distance=None,
@@ -138,7 +140,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     marching cubes, without the crossings at the edge of the band around the points) and written ADDITIONALLY as
     ``<mesh name>_pointcloud_mesh.ply`` (``TSDFFusion.meshwrite``; normals and colours are those of the nearest point); with
     ``clean_mesh_*`` that mesh goes through the same component filter.  Every other file is what it is without these flags, byte for
-    byte."""
+    byte.
+
+    ``sparse_volume`` with ``sparse_volume_bricks`` (the pool's capacity in bricks of 8 x 8 x 8 voxels): the system's predictions are fused
+    into a ``SparseTSDFVolume`` on the lattice that starts at the volume bounds' lower corner, which allocates the bricks the predictions
+    touch, and then made dense (``SparseTSDFVolume.dense``) over the allocated bricks; frames before a brick's birth are not applied to it
+    -- the one stated difference from the dense volume, inherent to every hashed volume.  The ground-truth side and every later stage are
+    what they are without the flag; the system's files are written under ``<system_name>+sparse`` (before the other suffixes)."""
     settings = _settings(locals())            # (the first statement: locals() is the arguments and nothing else) every refusal without a file
     scene = _load_scene(settings)
     keyframe_images, keyframe_predictions = _load_keyframes(settings, scene)
@@ -193,6 +201,8 @@ class Settings:
     clean_points: object               # OutlierFilter of clean_points_*, or None
     point_normals: Optional[tuple]     # (neighbours, max_distance) of point_normals_*, or None
     point_mesh: Optional[tuple]        # (voxel, radius, neighbours, min_neighbours) of point_mesh_*, or None
+    sparse_volume: bool = False        # fuse the system's predictions into a SparseTSDFVolume, then dense()
+    sparse_volume_bricks: int = 65536
 
 
 def _settings(arguments):
@@ -237,7 +247,11 @@ def _settings(arguments):
         raise ValueError("groundtruth_transform moves the mesh of groundtruth_mesh: it needs groundtruth_mesh")
     if a.evaluate_3d_align is not None and not float(a.evaluate_3d_align) > 0.0:
         raise ValueError(f"evaluate_3d_align must be a positive distance, got {a.evaluate_3d_align}")
-    output_name = a.system_name + ("+consistent" if a.filter_consistency else "") + ("+clean" if clean is not None else "") + (
+    if int(a.sparse_volume_bricks) != 65536 and not a.sparse_volume:
+        raise ValueError("sparse_volume_bricks sizes the pool of sparse_volume: it needs sparse_volume")
+    if int(a.sparse_volume_bricks) < 1:
+        raise ValueError(f"sparse_volume_bricks must be at least 1, got {a.sparse_volume_bricks}")
+    output_name = a.system_name + ("+sparse" if a.sparse_volume else "") + ("+consistent" if a.filter_consistency else "") + ("+clean" if clean is not None else "") + (
         "+smooth" if smooth is not None else "") + ("+simple" if simplify is not None else "")
     return Settings(
         reconstruction_folder=a.reconstruction_folder, prediction_folder=a.prediction_folder, data_folder=a.data_folder,
@@ -252,7 +266,8 @@ def _settings(arguments):
         fuse_groundtruth_3d=a.evaluate_3d and a.groundtruth_mesh is None,
         visible_min_views=int(a.evaluate_3d_min_views) if a.evaluate_3d_visible else None,
         align={"align_distance": a.evaluate_3d_align, "align_scale": a.evaluate_3d_align_scale, "align_plane": align_plane},
-        clean=clean, simplify=simplify, smooth=smooth, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh)
+        clean=clean, simplify=simplify, smooth=smooth, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh,
+        sparse_volume=bool(a.sparse_volume), sparse_volume_bricks=int(a.sparse_volume_bricks))
 
 
 def _number(value):
@@ -588,11 +603,41 @@ def _groundtruth_surface(settings, scene, groundtruths, volume_bounds):
 
 def _fuse_system(settings, scene, images, predictions, volume_bounds):
     """Fuses the keyframe predictions and writes the system's meshes (``TSDFFusion.integrate``): ``(the volume, the mesh name)``."""
-    volume = TSDFVolume(volume_bounds, voxel_size=settings.voxel_size, device=settings.device)
     mesh_name = _mesh_name(settings, settings.output_name)
+    if settings.sparse_volume:
+        return _fuse_system_sparse(settings, scene, images, predictions, volume_bounds, mesh_name), mesh_name
+    volume = TSDFVolume(volume_bounds, voxel_size=settings.voxel_size, device=settings.device)
     TSDFFusion.integrate(volume, images, predictions, scene.keyframe_poses, scene.scaled_K, mesh_name, settings.save_progressive,
                          simplify=settings.simplify, smooth=settings.smooth, clean=settings.clean)
     return volume, mesh_name
+
+
+def sparse_volume_for(settings, volume_bounds):
+    """The ``SparseTSDFVolume`` of ``sparse_volume``: its lattice starts at the lower corner of the bounds, so its voxels are those of the
+    dense volumes of the same run; the extent of the bounds is not used."""
+    from dvmvs.tsdf.sparse_volume import SparseTSDFVolume
+    return SparseTSDFVolume(settings.voxel_size, origin=np.asarray(volume_bounds, dtype=np.float64)[:, 0], max_bricks=settings.sparse_volume_bricks,
+                            device=settings.device)
+
+
+def _fuse_system_sparse(settings, scene, images, predictions, volume_bounds, mesh_name):
+    """``_fuse_system`` through a ``SparseTSDFVolume``: every keyframe with weight 1, then ``dense()`` over the allocated bricks (over the
+    bounds when nothing was allocated); the meshes are written as ``TSDFFusion.integrate`` writes them."""
+    sparse = sparse_volume_for(settings, volume_bounds)
+    stages = dict(simplify=settings.simplify, smooth=settings.smooth, clean=settings.clean)
+
+    def dense():
+        return sparse.dense() if sparse.n_bricks else sparse.dense(volume_bounds)
+
+    for i in range(len(images)):
+        print(f"Fusing frame {i + 1}/{len(images)} for {mesh_name}")
+        sparse.integrate(images[i], predictions[i], scene.scaled_K, scene.keyframe_poses[i], obs_weight=1.0)
+        if settings.save_progressive:
+            TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *dense().get_mesh(**stages))
+    volume = dense()
+    print(f"{sparse.n_bricks} bricks of {sparse.max_bricks} allocated; saving mesh to", mesh_name)
+    TSDFFusion.meshwrite(mesh_name + "_complete.ply", *volume.get_mesh(**stages))
+    return volume
 
 
 def _write_point_clouds(settings, mesh_name, products):
@@ -840,6 +885,11 @@ def build_parser():
                         help="remove the connected components of the system's mesh with fewer faces than this; files are written under <system>+clean")
     parser.add_argument("--clean_mesh_largest", action="store_true",
                         help="keep only the largest connected component of the system's mesh (by area), if it passes the two thresholds")
+    parser.add_argument("--sparse_volume", action="store_true",
+                        help="fuse the system's predictions into a brick-hashed volume that allocates what they touch, then make it dense; "
+                             "files are written under <system>+sparse")
+    parser.add_argument("--sparse_volume_bricks", default=65536, type=int,
+                        help="with --sparse_volume: the pool's capacity in bricks of 8 x 8 x 8 voxels")
     return parser
 
 

@@ -1305,6 +1305,69 @@ int dvmvs_implicit_values_fwd(const float* nodes, long long A, const float* poin
 int dvmvs_implicit_trim_fwd(const float* verts, long long V, const int* faces, long long F, const unsigned char* valid, int X, int Y,
                             int Z, unsigned char* keep_vertex, unsigned char* keep_face, dvmvs_stream_t stream);
 
+/*
+ * A TSDF volume without bounds: a hash table of 8 x 8 x 8-voxel bricks over a pool of fixed capacity (ABI 11, later addition;
+ * csrc/sparse_volume.hip, csrc/sparse_grid.h).  The reference project has nothing for this: the definitions are
+ * this project's own, and dvmvs/sparse.py is the host form of the marking.
+ * Lattice.  Voxel v is a signed integer triple at origin + float(v) * voxel_size, evaluated in fp32 as dvmvs_tsdf_integrate evaluates it
+ *   (one multiply, one add, no contraction): voxel v here and voxel v of a dense volume with the same origin see the same floats.  Brick
+ *   b = floor(v / 8) per component, |b| < 2^20, so float(v) is exact.  Key = ((b_x + 2^20 - 1) << 42) | ((b_y + 2^20 - 1) << 21) |
+ *   (b_z + 2^20 - 1), an int64 in [0, 2^63); ascending keys are the bricks in lexicographic (x, y, z) order.  EMPTY = 2^63 - 1 is no brick.
+ * State, all device memory of the caller, never reallocated:
+ *   table_keys [table_slots] int64, EMPTY where free; table_birth [table_slots] int32, 2^31 - 1 where free; table_slots a power of two.
+ *     Where in the table a key sits depends on the schedule; nothing below that is observable does.
+ *   fresh [table_slots] int64, EMPTY everywhere between flushes: the keys a flush inserted, in any order.
+ *   pool_tsdf, pool_weight, pool_color [max_bricks, 512] fp32, initially 1, 0, 0; local index x * 64 + y * 8 + z.
+ *   pool_key [max_bricks] int64, pool_birth [max_bricks] int32: defined for slots < status[0].
+ *   status [8] int64, zero at first: [0] bricks allocated (n_bricks <= max_bricks), [1] bricks dropped because the pool was full,
+ *     [2] marks dropped because a probe saw the whole table without finding the key or a free slot, [3] pixels that marked nothing
+ *     because a sample left |b| < 2^20, was not finite, or spanned more than 4 bricks on an axis, [4] keys inserted by the flush in
+ *     progress (0 between flushes), [5..7] zero.
+ * A flush of the frames numbered first_frame .. first_frame + n_frames - 1 (the volume counts the frames it is given from 0) is
+ *   dvmvs_sparse_mark; a sort of fresh into sorted [table_slots] (ascending, by any device sort); dvmvs_sparse_assign;
+ *   dvmvs_sparse_integrate, on one stream.  No entry reads anything on the host.
+ * dvmvs_sparse_mark: depth [n,h,w], cam_intr [n,3,3], camera-to-world cam_pose [n,4,4] fp32.  One pixel per lane.  A depth > max_depth
+ *   counts as 0; a depth that is zero, negative or not finite marks nothing.  Every other pixel marks exactly the bricks of
+ *   dvmvs/sparse.py::mark_bricks, whose fp32 operations, in its order, the kernel repeats (correctly rounded +, -, *, /, sqrt, floor,
+ *   ceil; no contraction): samples of the pixel's ray from max(d - trunc, 0) to d + trunc, at most 2 voxels apart (at most 16 intervals;
+ *   longer bands are sampled more coarsely with the margin growing to match), each marking the bricks that the box sample +- m meets,
+ *   m = 0.501953125 (z + delta / 2) sqrt(1/fx^2 + 1/fy^2) + (delta / 2) sqrt(1 + a^2 + b^2) + slack (derivation in the kernel's header
+ *   comment).  A marked brick that is not in the table is inserted (compare-and-swap after a read); its birth becomes the smallest frame
+ *   number that marks it (integer atomicMin).  EVERY PROBE LOOP IS BOUNDED BY table_slots; a mark that finds no slot is counted in
+ *   status[2] and dropped.
+ * dvmvs_sparse_assign: rank r of the non-EMPTY keys of sorted gets pool slot status[0] + r, its key and its birth; ranks at or beyond
+ *   max_bricks are dropped and counted in status[1] (their keys stay in the table, so they are never offered again).  Then status[0] is
+ *   advanced, status[4] zeroed and fresh refilled with EMPTY.  The pool's layout is therefore deterministic: by flush, ascending key inside.
+ * dvmvs_sparse_integrate: one workgroup per pool slot (max_bricks workgroups; those of slots >= status[0], read on the device, return at
+ *   once).  A brick's voxels receive, for each frame g = first_frame + f in index order with g >= birth, the per-voxel statements of
+ *   dvmvs_tsdf_integrate on that frame after depth > max_depth -> 0, in registers, one load and one store per voxel: the bits of the dense
+ *   kernel on that brick under the birth rule, free-space updates (dist = 1) included.  Frames before a brick's birth are not applied --
+ *   the one stated difference from the dense volume.  Because birth is a property of the frame numbers, the result does not depend on how
+ *   frames are batched into flushes.  Colour as in dvmvs_tsdf_integrate_frames: exactly one of rgb_u8 [n,h,w,3] and folded [n,h,w];
+ *   obs_weight_host: n floats on the host.
+ * dvmvs_sparse_gather: copies the bricks of slots < n_bricks (a host number: the caller has read status[0]) that lie inside the box of
+ *   bricks_x x bricks_y x bricks_z bricks from brick (first_x, first_y, first_z) to their place in dense [8 bricks_x, 8 bricks_y,
+ *   8 bricks_z] arrays (z fastest); bricks outside the box are skipped, voxels of no brick are left as the caller filled them.
+ * DVMVS_EINVAL for a null pointer, a table_slots that is no power of two, a count < 1 (n_bricks < 0), first_frame < 0, a voxel_size or
+ *   trunc_margin that is not finite and > 0, an origin that is not finite (mark), a NaN max_depth, both or neither colour form;
+ *   DVMVS_EUNSUPPORTED for 2^31 pixels per frame, frame numbers or pool slots, more than 2^30 table slots.  Nothing is enqueued then.
+ */
+int dvmvs_sparse_mark(long long* table_keys, int* table_birth, long long table_slots, long long* fresh, long long* status,
+                      const float* depth, const float* cam_intr, const float* cam_pose, int n_frames, int im_h, int im_w, float origin_x,
+                      float origin_y, float origin_z, float voxel_size, float trunc_margin, float max_depth, int first_frame,
+                      dvmvs_stream_t stream);
+int dvmvs_sparse_assign(const long long* table_keys, const int* table_birth, long long table_slots, const long long* sorted,
+                        long long* fresh, long long* status, long long* pool_key, int* pool_birth, long long max_bricks,
+                        dvmvs_stream_t stream);
+int dvmvs_sparse_integrate(float* pool_tsdf, float* pool_weight, float* pool_color, const long long* pool_key, const int* pool_birth,
+                           const long long* status, long long max_bricks, float origin_x, float origin_y, float origin_z, float voxel_size,
+                           const float* cam_intr, const float* cam_pose, const unsigned char* rgb_u8, const float* folded,
+                           const float* depth, int n_frames, int im_h, int im_w, float trunc_margin, const float* obs_weight_host,
+                           float max_depth, int first_frame, dvmvs_stream_t stream);
+int dvmvs_sparse_gather(const float* pool_tsdf, const float* pool_weight, const float* pool_color, const long long* pool_key,
+                        long long n_bricks, float* tsdf_vol, float* weight_vol, float* color_vol, int bricks_x, int bricks_y, int bricks_z,
+                        int first_x, int first_y, int first_z, dvmvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
