@@ -196,6 +196,11 @@ SIGNATURES = {
                                         ctypes.c_float, _c_int, _c_stream]),
     "dvmvs_sparse_gather": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_fp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                      _c_int, _c_stream]),
+    "dvmvs_sparse_neighbours": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_stream]),
+    "dvmvs_sparse_extract_count": (_c_int, [_c_fp, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_stream]),
+    "dvmvs_sparse_extract_scan": (_c_int, [_c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_stream]),
+    "dvmvs_sparse_extract_emit": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -242,6 +247,9 @@ ADDED_WITHIN_ABI_MESH_SMOOTH = ("dvmvs_mesh_smooth_workspace_bytes", "dvmvs_mesh
                                 "dvmvs_mesh_smooth_rows_export", "dvmvs_mesh_smooth_steps", "dvmvs_mesh_smooth_normals")
 # ... and the eighteenth (a TSDF volume without bounds: a hash table of bricks over a pool)
 ADDED_WITHIN_ABI_SPARSE_VOLUME = ("dvmvs_sparse_mark", "dvmvs_sparse_assign", "dvmvs_sparse_integrate", "dvmvs_sparse_gather")
+# ... and the nineteenth (marching cubes straight from the pool of the sparse volume)
+ADDED_WITHIN_ABI_SPARSE_EXTRACT = ("dvmvs_sparse_neighbours", "dvmvs_sparse_extract_count", "dvmvs_sparse_extract_scan",
+                                   "dvmvs_sparse_extract_emit")
 
 _lib = None
 _lock = threading.Lock()
@@ -264,7 +272,8 @@ def lib():
                  + ADDED_WITHIN_ABI_NEAREST + ADDED_WITHIN_ABI_CONSISTENCY + ADDED_WITHIN_ABI_SURFACE_SAMPLE + ADDED_WITHIN_ABI_MESH_RASTER
                  + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE + ADDED_WITHIN_ABI_MESH_COMPONENTS
                  + ADDED_WITHIN_ABI_POINT_NEIGHBOURS + ADDED_WITHIN_ABI_POINT_NORMALS + ADDED_WITHIN_ABI_REGISTRATION_PLANE
-                 + ADDED_WITHIN_ABI_IMPLICIT + ADDED_WITHIN_ABI_MESH_SIMPLIFY + ADDED_WITHIN_ABI_MESH_SMOOTH + ADDED_WITHIN_ABI_SPARSE_VOLUME)
+                 + ADDED_WITHIN_ABI_IMPLICIT + ADDED_WITHIN_ABI_MESH_SIMPLIFY + ADDED_WITHIN_ABI_MESH_SMOOTH + ADDED_WITHIN_ABI_SPARSE_VOLUME
+                 + ADDED_WITHIN_ABI_SPARSE_EXTRACT)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

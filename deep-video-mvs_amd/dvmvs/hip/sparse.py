@@ -1,6 +1,8 @@
 """The sparse TSDF volume's entries on the device (csrc/sparse_volume.hip; contract in include/dvmvs_hip.h): the
 state of a brick-hashed volume and the four steps of a flush -- mark, sort, assign, integrate -- plus the gather of ``dense()``.  Plain
-functions over the C ABI and the ops package's launch plumbing; ``dvmvs.tsdf.SparseTSDFVolume`` is the class that users see."""
+functions over the C ABI and the ops package's launch plumbing; ``dvmvs.tsdf.SparseTSDFVolume`` is the class that users see.  Below them,
+marching cubes straight from the pool (csrc/sparse_extract.hip): ``sparse_neighbours`` and ``sparse_extract`` with
+the steps it is made of."""
 import torch
 
 from dvmvs.hip import _capi
@@ -40,6 +42,7 @@ class SparseState:
         self.tsdf = torch.ones((max_bricks, BRICK_VOXELS), dtype=torch.float32, device=dev)
         self.weight = torch.zeros((max_bricks, BRICK_VOXELS), dtype=torch.float32, device=dev)
         self.color = torch.zeros((max_bricks, BRICK_VOXELS), dtype=torch.float32, device=dev)
+        self.device = self.tsdf.device      # with its index ("cuda" -> "cuda:0"): what a tensor's ``.device`` compares equal to
 
 
 def sparse_mark(state, depth, cam_intr, cam_pose, origin, voxel_size, trunc_margin, max_depth, first_frame):
@@ -99,3 +102,88 @@ def sparse_gather(state, n_bricks, tsdf, weight, color, first_brick):
         raise ValueError(f"dvmvs::{name}: {n_bricks} bricks in a pool of {state.max_bricks}")
     launch("dvmvs_sparse_gather", state.device, ptr(state.tsdf), ptr(state.weight), ptr(state.color), ptr(state.pool_key), n_bricks, ptr(tsdf),
            ptr(weight), ptr(color), X // BRICK, Y // BRICK, Z // BRICK, int(first_brick[0]), int(first_brick[1]), int(first_brick[2]))
+
+
+EXTRACT_ROW = 27          # neighbour entries per brick: (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)
+EXTRACT_CELLS = 729       # voxels a brick can handle: local coordinates -1 .. 7 per axis
+
+
+def sparse_neighbours(state):
+    """The neighbour table of the allocated bricks (``dvmvs_sparse_neighbours``): int32 [max_bricks, 27] on the
+    device, row ``slot`` defined for slots < n_bricks, entry ``(dx + 1) * 9 + (dy + 1) * 3 + (dz + 1)`` = the pool slot of brick b + d or
+    -1.  Reads ``status`` and ``pool_key`` only -- not the hash table: the keys of the slots < n_bricks (compared on the device) are sorted
+    with ``torch.sort``, every other slot counting as the empty key, and each neighbour is found by a bounded binary search.  No host
+    read.  The table holds until the next flush; ``SparseTSDFVolume`` caches it."""
+    dev = state.device
+    with torch.cuda.device(dev):
+        slots = torch.arange(state.max_bricks, dtype=torch.int64, device=dev)
+        keys = torch.where(slots < state.status[STATUS_BRICKS], state.pool_key, torch.full_like(state.pool_key, EMPTY_KEY))
+        ordered, index = torch.sort(keys)
+    neighbour = torch.empty((state.max_bricks, EXTRACT_ROW), dtype=torch.int32, device=dev)
+    launch("dvmvs_sparse_neighbours", dev, ptr(state.pool_key), ptr(ordered), ptr(index), ptr(state.status), state.max_bricks, ptr(neighbour))
+    return neighbour
+
+
+def sparse_extract_count(state, neighbour, counts=None):
+    """Step 2 of an extraction (``dvmvs_sparse_extract_count``): int32 [max_bricks, 2], the owned crossing edges and the triangles of
+    the voxels each brick handles (rows of slots >= n_bricks are not written)."""
+    name = "sparse_extract_count"
+    check_tensors(name, neighbour, dtype=torch.int32, label="neighbour", shape=(state.max_bricks, EXTRACT_ROW), device=state.device, contiguous=True)
+    if counts is None:
+        counts = torch.empty((state.max_bricks, 2), dtype=torch.int32, device=state.device)
+    check_tensors(name, counts, dtype=torch.int32, label="counts", shape=(state.max_bricks, 2), device=state.device, contiguous=True)
+    launch("dvmvs_sparse_extract_count", state.device, ptr(state.tsdf), ptr(neighbour), ptr(state.status), state.max_bricks, ptr(counts))
+    return counts
+
+
+def sparse_extract_scan(state, counts):
+    """Step 3 (``dvmvs_sparse_extract_scan``): ``(offsets int64 [max_bricks, 2], summary int64 [5])`` on the device; summary =
+    (n_bricks, bricks dropped by the pool, marks dropped by the table, V, F)."""
+    check_tensors("sparse_extract_scan", counts, dtype=torch.int32, label="counts", shape=(state.max_bricks, 2), device=state.device, contiguous=True)
+    offsets = torch.empty((state.max_bricks, 2), dtype=torch.int64, device=state.device)
+    summary = torch.empty(5, dtype=torch.int64, device=state.device)
+    launch("dvmvs_sparse_extract_scan", state.device, ptr(counts), ptr(state.status), state.max_bricks, ptr(offsets), ptr(summary))
+    return offsets, summary
+
+
+def sparse_extract_emit(state, neighbour, offsets, n_bricks, V, F, origin, voxel_size, colour=True):
+    """Step 4 (``dvmvs_sparse_extract_emit``) with the numbers of the summary: ``(verts [V,3] float32, faces [F,3] int32, normals [V,3]
+    float32, colours [V,3] uint8 or None)``.  The workspace is 729 int32 per ALLOCATED brick."""
+    name = "sparse_extract_emit"
+    dev = state.device
+    n_bricks, V, F = int(n_bricks), int(V), int(F)
+    if not 0 <= n_bricks <= state.max_bricks:
+        raise ValueError(f"dvmvs::{name}: {n_bricks} bricks in a pool of {state.max_bricks}")
+    if V >= 1 << 31 or F >= 1 << 31:
+        raise RuntimeError(f"dvmvs::{name}: {V} vertices and {F} faces do not fit int32 indices")
+    check_tensors(name, neighbour, dtype=torch.int32, label="neighbour", shape=(state.max_bricks, EXTRACT_ROW), device=dev, contiguous=True)
+    check_tensors(name, offsets, dtype=torch.int64, label="offsets", shape=(state.max_bricks, 2), device=dev, contiguous=True)
+    verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    normals = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    colours = torch.empty((V, 3), dtype=torch.uint8, device=dev) if colour else None
+    if n_bricks and (V or F):
+        origin = [float(o) for o in origin]
+        vertex_base = torch.empty((n_bricks, EXTRACT_CELLS), dtype=torch.int32, device=dev)
+        launch("dvmvs_sparse_extract_emit", dev, ptr(state.tsdf), ptr(state.color) if colour else None, ptr(state.pool_key), ptr(neighbour),
+               ptr(offsets), n_bricks, origin[0], origin[1], origin[2], float(voxel_size), ptr(vertex_base), ptr(verts), ptr(normals),
+               opt_ptr(colours), ptr(faces), V, F)
+    return verts, faces, normals, colours
+
+
+def sparse_extract(state, origin, voxel_size, colour=True, neighbour=None, allow_overflow=False):
+    """Marching cubes over the allocated bricks, reading only the pool (csrc/sparse_extract.hip; definition in include/dvmvs_hip.h and
+    DESIGN.md section 4.8s): ``(verts [V,3] float32, faces [F,3] int32, normals [V,3] float32, colours [V,3] uint8 or None)`` device
+    tensors, the mesh that ``marching_cubes`` gives at level 0 on the unbounded volume whose voxels are the allocated bricks' and
+    (1, 0, 0) elsewhere.  ``neighbour``: the table of ``sparse_neighbours`` for the state as it is (built when None).  ONE host read: the
+    summary (n_bricks, dropped counts, V, F).  ``RuntimeError`` when bricks or marks were dropped, unless ``allow_overflow``.  No brick:
+    V = F = 0 with typed empty tensors."""
+    if neighbour is None:
+        neighbour = sparse_neighbours(state)
+    counts = sparse_extract_count(state, neighbour)
+    offsets, summary = sparse_extract_scan(state, counts)
+    n_bricks, dropped_pool, dropped_table, V, F = (int(x) for x in summary.cpu())      # the one host read
+    if (dropped_pool or dropped_table) and not allow_overflow:
+        raise RuntimeError(f"sparse_extract: {dropped_pool} bricks did not fit the pool of {state.max_bricks} and {dropped_table} marks found "
+                           f"no table slot: the volume is incomplete (a larger max_bricks / table_slots, or allow_overflow=True)")
+    return sparse_extract_emit(state, neighbour, offsets, n_bricks, V, F, origin, voxel_size, colour=colour)

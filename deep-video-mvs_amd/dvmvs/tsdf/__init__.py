@@ -18,7 +18,7 @@ The modules, each importing only those before it: ``dvmvs.hip.volume`` (the two 
 integration), ``mesh_views`` (``render_mesh``, ``visible_mesh``, the camera tensors), ``volume`` (``TSDFVolume``, ``fold_color``), ``ply``
 (the PLY reader and writers), ``scoring`` (the work of ``TSDFVolume.score_against``, which that method imports when it is called),
 ``sparse_volume`` (``SparseTSDFVolume``, the volume that needs no bounds: a hash table of bricks over a pool; ``dense()`` gives a
-``TSDFVolume``; ``dvmvs.tsdf.SparseTSDFVolume`` resolves to it on first use, so importing the package loads what it always loaded),
+``TSDFVolume``, ``mesh_tensors`` / ``get_mesh`` extract the surface straight from the pool; ``dvmvs.tsdf.SparseTSDFVolume`` resolves to it on first use, so importing the package loads what it always loaded),
 ``fusion`` (``TSDFFusion``, ``LiveFusion``) and ``program`` (``run``, its stages and the parser).
 """
 from dvmvs.hip.volume import marching_cubes

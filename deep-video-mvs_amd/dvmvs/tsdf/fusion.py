@@ -115,7 +115,8 @@ class LiveFusion:
     from ``sparse_origin`` and a pool of ``max_bricks`` bricks of 8 x 8 x 8 voxels) instead, which allocates what the frames touch; frames
     before a brick's birth are not applied to it -- the one stated difference from the dense volume, inherent to every hashed volume.
     ``volume`` is then ``sparse.dense()``, a ``TSDFVolume`` over the allocated bricks, made when it is asked for (one host read) and kept
-    until the next ``add``.  The consistency filter works on the depth maps before fusion and is the same in both modes.  With bounds
+    until the next ``add``; ``get_mesh`` / ``mesh_tensors`` take the surface straight from the sparse volume's pool, without ``dense()``
+    (with bounds given: from the dense volume).  The consistency filter works on the depth maps before fusion and is the same in both modes.  With bounds
     given nothing differs from what it was: ``sparse`` is None."""
 
     def __init__(self, vol_bnds, voxel_size=0.025, max_depth=5.0, batch=8, device="cuda", min_consistent_views=0, consistency_sources=4,
@@ -224,3 +225,19 @@ class LiveFusion:
         if self._volume is None:
             self._volume = self.sparse.dense()
         return self._volume
+
+    def _surface_source(self):
+        """What the mesh is extracted from, after a flush: the sparse volume itself where there is one (from its pool, no ``dense()``),
+        else the dense volume."""
+        self.flush()
+        return self.sparse if self.sparse is not None else self._volume
+
+    def get_mesh(self, **stages):
+        """``get_mesh`` of the reconstruction so far (``clean=`` / ``smooth=`` / ``simplify=`` as ``TSDFVolume.get_mesh`` takes them), as
+        numpy arrays.  Without bounds the surface comes straight from the sparse volume's pool (``SparseTSDFVolume.get_mesh``): ``volume``
+        is not made."""
+        return self._surface_source().get_mesh(**stages)
+
+    def mesh_tensors(self, **stages):
+        """``(verts, faces)`` device tensors of the reconstruction so far; as ``get_mesh``."""
+        return self._surface_source().mesh_tensors(**stages)

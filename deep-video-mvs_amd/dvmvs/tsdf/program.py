@@ -21,7 +21,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, evaluate_3d_align_plane=False,
         evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, point_mesh_voxel=None, point_mesh_radius=None,
         point_mesh_neighbours=32, point_mesh_min_neighbours=3,
-        sparse_volume=False, sparse_volume_bricks=65536,      # (here, not last: the places of the parameters behind them are pinned by tests)
+        sparse_volume=False, sparse_volume_bricks=65536, sparse_volume_extract=False,      # (here, not last: the places of the parameters behind them are pinned by tests)
         simplify_mesh_voxel=None, simplify_mesh_average=False,
         smooth_mesh_iterations=None, smooth_mesh_laplacian=False, smooth_mesh_lambda=None, smooth_mesh_mu=None, smooth_mesh_fixed_boundary=False,
         groundtruth_transform=None, point_normals_neighbours=None,
@@ -146,7 +146,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     into a ``SparseTSDFVolume`` on the lattice that starts at the volume bounds' lower corner, which allocates the bricks the predictions
     touch, and then made dense (``SparseTSDFVolume.dense``) over the allocated bricks; frames before a brick's birth are not applied to it
     -- the one stated difference from the dense volume, inherent to every hashed volume.  The ground-truth side and every later stage are
-    what they are without the flag; the system's files are written under ``<system_name>+sparse`` (before the other suffixes)."""
+    what they are without the flag; the system's files are written under ``<system_name>+sparse`` (before the other suffixes).
+
+    ``sparse_volume_extract`` (needs ``sparse_volume``): the system's mesh files are written straight from the sparse volume's pool
+    (``SparseTSDFVolume.get_mesh``: extract -> clean -> smooth -> simplify on device tensors) and ``evaluate_3d`` scores with the sparse
+    volume's ``score_against``; ``dense()`` is called only when another requested stage needs a ``TSDFVolume`` (``render_keyframes``).  The
+    surface is the dense one's as a set of welded triangles, listed by brick instead of by voxel; the output folder stays
+    ``<system_name>+sparse``."""
     settings = _settings(locals())            # (the first statement: locals() is the arguments and nothing else) every refusal without a file
     scene = _load_scene(settings)
     keyframe_images, keyframe_predictions = _load_keyframes(settings, scene)
@@ -159,7 +165,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     if settings.evaluate_3d:
         _evaluate_3d(settings, scene, volume, groundtruth_surface, mesh_name)
     if settings.render_keyframes:
-        _render_keyframes(settings, scene, volume)
+        _render_keyframes(settings, scene, _renderable(volume, volume_bounds))
 
 
 # ---- settings: run's arguments, checked ---------------------------------------------------------------------------------------------------
@@ -203,6 +209,7 @@ class Settings:
     point_mesh: Optional[tuple]        # (voxel, radius, neighbours, min_neighbours) of point_mesh_*, or None
     sparse_volume: bool = False        # fuse the system's predictions into a SparseTSDFVolume, then dense()
     sparse_volume_bricks: int = 65536
+    sparse_volume_extract: bool = False   # the system's meshes and score straight from the sparse volume's pool; dense() only for rendering
 
 
 def _settings(arguments):
@@ -251,6 +258,8 @@ def _settings(arguments):
         raise ValueError("sparse_volume_bricks sizes the pool of sparse_volume: it needs sparse_volume")
     if int(a.sparse_volume_bricks) < 1:
         raise ValueError(f"sparse_volume_bricks must be at least 1, got {a.sparse_volume_bricks}")
+    if a.sparse_volume_extract and not a.sparse_volume:
+        raise ValueError("sparse_volume_extract meshes the pool of sparse_volume: it needs sparse_volume")
     output_name = a.system_name + ("+sparse" if a.sparse_volume else "") + ("+consistent" if a.filter_consistency else "") + ("+clean" if clean is not None else "") + (
         "+smooth" if smooth is not None else "") + ("+simple" if simplify is not None else "")
     return Settings(
@@ -267,7 +276,8 @@ def _settings(arguments):
         visible_min_views=int(a.evaluate_3d_min_views) if a.evaluate_3d_visible else None,
         align={"align_distance": a.evaluate_3d_align, "align_scale": a.evaluate_3d_align_scale, "align_plane": align_plane},
         clean=clean, simplify=simplify, smooth=smooth, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh,
-        sparse_volume=bool(a.sparse_volume), sparse_volume_bricks=int(a.sparse_volume_bricks))
+        sparse_volume=bool(a.sparse_volume), sparse_volume_bricks=int(a.sparse_volume_bricks),
+        sparse_volume_extract=bool(a.sparse_volume_extract))
 
 
 def _number(value):
@@ -622,22 +632,30 @@ def sparse_volume_for(settings, volume_bounds):
 
 def _fuse_system_sparse(settings, scene, images, predictions, volume_bounds, mesh_name):
     """``_fuse_system`` through a ``SparseTSDFVolume``: every keyframe with weight 1, then ``dense()`` over the allocated bricks (over the
-    bounds when nothing was allocated); the meshes are written as ``TSDFFusion.integrate`` writes them."""
+    bounds when nothing was allocated); the meshes are written as ``TSDFFusion.integrate`` writes them.  With ``sparse_volume_extract``
+    the meshes come from the pool, nothing is made dense, and the sparse volume itself is returned."""
     sparse = sparse_volume_for(settings, volume_bounds)
     stages = dict(simplify=settings.simplify, smooth=settings.smooth, clean=settings.clean)
 
-    def dense():
-        return sparse.dense() if sparse.n_bricks else sparse.dense(volume_bounds)
+    def meshed():      # what the meshes are taken from
+        return sparse if settings.sparse_volume_extract else _renderable(sparse, volume_bounds)
 
     for i in range(len(images)):
         print(f"Fusing frame {i + 1}/{len(images)} for {mesh_name}")
         sparse.integrate(images[i], predictions[i], scene.scaled_K, scene.keyframe_poses[i], obs_weight=1.0)
         if settings.save_progressive:
-            TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *dense().get_mesh(**stages))
-    volume = dense()
+            TSDFFusion.meshwrite(f"{mesh_name}_frame_{i:05d}.ply", *meshed().get_mesh(**stages))
+    volume = meshed()
     print(f"{sparse.n_bricks} bricks of {sparse.max_bricks} allocated; saving mesh to", mesh_name)
     TSDFFusion.meshwrite(mesh_name + "_complete.ply", *volume.get_mesh(**stages))
     return volume
+
+
+def _renderable(volume, volume_bounds):
+    """``volume`` as a ``TSDFVolume``: a ``SparseTSDFVolume`` made dense over its allocated bricks (over the bounds when it has none)."""
+    if isinstance(volume, TSDFVolume):
+        return volume
+    return volume.dense() if volume.n_bricks else volume.dense(volume_bounds)
 
 
 def _write_point_clouds(settings, mesh_name, products):
@@ -890,6 +908,9 @@ def build_parser():
                              "files are written under <system>+sparse")
     parser.add_argument("--sparse_volume_bricks", default=65536, type=int,
                         help="with --sparse_volume: the pool's capacity in bricks of 8 x 8 x 8 voxels")
+    parser.add_argument("--sparse_volume_extract", action="store_true",
+                        help="with --sparse_volume: write the system's meshes and score them straight from the allocated bricks (marching cubes "
+                             "over the pool); the volume is made dense only for --render_keyframes")
     return parser
 
 

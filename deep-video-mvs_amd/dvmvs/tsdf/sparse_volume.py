@@ -1,13 +1,14 @@
 """``SparseTSDFVolume``: a TSDF volume that needs no bounds.  Space is an unbounded lattice of 8 x 8 x 8-voxel
 bricks, a hash table on the device maps brick coordinates to existence, a pool of fixed capacity holds the voxels of the bricks that the
-frames' truncation bands touched, and only those are updated.  ``dense()`` hands the result to everything that takes a ``TSDFVolume``."""
+frames' truncation bands touched, and only those are updated.  ``dense()`` hands the result to everything that takes a ``TSDFVolume``;
+``mesh_tensors`` / ``get_mesh`` and what builds on them extract the surface straight from the pool."""
 import numpy as np
 import torch
 
 from dvmvs.hip import sparse as hip_sparse
 from dvmvs.sparse import BRICK, unpack_keys
 from dvmvs.tsdf.mesh_views import camera_tensors
-from dvmvs.tsdf.volume import TSDFVolume, fold_color
+from dvmvs.tsdf.volume import TSDFVolume, finish_mesh, fold_color, mesh_stages
 
 
 class SparseTSDFVolume:
@@ -42,6 +43,7 @@ class SparseTSDFVolume:
         self._state = hip_sparse.SparseState(max_bricks, table_slots, self.device)
         self.device = self._state.tsdf.device
         self.frames = 0                   # frames given so far: the number of the next frame
+        self._neighbour = None            # neighbour table of the extraction: describes which bricks exist, so integrate_frames drops it
 
     voxel_size = property(lambda self: self._voxel_size)
     origin = property(lambda self: self._origin.copy())
@@ -90,6 +92,7 @@ class SparseTSDFVolume:
             raise ValueError("max_depth is NaN")
         first, state = self.frames, self._state
         self.frames += n                  # (before the calls: a failed call may have been enqueued)
+        self._neighbour = None
         hip_sparse.sparse_mark(state, depth, K, P, self._origin, self._voxel_size, self._trunc_margin, max_depth, first)
         hip_sparse.sparse_assign(state)
         hip_sparse.sparse_integrate(state, depth, K, P, rgb, folded, self._origin, self._voxel_size, self._trunc_margin, weights, max_depth,
@@ -180,3 +183,63 @@ class SparseTSDFVolume:
             raise RuntimeError(f"SparseTSDFVolume.dense: a box of {tuple(int(c) for c in count)} bricks became a volume of {tuple(volume.vol_dim)} voxels")
         hip_sparse.sparse_gather(state, n, volume._tsdf, volume._weight, volume._color, first)
         return volume
+
+    def neighbours(self):
+        """The neighbour table of the allocated bricks (``dvmvs.hip.sparse.sparse_neighbours``; int32 [max_bricks, 27] on the device),
+        built on first use and kept until the next ``integrate_frames``.  No host read."""
+        if self._neighbour is None:
+            self._neighbour = hip_sparse.sparse_neighbours(self._state)
+        return self._neighbour
+
+    def _extract(self, color, clean, allow_overflow=False):
+        """Marching cubes over the allocated bricks, reading only the pool (``dvmvs.hip.sparse.sparse_extract``), then ``clean`` as
+        ``TSDFVolume._extract`` applies it."""
+        mesh = hip_sparse.sparse_extract(self._state, self._origin, self._voxel_size, colour=color, neighbour=self.neighbours(),
+                                         allow_overflow=allow_overflow)
+        return finish_mesh(mesh, None, None, clean)
+
+    def _surface(self, color, simplify, smooth, clean, allow_overflow=False):
+        """extract -> clean -> smooth -> simplify on device tensors, the stages of ``TSDFVolume._surface`` (``finish_mesh``)."""
+        simplify, smooth, clean = mesh_stages(simplify, smooth, clean)
+        return finish_mesh(self._extract(color, clean, allow_overflow), simplify, smooth, None)
+
+    def get_mesh(self, simplify=None, smooth=None, clean=None, allow_overflow=False):
+        """``TSDFVolume.get_mesh`` of this volume, without a dense copy: (verts [V,3] float32 in world units, faces [F,3] int32, normals
+        [V,3] float32, colours [V,3] uint8 RGB) as numpy arrays.  The surface is that of the unbounded volume whose voxels are the
+        allocated bricks' and (1, 0, 0) elsewhere -- the mesh of ``dense(box).get_mesh()`` for any box that holds the allocated bricks
+        with a brick of margin, as a set of welded triangles; the normals' gradient is the central difference everywhere; the order is by
+        handling brick.  ``clean`` / ``smooth`` / ``simplify`` as there.  One host read (brick, overflow, vertex
+        and face counts together) plus those of the stages.  ``RuntimeError`` when bricks were dropped (``overflow``), unless
+        ``allow_overflow``; no brick gives V = F = 0."""
+        verts, faces, norms, colors = self._surface(True, simplify, smooth, clean, allow_overflow)
+        return verts.cpu().numpy(), faces.cpu().numpy(), norms.cpu().numpy(), colors.cpu().numpy()
+
+    def get_point_cloud(self):
+        """[N,6] float32: the mesh's vertices (xyz, world units) followed by their colour (rgb), as ``TSDFVolume.get_point_cloud``."""
+        verts, _, _, colors = self.get_mesh()
+        return np.hstack([verts, colors])
+
+    def vertices(self, simplify=None, smooth=None, clean=None, allow_overflow=False):
+        """The vertices of the zero iso-surface as a float32 [V,3] DEVICE tensor (``TSDFVolume.vertices``)."""
+        return self._surface(False, simplify, smooth, clean, allow_overflow)[0]
+
+    def mesh_tensors(self, simplify=None, smooth=None, clean=None, allow_overflow=False):
+        """``(verts float32 [V,3], faces int32 [F,3])`` of the zero iso-surface as DEVICE tensors (``TSDFVolume.mesh_tensors``), extracted
+        from the pool."""
+        return self._surface(False, simplify, smooth, clean, allow_overflow)[:2]
+
+    def surface_points(self, sample_density=None, voxel=None, simplify=None, smooth=None, clean=None):
+        """The point set the 3-D metrics take from this volume's surface, a float32 [N,3] DEVICE tensor (``TSDFVolume.surface_points``)."""
+        from dvmvs.errors import prepare_points_device
+        verts, faces = self.mesh_tensors(simplify=simplify, smooth=smooth, clean=clean)
+        return prepare_points_device(verts, faces, sample_density, voxel)
+
+    def score_against(self, reference, threshold=0.05, return_sizes=False, sample_density=None, voxel=None, visible_from=None, clean=None,
+                      simplify=None, smooth=None, align_plane=False, align_normal_neighbours=20, align_normal_distance=np.inf, align_distance=None,
+                      align_scale=False, return_transform=False):
+        """``TSDFVolume.score_against`` with this volume's surface, extracted from the pool, as the prediction; ``reference`` and every
+        keyword as there.  (As the REFERENCE of another volume's ``score_against``, pass ``mesh_tensors()``.)"""
+        from dvmvs.tsdf.scoring import score_volume
+        return score_volume(self, reference, threshold, return_sizes, sample_density, voxel, visible_from, align_distance, align_scale,
+                            return_transform, clean=clean, align_plane=align_plane, align_normal_neighbours=align_normal_neighbours,
+                            align_normal_distance=align_normal_distance, simplify=simplify, smooth=smooth)[0]

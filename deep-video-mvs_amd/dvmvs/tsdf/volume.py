@@ -34,6 +34,26 @@ def mesh_stages(*stages):
     return tuple(placed.get(name) for name in names)
 
 
+def finish_mesh(mesh, simplify, smooth, clean):
+    """What follows the extraction, on ``mesh`` = ``(verts, faces, normals, colours or None)`` device tensors, whichever volume they come
+    from (``TSDFVolume``, ``SparseTSDFVolume``): with ``clean`` (a ``dvmvs.components.ComponentFilter``) through ``filter_components``,
+    then with ``smooth`` (a ``dvmvs.smooth.SmoothSettings``) through ``smooth_mesh``, then with ``simplify`` (a
+    ``dvmvs.simplify.SimplifySettings``) through ``simplify_mesh``, all on the device.  The stages are taken as given (``mesh_stages``
+    sorts a method's arguments first); a stage that is None is left out."""
+    if clean is not None:
+        from dvmvs.components import filter_components_device
+        mesh = filter_components_device(mesh[0], mesh[1], clean, mesh[2], mesh[3])
+    if smooth is not None:
+        from dvmvs.smooth import smooth_mesh_device, smooth_settings
+        smooth_settings(smooth)
+        mesh = smooth_mesh_device(mesh[0], mesh[1], smooth, mesh[2], mesh[3])
+    if simplify is not None:
+        from dvmvs.simplify import simplify_mesh_device, simplify_settings
+        simplify_settings(simplify)
+        mesh = simplify_mesh_device(mesh[0], mesh[1], simplify, mesh[2], mesh[3])
+    return mesh
+
+
 class TSDFVolume:
     """Voxel volume over ``vol_bnds`` ([[x0, x1], [y0, y1], [z0, z1]] in metres) with ``voxel_size`` edges.  tsdf starts at 1,
     weight and colour at 0; truncation = 5 voxels, as in the reference."""
@@ -151,26 +171,14 @@ class TSDFVolume:
         """``marching_cubes`` of the volume, with ``clean`` (a ``dvmvs.components.ComponentFilter``) through ``filter_components`` on the
         device: the components of the welded mesh that the filter does not keep (floaters) are gone before anything else sees it."""
         mesh = marching_cubes(self._tsdf, 0.0, self._color if color else None, self._vol_origin, self._voxel_size)
-        if clean is not None:
-            from dvmvs.components import filter_components_device
-            mesh = filter_components_device(mesh[0], mesh[1], clean, mesh[2], mesh[3])
-        return mesh
+        return finish_mesh(mesh, None, None, clean)
 
     def _surface(self, color, simplify, smooth, clean):
         """``_extract``; with ``smooth`` (a ``dvmvs.smooth.SmoothSettings``) what it leaves through ``smooth_mesh`` on the device; with
         ``simplify`` (a ``dvmvs.simplify.SimplifySettings``) what that leaves through ``simplify_mesh`` on the device: extract -> clean ->
-        smooth -> simplify.  Without the two, ``_extract`` and nothing else."""
+        smooth -> simplify (``finish_mesh``).  Without the two, ``_extract`` and nothing else."""
         simplify, smooth, clean = mesh_stages(simplify, smooth, clean)
-        mesh = self._extract(color, clean)
-        if smooth is not None:
-            from dvmvs.smooth import smooth_mesh_device, smooth_settings
-            smooth_settings(smooth)
-            mesh = smooth_mesh_device(mesh[0], mesh[1], smooth, mesh[2], mesh[3])
-        if simplify is not None:
-            from dvmvs.simplify import simplify_mesh_device, simplify_settings
-            simplify_settings(simplify)
-            mesh = simplify_mesh_device(mesh[0], mesh[1], simplify, mesh[2], mesh[3])
-        return mesh
+        return finish_mesh(self._extract(color, clean), simplify, smooth, None)
 
     def get_mesh(self, simplify=None, smooth=None, clean=None):
         """(verts [V,3] float32 in world units, faces [F,3] int32, normals [V,3] float32, colours [V,3] uint8 RGB) of the zero

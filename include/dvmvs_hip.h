@@ -77,7 +77,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_mesh_simplify_* and dvmvs_voxel_downsample_runs (simplifying a triangle mesh by vertex clustering with
  * quadric error representatives); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_mesh_smooth_* (smoothing a triangle mesh by the Laplacian and Taubin filters; vertex normals from the
- * faces); no earlier signature changed, the number stays 11 by the same rule. */
+ * faces); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_sparse_neighbours and dvmvs_sparse_extract_* (marching cubes straight from the pool of the sparse TSDF
+ * volume); no earlier signature changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -1367,6 +1369,52 @@ int dvmvs_sparse_integrate(float* pool_tsdf, float* pool_weight, float* pool_col
 int dvmvs_sparse_gather(const float* pool_tsdf, const float* pool_weight, const float* pool_color, const long long* pool_key,
                         long long n_bricks, float* tsdf_vol, float* weight_vol, float* color_vol, int bricks_x, int bricks_y, int bricks_z,
                         int first_x, int first_y, int first_z, dvmvs_stream_t stream);
+
+/*
+ * Marching cubes straight from the pool of the sparse volume (ABI 11, later addition; csrc/sparse_extract.hip,
+ * csrc/sparse_extract_grid.h).  No dense copy is made: the work and the memory follow the allocated bricks.
+ * Definition.  The sparse volume read as an unbounded dense volume: voxel v (|v| < 2^23) holds its brick's pool values when the brick is
+ *   allocated (a slot < status[0]) and (tsdf 1, weight 0, colour 0) otherwise.  The mesh is what dvmvs_marching_cubes_* gives on that
+ *   volume at level 0: inside = value < 0; a grid edge with exactly one inside endpoint carries one vertex, owned by the voxel at its lower
+ *   end; case and triangle tables of csrc/marching_cubes_tables.h, a cube's triangles in table order; one vertex per crossing edge, shared
+ *   by every face around it, across brick borders too.  Cubes and owned edges of voxels in UNALLOCATED bricks next to allocated ones count.
+ *   Vertex on the +axis edge of voxel a, b = a + e_axis (fp32, no contraction, the statements of the dense kernel with the global signed
+ *   index): t = (0 - v_a) / (v_b - v_a); p = float(a_axis) + t on the edge axis, float(a) on the others; position = p * voxel_size +
+ *   origin; normal = g_a + t (g_b - g_a) divided by its length (zero stays zero) with g ALWAYS the central difference
+ *   (v[+1] - v[-1]) * 0.5 per axis (there is no border); colour = the folded colour voxel at rint(p) (0 where unallocated), decoded as
+ *   the dense kernel decodes it.
+ * Inputs read: status, pool_key and the pool arrays; the hash table is not.  The key -> slot map is rebuilt: the caller sorts the keys of
+ *   the slots < status[0] (every other entry of the sort's input being EMPTY) ascending into sorted [max_bricks] with the slots they came
+ *   from in sort_index [max_bricks] (int64), by any device sort.
+ * dvmvs_sparse_neighbours: neighbour [max_bricks, 27] int32; for slots < status[0] (read on the device), entry (dx+1)*9 + (dy+1)*3 + (dz+1)
+ *   is the pool slot of brick b + d, d in {-1,0,1}^3, or -1 (not allocated, or outside |b| <= 2^20 - 1, then without a search).  The
+ *   lookup is a binary search of exactly 32 steps over sorted[0 .. status[0]).  The table describes which bricks exist: it holds until
+ *   the next flush.
+ * Handling.  A voxel of an allocated brick is handled by that brick.  A voxel w of an unallocated brick u is handled by the allocated brick
+ *   of SMALLEST KEY among u + e, e in {0,1}^3 with e_a = 1 only where w's coordinate inside u is 7 on axis a (the bricks its cube touches);
+ *   by nobody when none is allocated.  A brick therefore handles voxels of local coordinates -1 .. 7 per axis: its 9^3 lattice, cell
+ *   (lx+1)*81 + (ly+1)*9 + (lz+1).
+ * dvmvs_sparse_extract_count: one workgroup per pool slot (max_bricks of them; those of slots >= status[0] return at once) stages the
+ *   brick's tsdf with the halo -2 .. 9 per axis from its neighbours into LDS (missing neighbours read 1) and writes the owned crossing
+ *   edges and the triangles of the voxels it handles to counts[2 slot], counts[2 slot + 1] (int32 [2 max_bricks]).
+ * dvmvs_sparse_extract_scan: offsets [2 max_bricks] int64 <- the exclusive prefix sums of counts over the slots < status[0];
+ *   summary [5] int64 <- (status[0], status[1], status[2], V, F).  The caller reads summary: the one host read of an extraction.
+ * dvmvs_sparse_extract_emit: n_bricks, V, F from summary; vertex_base: workspace, int32 [729 n_bricks].  verts [V,3] fp32, normals [V,3]
+ *   fp32, colors [V,3] uint8 RGB (pool_color and colors NULL: no colours), faces [F,3] int32.  ORDER: vertices by (pool slot of the
+ *   handling brick, cell of the owner voxel in its lattice, axis x < y < z); faces by (pool slot of the handling brick, cell of the cube's
+ *   lowest corner, table order).  The same pool state gives the same bytes.  Stores are guarded by V and F.  No atomics.
+ * DVMVS_EINVAL for a null pointer, max_bricks < 1, negative counts; DVMVS_EUNSUPPORTED for 2^31 pool slots, vertices or faces.
+ */
+int dvmvs_sparse_neighbours(const long long* pool_key, const long long* sorted, const long long* sort_index, const long long* status,
+                            long long max_bricks, int* neighbour, dvmvs_stream_t stream);
+int dvmvs_sparse_extract_count(const float* pool_tsdf, const int* neighbour, const long long* status, long long max_bricks, int* counts,
+                               dvmvs_stream_t stream);
+int dvmvs_sparse_extract_scan(const int* counts, const long long* status, long long max_bricks, long long* offsets, long long* summary,
+                              dvmvs_stream_t stream);
+int dvmvs_sparse_extract_emit(const float* pool_tsdf, const float* pool_color, const long long* pool_key, const int* neighbour,
+                              const long long* offsets, long long n_bricks, float origin_x, float origin_y, float origin_z, float voxel_size,
+                              int* vertex_base, float* verts, float* normals, unsigned char* colors, int* faces, long long V, long long F,
+                              dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
