@@ -201,6 +201,12 @@ SIGNATURES = {
     "dvmvs_sparse_extract_scan": (_c_int, [_c_fp, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_stream]),
     "dvmvs_sparse_extract_emit": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                            ctypes.c_float, _c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, ctypes.c_longlong, _c_stream]),
+    "dvmvs_sparse_raycast_index": (_c_int, [_c_fp, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_stream]),
+    "dvmvs_sparse_raycast_flags": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_stream]),
+    "dvmvs_sparse_raycast_fwd": (_c_int, [_c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_longlong, _c_fp, ctypes.c_longlong, _c_fp, _c_fp, _c_int, _c_int,
+                                          _c_int, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_int,
+                                          _c_fp, _c_fp, _c_int, _c_int, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_fp, _c_fp,
+                                          _c_fp, _c_stream]),
 }
 
 # Added to the header without a new ABI number (the number is pinned at 11): a library built before the addition passes the version
@@ -250,6 +256,8 @@ ADDED_WITHIN_ABI_SPARSE_VOLUME = ("dvmvs_sparse_mark", "dvmvs_sparse_assign", "d
 # ... and the nineteenth (marching cubes straight from the pool of the sparse volume)
 ADDED_WITHIN_ABI_SPARSE_EXTRACT = ("dvmvs_sparse_neighbours", "dvmvs_sparse_extract_count", "dvmvs_sparse_extract_scan",
                                    "dvmvs_sparse_extract_emit")
+# ... and the twentieth (ray-casting the sparse volume straight from its pool)
+ADDED_WITHIN_ABI_SPARSE_RAYCAST = ("dvmvs_sparse_raycast_index", "dvmvs_sparse_raycast_flags", "dvmvs_sparse_raycast_fwd")
 
 _lib = None
 _lock = threading.Lock()
@@ -273,7 +281,7 @@ def lib():
                  + ADDED_WITHIN_ABI_REGISTRATION + ADDED_WITHIN_ABI_DIRECT_CONV_SHAPE + ADDED_WITHIN_ABI_MESH_COMPONENTS
                  + ADDED_WITHIN_ABI_POINT_NEIGHBOURS + ADDED_WITHIN_ABI_POINT_NORMALS + ADDED_WITHIN_ABI_REGISTRATION_PLANE
                  + ADDED_WITHIN_ABI_IMPLICIT + ADDED_WITHIN_ABI_MESH_SIMPLIFY + ADDED_WITHIN_ABI_MESH_SMOOTH + ADDED_WITHIN_ABI_SPARSE_VOLUME
-                 + ADDED_WITHIN_ABI_SPARSE_EXTRACT)
+                 + ADDED_WITHIN_ABI_SPARSE_EXTRACT + ADDED_WITHIN_ABI_SPARSE_RAYCAST)
         missing = [name for name in added if not hasattr(handle, name)]
         if missing:
             raise RuntimeError(f"{LIB_PATH} was built before {', '.join(missing)} joined ABI {ABI_VERSION} (the number did not change); "

@@ -2,7 +2,10 @@
 state of a brick-hashed volume and the four steps of a flush -- mark, sort, assign, integrate -- plus the gather of ``dense()``.  Plain
 functions over the C ABI and the ops package's launch plumbing; ``dvmvs.tsdf.SparseTSDFVolume`` is the class that users see.  Below them,
 marching cubes straight from the pool (csrc/sparse_extract.hip): ``sparse_neighbours`` and ``sparse_extract`` with
-the steps it is made of."""
+the steps it is made of; and ray-casting straight from the pool (csrc/sparse_raycast.hip): ``sparse_raycast_index``,
+``sparse_raycast_flags`` and ``sparse_raycast``."""
+import math
+
 import torch
 
 from dvmvs.hip import _capi
@@ -187,3 +190,88 @@ def sparse_extract(state, origin, voxel_size, colour=True, neighbour=None, allow
         raise RuntimeError(f"sparse_extract: {dropped_pool} bricks did not fit the pool of {state.max_bricks} and {dropped_table} marks found "
                            f"no table slot: the volume is incomplete (a larger max_bricks / table_slots, or allow_overflow=True)")
     return sparse_extract_emit(state, neighbour, offsets, n_bricks, V, F, origin, voxel_size, colour=colour)
+
+
+# ---- ray-casting straight from the pool (csrc/sparse_raycast.hip) -------------------------------------------------
+RAYCAST_MAX_STEPS = 1 << 20      # kSrMaxSteps: the box diagonal in steps, floor(|8 count - 1| / step) + 2, must stay below
+
+
+def raycast_index_slots(max_bricks):
+    """Entries of the render index of a pool of ``max_bricks`` bricks: the power of two >= 2 * max_bricks (at most half full)."""
+    return 1 << max(4, (2 * int(max_bricks) - 1).bit_length())
+
+
+def sparse_raycast_index(state):
+    """The render index of the allocated bricks (``dvmvs_sparse_raycast_index``): int64 [slots, 2] on the device, an open-addressing table
+    of (key, value) entries filled from ``pool_key[:n_bricks]`` with ``n_bricks`` read on the device; value = pool slot (the crossing flag
+    joins it in ``sparse_raycast_flags``).  Reads ``status`` and ``pool_key`` only -- not the volume's hash table.  No host read."""
+    slots = raycast_index_slots(state.max_bricks)
+    index = torch.empty((slots, 2), dtype=torch.int64, device=state.device)
+    launch("dvmvs_sparse_raycast_index", state.device, ptr(state.pool_key), ptr(state.status), state.max_bricks, ptr(index), slots)
+    return index
+
+
+def sparse_raycast_flags(state, neighbour, index):
+    """Per-slot crossing flags (``dvmvs_sparse_raycast_flags``): uint8 [max_bricks], 1 where one of the 9^3 corners of the brick's cells has
+    ``weight > 0 and tsdf <= 0``; the same bit enters the brick's value in ``index``, in place.  ``neighbour``: the table of
+    ``sparse_neighbours``; ``index``: that of ``sparse_raycast_index``, both for the state as it is.  No host read."""
+    name = "sparse_raycast_flags"
+    check_tensors(name, neighbour, dtype=torch.int32, label="neighbour", shape=(state.max_bricks, EXTRACT_ROW), device=state.device, contiguous=True)
+    check_tensors(name, index, dtype=torch.int64, label="index", shape=(raycast_index_slots(state.max_bricks), 2), device=state.device,
+                  contiguous=True)
+    flags = torch.zeros((state.max_bricks,), dtype=torch.uint8, device=state.device)
+    launch("dvmvs_sparse_raycast_flags", state.device, ptr(state.tsdf), ptr(state.weight), ptr(state.pool_key), ptr(neighbour), ptr(state.status),
+           state.max_bricks, ptr(index), int(index.shape[0]), ptr(flags))
+    return flags
+
+
+def raycast_steps(count, step):
+    """The longest march through a box of ``count`` bricks per axis, as the C entry computes it: floor(diagonal / step) + 2."""
+    d = [8.0 * int(c) - 1.0 for c in count]
+    return math.floor(math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) / float(step)) + 2.0
+
+
+def sparse_raycast(state, index, flags, neighbour, first_brick, count, origin, voxel_size, cam_intr, cam_pose, height, width, near=0.0,
+                   far=float("inf"), step=1.0, normals=True, colour=True, skip_empty=True):
+    """Renders the sparse volume from N views in one launch, reading only the pool (``dvmvs_sparse_raycast_fwd``): the outputs of
+    ``dvmvs.hip.ops.tsdf_raycast`` on the dense volume over the box of ``count`` bricks per axis from brick ``first_brick``, whose voxel
+    (0, 0, 0) lies at ``origin`` (float32), bit for bit.  ``index``, ``flags``, ``neighbour``: the tables of ``sparse_raycast_index``,
+    ``sparse_raycast_flags`` and ``sparse_neighbours`` for the state as it is.  ``cam_intr`` [N,3,3] and camera-to-world ``cam_pose``
+    [N,4,4], float32 on the state's device.  Returns ``(depth [N,height,width] float32, normals [N,height,width,3] float32 or None, rgb
+    [N,height,width,3] uint8 or None)``.  Runs on the current stream without touching the host."""
+    name = "sparse_raycast"
+    dev = state.device
+    check_tensors(name, index, dtype=torch.int64, label="index", shape=(raycast_index_slots(state.max_bricks), 2), device=dev, contiguous=True)
+    check_tensors(name, flags, dtype=torch.uint8, label="flags", shape=(state.max_bricks,), device=dev, contiguous=True)
+    check_tensors(name, neighbour, dtype=torch.int32, label="neighbour", shape=(state.max_bricks, EXTRACT_ROW), device=dev, contiguous=True)
+    check_tensors(name, cam_intr, label="cam_intr", shape=(None, 3, 3), device=dev)
+    check_tensors(name, cam_pose, label="cam_pose", shape=(None, 4, 4), device=dev)
+    N = int(cam_pose.shape[0])
+    height, width = int(height), int(width)
+    if N < 1 or cam_intr.shape[0] != N or height < 1 or width < 1:
+        raise ValueError(f"dvmvs::{name}: expected N >= 1 poses and as many intrinsics and a positive image size, got "
+                         f"{tuple(cam_pose.shape)}, {tuple(cam_intr.shape)}, {height}x{width}")
+    near, far, step, voxel_size = float(near), float(far), float(step), float(voxel_size)
+    if not (0.0 < step <= 5.0):
+        raise ValueError(f"dvmvs::{name}: step must be in (0, 5] voxels (the truncation), got {step}")
+    if not (0.0 <= near < float("inf")) or far != far:
+        raise ValueError(f"dvmvs::{name}: near must be finite and >= 0 and far not NaN, got {near}, {far}")
+    if not voxel_size > 0.0:
+        raise ValueError(f"dvmvs::{name}: voxel_size must be positive, got {voxel_size}")
+    origin = [float(o) for o in origin]
+    first, count = [int(f) for f in first_brick], [int(c) for c in count]
+    if len(origin) != 3 or len(first) != 3 or len(count) != 3:
+        raise ValueError(f"dvmvs::{name}: origin, first_brick and count must have three components")
+    if min(count) < 1 or max(count) > 1 << 21 or min(first) < -(1 << 20) or max(f + c - 1 for f, c in zip(first, count)) > 1 << 20:
+        raise ValueError(f"dvmvs::{name}: the box of {count} bricks from {first} is empty or leaves the lattice's coordinate range")
+    if raycast_steps(count, step) >= RAYCAST_MAX_STEPS:
+        raise ValueError(f"dvmvs::{name}: the box of {count} bricks is too long to march at step {step}")
+    cam_intr, cam_pose = cam_intr.contiguous(), cam_pose.contiguous()
+    depth = torch.empty((N, height, width), dtype=torch.float32, device=dev)
+    normal = torch.empty((N, height, width, 3), dtype=torch.float32, device=dev) if normals else None
+    rgb = torch.empty((N, height, width, 3), dtype=torch.uint8, device=dev) if colour else None
+    launch("dvmvs_sparse_raycast_fwd", dev, ptr(state.tsdf), ptr(state.weight), ptr(state.color) if colour else None, ptr(state.status),
+           state.max_bricks, ptr(index), int(index.shape[0]), ptr(neighbour), ptr(flags), first[0], first[1], first[2], count[0], count[1],
+           count[2], origin[0], origin[1], origin[2], voxel_size, 1 if skip_empty else 0, ptr(cam_intr), ptr(cam_pose), N, height, width,
+           near, far, step, ptr(depth), opt_ptr(normal), opt_ptr(rgb))
+    return depth, normal, rgb

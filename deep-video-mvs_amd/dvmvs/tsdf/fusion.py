@@ -115,7 +115,7 @@ class LiveFusion:
     from ``sparse_origin`` and a pool of ``max_bricks`` bricks of 8 x 8 x 8 voxels) instead, which allocates what the frames touch; frames
     before a brick's birth are not applied to it -- the one stated difference from the dense volume, inherent to every hashed volume.
     ``volume`` is then ``sparse.dense()``, a ``TSDFVolume`` over the allocated bricks, made when it is asked for (one host read) and kept
-    until the next ``add``; ``get_mesh`` / ``mesh_tensors`` take the surface straight from the sparse volume's pool, without ``dense()``
+    until the next ``add``; ``get_mesh`` / ``mesh_tensors`` / ``render`` take the surface straight from the sparse volume's pool, without ``dense()``
     (with bounds given: from the dense volume).  The consistency filter works on the depth maps before fusion and is the same in both modes.  With bounds
     given nothing differs from what it was: ``sparse`` is None."""
 
@@ -241,3 +241,10 @@ class LiveFusion:
     def mesh_tensors(self, **stages):
         """``(verts, faces)`` device tensors of the reconstruction so far; as ``get_mesh``."""
         return self._surface_source().mesh_tensors(**stages)
+
+    def render(self, cam_intr, cam_poses, height, width, **settings):
+        """``render`` of the reconstruction so far (``near`` / ``far`` / ``step`` / ``normals`` / ``colour`` / ``skip_empty`` as
+        ``TSDFVolume.render`` takes them): pending frames are fused first.  Without bounds the views are ray-cast straight from the sparse
+        volume's pool (``SparseTSDFVolume.render``, which also takes ``bounds=``): ``volume`` is not made, so looking at the reconstruction
+        while it grows costs no dense copy.  With bounds given: ``TSDFVolume.render`` of the dense volume."""
+        return self._surface_source().render(cam_intr, cam_poses, height, width, **settings)

@@ -21,7 +21,7 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
         evaluate_3d_visible=False, evaluate_3d_min_views=1, evaluate_3d_align=None, evaluate_3d_align_scale=False, evaluate_3d_align_plane=False,
         evaluate_3d_align_neighbours=20, evaluate_3d_align_normal_distance=None, point_mesh_voxel=None, point_mesh_radius=None,
         point_mesh_neighbours=32, point_mesh_min_neighbours=3,
-        sparse_volume=False, sparse_volume_bricks=65536, sparse_volume_extract=False,      # (here, not last: the places of the parameters behind them are pinned by tests)
+        sparse_volume=False, sparse_volume_bricks=65536, sparse_volume_extract=False, sparse_volume_render=False,      # (here, not last: the places of the parameters behind them are pinned by tests)
         simplify_mesh_voxel=None, simplify_mesh_average=False,
         smooth_mesh_iterations=None, smooth_mesh_laplacian=False, smooth_mesh_lambda=None, smooth_mesh_mu=None, smooth_mesh_fixed_boundary=False,
         groundtruth_transform=None, point_normals_neighbours=None,
@@ -152,7 +152,11 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     (``SparseTSDFVolume.get_mesh``: extract -> clean -> smooth -> simplify on device tensors) and ``evaluate_3d`` scores with the sparse
     volume's ``score_against``; ``dense()`` is called only when another requested stage needs a ``TSDFVolume`` (``render_keyframes``).  The
     surface is the dense one's as a set of welded triangles, listed by brick instead of by voxel; the output folder stays
-    ``<system_name>+sparse``."""
+    ``<system_name>+sparse``.
+
+    ``sparse_volume_render`` (needs ``sparse_volume``): ``render_keyframes`` ray-casts the keyframes straight from the sparse volume's pool
+    (``SparseTSDFVolume.render``) instead of from ``dense()``; the files are the same bytes.  With ``sparse_volume_extract`` as well,
+    ``dense()`` is never called."""
     settings = _settings(locals())            # (the first statement: locals() is the arguments and nothing else) every refusal without a file
     scene = _load_scene(settings)
     keyframe_images, keyframe_predictions = _load_keyframes(settings, scene)
@@ -160,12 +164,13 @@ def run(reconstruction_folder, prediction_folder, data_folder, dataset_name, sce
     products = _filter_keyframes(settings, scene, keyframe_images, keyframe_predictions)
     os.makedirs(settings.reconstruction_folder, exist_ok=True)
     groundtruth_surface = _groundtruth_surface(settings, scene, groundtruths, volume_bounds)
-    volume, mesh_name = _fuse_system(settings, scene, keyframe_images, products.predictions, volume_bounds)
+    sparse = sparse_volume_for(settings, volume_bounds) if settings.sparse_volume else None
+    volume, mesh_name = _fuse_system(settings, scene, keyframe_images, products.predictions, volume_bounds, sparse)
     _write_point_clouds(settings, mesh_name, products)
     if settings.evaluate_3d:
         _evaluate_3d(settings, scene, volume, groundtruth_surface, mesh_name)
     if settings.render_keyframes:
-        _render_keyframes(settings, scene, _renderable(volume, volume_bounds))
+        _render_keyframes(settings, scene, sparse if settings.sparse_volume_render else _renderable(volume, volume_bounds), volume_bounds)
 
 
 # ---- settings: run's arguments, checked ---------------------------------------------------------------------------------------------------
@@ -209,6 +214,7 @@ class Settings:
     point_mesh: Optional[tuple]        # (voxel, radius, neighbours, min_neighbours) of point_mesh_*, or None
     sparse_volume: bool = False        # fuse the system's predictions into a SparseTSDFVolume, then dense()
     sparse_volume_bricks: int = 65536
+    sparse_volume_render: bool = False    # render_keyframes ray-casts the sparse volume's pool instead of dense()
     sparse_volume_extract: bool = False   # the system's meshes and score straight from the sparse volume's pool; dense() only for rendering
 
 
@@ -260,6 +266,8 @@ def _settings(arguments):
         raise ValueError(f"sparse_volume_bricks must be at least 1, got {a.sparse_volume_bricks}")
     if a.sparse_volume_extract and not a.sparse_volume:
         raise ValueError("sparse_volume_extract meshes the pool of sparse_volume: it needs sparse_volume")
+    if a.sparse_volume_render and not a.sparse_volume:
+        raise ValueError("sparse_volume_render ray-casts the pool of sparse_volume: it needs sparse_volume")
     output_name = a.system_name + ("+sparse" if a.sparse_volume else "") + ("+consistent" if a.filter_consistency else "") + ("+clean" if clean is not None else "") + (
         "+smooth" if smooth is not None else "") + ("+simple" if simplify is not None else "")
     return Settings(
@@ -277,7 +285,7 @@ def _settings(arguments):
         align={"align_distance": a.evaluate_3d_align, "align_scale": a.evaluate_3d_align_scale, "align_plane": align_plane},
         clean=clean, simplify=simplify, smooth=smooth, clean_points=clean_points, point_normals=point_normals, point_mesh=point_mesh,
         sparse_volume=bool(a.sparse_volume), sparse_volume_bricks=int(a.sparse_volume_bricks),
-        sparse_volume_extract=bool(a.sparse_volume_extract))
+        sparse_volume_render=bool(a.sparse_volume_render), sparse_volume_extract=bool(a.sparse_volume_extract))
 
 
 def _number(value):
@@ -611,11 +619,13 @@ def _groundtruth_surface(settings, scene, groundtruths, volume_bounds):
     return surface
 
 
-def _fuse_system(settings, scene, images, predictions, volume_bounds):
-    """Fuses the keyframe predictions and writes the system's meshes (``TSDFFusion.integrate``): ``(the volume, the mesh name)``."""
+def _fuse_system(settings, scene, images, predictions, volume_bounds, sparse=None):
+    """Fuses the keyframe predictions and writes the system's meshes (``TSDFFusion.integrate``): ``(the volume, the mesh name)``.  With
+    ``sparse_volume`` the frames go into ``sparse`` (``sparse_volume_for``; made here when None), which the caller keeps."""
     mesh_name = _mesh_name(settings, settings.output_name)
     if settings.sparse_volume:
-        return _fuse_system_sparse(settings, scene, images, predictions, volume_bounds, mesh_name), mesh_name
+        sparse = sparse_volume_for(settings, volume_bounds) if sparse is None else sparse
+        return _fuse_system_sparse(settings, scene, images, predictions, volume_bounds, mesh_name, sparse), mesh_name
     volume = TSDFVolume(volume_bounds, voxel_size=settings.voxel_size, device=settings.device)
     TSDFFusion.integrate(volume, images, predictions, scene.keyframe_poses, scene.scaled_K, mesh_name, settings.save_progressive,
                          simplify=settings.simplify, smooth=settings.smooth, clean=settings.clean)
@@ -630,11 +640,10 @@ def sparse_volume_for(settings, volume_bounds):
                             device=settings.device)
 
 
-def _fuse_system_sparse(settings, scene, images, predictions, volume_bounds, mesh_name):
-    """``_fuse_system`` through a ``SparseTSDFVolume``: every keyframe with weight 1, then ``dense()`` over the allocated bricks (over the
+def _fuse_system_sparse(settings, scene, images, predictions, volume_bounds, mesh_name, sparse):
+    """``_fuse_system`` through the ``SparseTSDFVolume`` ``sparse``: every keyframe with weight 1, then ``dense()`` over the allocated bricks (over the
     bounds when nothing was allocated); the meshes are written as ``TSDFFusion.integrate`` writes them.  With ``sparse_volume_extract``
     the meshes come from the pool, nothing is made dense, and the sparse volume itself is returned."""
-    sparse = sparse_volume_for(settings, volume_bounds)
     stages = dict(simplify=settings.simplify, smooth=settings.smooth, clean=settings.clean)
 
     def meshed():      # what the meshes are taken from
@@ -750,8 +759,10 @@ def _evaluate_3d(settings, scene, volume, groundtruth, mesh_name):
                         **_smooth_entries(settings.smooth), **_simplify_entries(volume, clean, settings.simplify, settings.smooth))
 
 
-def _render_keyframes(settings, scene, volume):
-    """The fused depth of every keyframe: rendered, saved like predictions and, where ground truth exists, scored on the device."""
+def _render_keyframes(settings, scene, volume, volume_bounds=None):
+    """The fused depth of every keyframe: rendered, saved like predictions and, where ground truth exists, scored on the device.  A
+    ``SparseTSDFVolume`` is ray-cast from its pool over the box of its allocated bricks (over ``volume_bounds`` when it has none): the box
+    of ``_renderable``."""
     from dvmvs.dataset_loader import load_depth_png
     from dvmvs.errors import compute_errors_device
     from dvmvs.utils import save_predictions, save_results
@@ -760,7 +771,10 @@ def _render_keyframes(settings, scene, volume):
     if not poses:
         print("No keyframe to render")
         return
-    depth, _, _ = volume.render(scene.scaled_K, np.stack(poses), scene.height, scene.width, normals=False, colour=False)
+    box = {}
+    if not isinstance(volume, TSDFVolume) and volume.brick_extent is None:
+        box = {"bounds": volume_bounds}
+    depth, _, _ = volume.render(scene.scaled_K, np.stack(poses), scene.height, scene.width, normals=False, colour=False, **box)
     hit = depth > 0
     print("Rendered {} keyframes from the fused volume: {:.1f} % of the pixels hit a surface".format(len(poses), 100.0 * float(hit.float().mean())))
     rendered = depth.cpu().numpy()
@@ -911,6 +925,9 @@ def build_parser():
     parser.add_argument("--sparse_volume_extract", action="store_true",
                         help="with --sparse_volume: write the system's meshes and score them straight from the allocated bricks (marching cubes "
                              "over the pool); the volume is made dense only for --render_keyframes")
+    parser.add_argument("--sparse_volume_render", action="store_true",
+                        help="with --sparse_volume: --render_keyframes ray-casts the keyframes straight from the allocated bricks, without "
+                             "making the volume dense")
     return parser
 
 

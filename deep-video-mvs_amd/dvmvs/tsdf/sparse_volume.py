@@ -1,7 +1,8 @@
 """``SparseTSDFVolume``: a TSDF volume that needs no bounds.  Space is an unbounded lattice of 8 x 8 x 8-voxel
 bricks, a hash table on the device maps brick coordinates to existence, a pool of fixed capacity holds the voxels of the bricks that the
 frames' truncation bands touched, and only those are updated.  ``dense()`` hands the result to everything that takes a ``TSDFVolume``;
-``mesh_tensors`` / ``get_mesh`` and what builds on them extract the surface straight from the pool."""
+``mesh_tensors`` / ``get_mesh`` and what builds on them extract the surface straight from the pool, and
+``render`` ray-casts it from the pool."""
 import numpy as np
 import torch
 
@@ -44,6 +45,8 @@ class SparseTSDFVolume:
         self.device = self._state.tsdf.device
         self.frames = 0                   # frames given so far: the number of the next frame
         self._neighbour = None            # neighbour table of the extraction: describes which bricks exist, so integrate_frames drops it
+        self._render_tables = None        # (index, flags) of render(): describe the pool's keys and contents; dropped likewise
+        self._render_read = None          # (status, extent) of render(): its one host read per state of the volume; dropped likewise
 
     voxel_size = property(lambda self: self._voxel_size)
     origin = property(lambda self: self._origin.copy())
@@ -92,7 +95,7 @@ class SparseTSDFVolume:
             raise ValueError("max_depth is NaN")
         first, state = self.frames, self._state
         self.frames += n                  # (before the calls: a failed call may have been enqueued)
-        self._neighbour = None
+        self._neighbour = self._render_tables = self._render_read = None
         hip_sparse.sparse_mark(state, depth, K, P, self._origin, self._voxel_size, self._trunc_margin, max_depth, first)
         hip_sparse.sparse_assign(state)
         hip_sparse.sparse_integrate(state, depth, K, P, rgb, folded, self._origin, self._voxel_size, self._trunc_margin, weights, max_depth,
@@ -140,6 +143,35 @@ class SparseTSDFVolume:
         o = self._origin.astype(np.float64)
         return np.stack([o + first * size, o + (last + 1) * size], axis=1)
 
+    def _refuse_overflow(self, what, status, allow_overflow):
+        lost = status[hip_sparse.STATUS_DROPPED_POOL] + status[hip_sparse.STATUS_DROPPED_TABLE]
+        if lost and not allow_overflow:
+            raise RuntimeError(f"SparseTSDFVolume.{what}: {status[hip_sparse.STATUS_DROPPED_POOL]} bricks did not fit the pool of "
+                               f"{self._state.max_bricks} and {status[hip_sparse.STATUS_DROPPED_TABLE]} marks found no table slot: the volume is "
+                               f"incomplete (a larger max_bricks / table_slots, or allow_overflow=True)")
+
+    def _box(self, what, bounds, extent):
+        """The brick-aligned box of ``dense()`` and ``render()``, so the two cannot drift: ``(first [3] int64, count [3] int64, low [3]
+        float64)`` -- ``bounds`` grown outwards to whole bricks, or without ``bounds`` the box of ``extent`` = (first, last) allocated brick
+        per axis (None: no brick).  ``low = origin + first * 8 * voxel``; the box's float32 origin is ``low.astype(float32)`` and its
+        dimensions are ``8 * count`` voxels."""
+        size = BRICK * np.float64(np.float32(self._voxel_size))
+        o = self._origin.astype(np.float64)
+        if bounds is None:
+            if extent is None:
+                raise ValueError(f"SparseTSDFVolume.{what}: no brick is allocated and no bounds were given")
+            first, last = (np.asarray(e, dtype=np.int64) for e in extent)
+        else:
+            bounds = np.asarray(bounds, dtype=np.float64)
+            if bounds.shape != (3, 2) or not np.isfinite(bounds).all() or not (bounds[:, 1] > bounds[:, 0]).all():
+                raise ValueError(f"SparseTSDFVolume.{what}: bounds must be a finite [[x0,x1],[y0,y1],[z0,z1]] with x1 > x0 ...")
+            first = np.floor((bounds[:, 0] - o) / size).astype(np.int64)
+            last = np.ceil((bounds[:, 1] - o) / size).astype(np.int64) - 1
+        count = (last - first + 1).astype(np.int64)
+        if (np.abs(first) > (1 << 20)).any() or (np.abs(last) > (1 << 20)).any():
+            raise ValueError(f"SparseTSDFVolume.{what}: the box leaves the lattice's coordinate range")
+        return first, count, o + first * size
+
     def dense(self, bounds=None, allow_overflow=False):
         """A ``TSDFVolume`` over the brick-aligned box of the allocated bricks, or over ``bounds`` ([[x0,x1],[y0,y1],[z0,z1]] in metres,
         grown outwards to whole bricks), holding the allocated bricks' voxels and (1, 0, 0) elsewhere.  This is the one host read of the
@@ -155,34 +187,75 @@ class SparseTSDFVolume:
         state = self._state
         status = self._status()
         n = status[hip_sparse.STATUS_BRICKS]
-        lost = status[hip_sparse.STATUS_DROPPED_POOL] + status[hip_sparse.STATUS_DROPPED_TABLE]
-        if lost and not allow_overflow:
-            raise RuntimeError(f"SparseTSDFVolume.dense: {status[hip_sparse.STATUS_DROPPED_POOL]} bricks did not fit the pool of "
-                               f"{state.max_bricks} and {status[hip_sparse.STATUS_DROPPED_TABLE]} marks found no table slot: the volume is "
-                               f"incomplete (a larger max_bricks / table_slots, or allow_overflow=True)")
-        size = BRICK * np.float64(np.float32(self._voxel_size))
-        o = self._origin.astype(np.float64)
-        if bounds is None:
-            if n == 0:
-                raise ValueError("SparseTSDFVolume.dense: no brick is allocated and no bounds were given")
+        self._refuse_overflow("dense", status, allow_overflow)
+        extent = None
+        if bounds is None and n > 0:
             coords = unpack_keys(state.pool_key[:n].cpu().numpy())
-            first, last = coords.min(axis=0), coords.max(axis=0)
-        else:
-            bounds = np.asarray(bounds, dtype=np.float64)
-            if bounds.shape != (3, 2) or not np.isfinite(bounds).all() or not (bounds[:, 1] > bounds[:, 0]).all():
-                raise ValueError("SparseTSDFVolume.dense: bounds must be a finite [[x0,x1],[y0,y1],[z0,z1]] with x1 > x0 ...")
-            first = np.floor((bounds[:, 0] - o) / size).astype(np.int64)
-            last = np.ceil((bounds[:, 1] - o) / size).astype(np.int64) - 1
-        count = (last - first + 1).astype(np.int64)
-        if (np.abs(first) > (1 << 20)).any() or (np.abs(last) > (1 << 20)).any():
-            raise ValueError("SparseTSDFVolume.dense: the box leaves the lattice's coordinate range")
-        low = o + first * size
+            extent = coords.min(axis=0), coords.max(axis=0)
+        first, count, low = self._box("dense", bounds, extent)
         # (the upper bound half a voxel short: TSDFVolume takes ceil((x1 - x0) / voxel) voxels, which is then the brick count times 8)
         volume = TSDFVolume(np.stack([low, low + (count * BRICK - 0.5) * self._voxel_size], axis=1), self._voxel_size, device=self.device)
         if tuple(int(d) for d in volume.vol_dim) != tuple(int(c) * BRICK for c in count):
             raise RuntimeError(f"SparseTSDFVolume.dense: a box of {tuple(int(c) for c in count)} bricks became a volume of {tuple(volume.vol_dim)} voxels")
         hip_sparse.sparse_gather(state, n, volume._tsdf, volume._weight, volume._color, first)
         return volume
+
+    def _render_state(self):
+        """``(status, extent)``: the status words and the (first, last) allocated brick per axis (None without a brick), the minimum and
+        maximum of the key fields of the slots < n_bricks computed on the device.  ONE host read, kept until the next ``integrate_frames``."""
+        if self._render_read is None:
+            state = self._state
+            with torch.cuda.device(self.device):
+                live = torch.arange(state.max_bricks, dtype=torch.int64, device=self.device) < state.status[hip_sparse.STATUS_BRICKS]
+                fields = torch.stack([(state.pool_key >> shift) & 0x1FFFFF for shift in (42, 21, 0)], dim=1) - ((1 << 20) - 1)
+                low = torch.where(live[:, None], fields, torch.full_like(fields, 1 << 40)).amin(dim=0)
+                high = torch.where(live[:, None], fields, torch.full_like(fields, -(1 << 40))).amax(dim=0)
+                words = [int(x) for x in torch.cat([state.status, low, high]).cpu()]      # the one host read
+            status, low, high = words[:hip_sparse.STATUS_WORDS], words[-6:-3], words[-3:]
+            extent = (np.array(low, dtype=np.int64), np.array(high, dtype=np.int64)) if status[hip_sparse.STATUS_BRICKS] > 0 else None
+            self._render_read = status, extent
+        return self._render_read
+
+    @property
+    def brick_extent(self):
+        """``(first [3], last [3])`` brick coordinates of the box of the allocated bricks, or None when there is no brick: the box that
+        ``render`` takes without ``bounds`` (its one host read, kept until the next ``integrate_frames``)."""
+        extent = self._render_state()[1]
+        return None if extent is None else (extent[0].copy(), extent[1].copy())
+
+    def render(self, cam_intr, cam_poses, height, width, near=0.0, far=float("inf"), step=1.0, normals=True, colour=True, skip_empty=True,
+               bounds=None, allow_overflow=False):
+        """``TSDFVolume.render`` of this volume, without a dense copy (csrc/sparse_raycast.hip): for the box that
+        ``dense(bounds)`` computes -- ``bounds`` grown outwards to whole bricks, or without ``bounds`` the box of the allocated bricks --
+        ``(depth [N,height,width] float32, normals [N,height,width,3] float32 or None, rgb [N,height,width,3] uint8 or None)`` equal BIT FOR
+        BIT to ``self.dense(bounds).render(...)`` with the same ``near``, ``far``, ``step``, ``normals``, ``colour`` and ``skip_empty``.
+        ``skip_empty`` jumps over unallocated bricks and bricks without a crossing; the result is the same bits either way.
+
+        The host is read at most once per state of the volume (the status words and the box of the allocated bricks, computed on the
+        device), and that read, the render index, the bricks' crossing flags and the neighbour table are built on first use and kept until
+        the next ``integrate_frames``.  ``RuntimeError`` when bricks were dropped (``overflow``), unless ``allow_overflow``; ``ValueError``
+        when there is no brick and no ``bounds``, and when the box is too long to march (pass ``bounds=``).
+
+        Coordinates are BOX-RELATIVE float32: a point of a ray is ``g = (p - box origin) / voxel``.  A caller whose volume has parts far
+        apart should pass ``bounds`` around what is looked at: without them the box spans everything, and where ``g`` reaches 2^18 voxels
+        the trilinear weights ``g - floor(g)`` have only 2^-5 voxel of resolution left."""
+        state = self._state
+        status, extent = self._render_state()
+        self._refuse_overflow("render", status, allow_overflow)
+        first, count, low = self._box("render", bounds, extent)
+        step = float(step)
+        if not 0.0 < step <= 5.0:
+            raise ValueError(f"SparseTSDFVolume.render: step must be in (0, 5] voxels (the truncation), got {step}")
+        if (count > 1 << 21).any() or hip_sparse.raycast_steps(count, step) >= hip_sparse.RAYCAST_MAX_STEPS:
+            raise ValueError(f"SparseTSDFVolume.render: a box of {tuple(int(c) for c in count)} bricks is too long to march at step {step}: "
+                             f"pass bounds= around what is looked at")
+        K, P = camera_tensors(cam_intr, cam_poses, self.device)
+        if self._render_tables is None:
+            index = hip_sparse.sparse_raycast_index(state)
+            self._render_tables = index, hip_sparse.sparse_raycast_flags(state, self.neighbours(), index)
+        index, flags = self._render_tables
+        return hip_sparse.sparse_raycast(state, index, flags, self.neighbours(), first, count, low.astype(np.float32), self._voxel_size, K, P,
+                                         height, width, near=near, far=far, step=step, normals=normals, colour=colour, skip_empty=skip_empty)
 
     def neighbours(self):
         """The neighbour table of the allocated bricks (``dvmvs.hip.sparse.sparse_neighbours``; int32 [max_bricks, 27] on the device),

@@ -79,7 +79,9 @@ extern "C" {
  * ABI 11, later addition: dvmvs_mesh_smooth_* (smoothing a triangle mesh by the Laplacian and Taubin filters; vertex normals from the
  * faces); no earlier signature changed, the number stays 11 by the same rule.
  * ABI 11, later addition: dvmvs_sparse_neighbours and dvmvs_sparse_extract_* (marching cubes straight from the pool of the sparse TSDF
- * volume); no earlier signature changed, the number stays 11 by the same rule. */
+ * volume); no earlier signature changed, the number stays 11 by the same rule.
+ * ABI 11, later addition: dvmvs_sparse_raycast_* (ray-casting the sparse TSDF volume straight from its pool); no earlier signature
+ * changed, the number stays 11 by the same rule. */
 #define DVMVS_ABI_VERSION 11
 #define DVMVS_MAX_MEASUREMENTS 8      /* measurement frames fused per launch */
 #define DVMVS_MAX_DEPTH_LEVELS 256    /* sweep planes per launch */
@@ -1415,6 +1417,46 @@ int dvmvs_sparse_extract_emit(const float* pool_tsdf, const float* pool_color, c
                               const long long* offsets, long long n_bricks, float origin_x, float origin_y, float origin_z, float voxel_size,
                               int* vertex_base, float* verts, float* normals, unsigned char* colors, int* faces, long long V, long long F,
                               dvmvs_stream_t stream);
+
+/*
+ * Ray-casting the sparse volume straight from its pool (ABI 11, later addition; csrc/sparse_raycast.hip, csrc/sparse_raycast_grid.h;
+ * DESIGN.md section 4.8t).  No dense copy is made.
+ * Definition.  For the brick-aligned box of count_x x count_y x count_z bricks whose first brick is (first_x, first_y, first_z),
+ *   dvmvs_sparse_raycast_fwd writes depth, normal and rgb equal BIT FOR BIT to those of dvmvs_tsdf_raycast_fwd with the same origin,
+ *   voxel_size, cameras, near, far and step on the dense volume of 8 count voxels per axis whose voxel w holds the pool's voxel of brick
+ *   first + (w >> 3) at local index (w & 7) (x * 64 + y * 8 + z) when that brick is allocated (a slot < status[0]) and (tsdf 1,
+ *   weight 0, colour 0) otherwise -- what dvmvs_sparse_gather puts there.  The per-pixel statements are those of the dense kernel, one by
+ *   one; only where a voxel is read from differs.  skip_empty != 0 jumps over unallocated bricks and over bricks without a crossing
+ *   corner with verified jumps; the outputs are the same bits either way.
+ * Inputs read: status, pool_key and the pool arrays; the volume's hash table is not.
+ * dvmvs_sparse_raycast_index: the render index, index [2 index_slots] int64, index_slots a power of two >= 2 max_bricks.  Entry e =
+ *   (key, value); every entry is cleared to (EMPTY, -1), then the key of every slot < status[0] (read on the device) takes the first free
+ *   entry on its probe path (splitmix64 finaliser, linear probing, 64-bit compare-and-swap; at most index_slots attempts) with the value
+ *   = its slot.  Which entry a key lands in may depend on the schedule; what a lookup returns does not.
+ * dvmvs_sparse_raycast_flags: neighbour = the table of dvmvs_sparse_neighbours.  flags [max_bricks] uint8: for slots < status[0], 1 when
+ *   one of the 9^3 corners of the brick's cells (local 0 .. 8 per axis: its own voxels and the first layer of its seven forward
+ *   neighbours, where allocated) has weight > 0 && tsdf <= 0; the same bit is set in the brick's index value (slot | flag << 32).  Index
+ *   and flags describe the pool's CURRENT keys and contents: rebuild them after every flush.
+ * dvmvs_sparse_raycast_fwd: depth [N,h,w] fp32; normal [N,h,w,3] fp32 or NULL; rgb [N,h,w,3] uint8 or NULL (then pool_color may be NULL).
+ *   One lane per pixel, an 8x8 tile per wave, 16x16 per workgroup, one grid plane per view.  Every dereferenced pool slot comes from an
+ *   index value or a neighbour entry checked against [0, min(status[0], max_bricks)).
+ * Refusals, all before anything is enqueued.  DVMVS_EINVAL: a null pointer; max_bricks < 1; index_slots not a power of two or
+ *   < 2 max_bricks; n_views, im_h, im_w or a count < 1; a box that leaves [-2^20, 2^20] bricks; voxel_size <= 0; step outside (0, 5];
+ *   near < 0 or not finite; far NaN.  DVMVS_EUNSUPPORTED: 2^31 pool slots; a count above 2^21; h * w >= 2^31; more than 65535 views or
+ *   tile rows; 2^32 threads; a box whose diagonal in steps, floor(|8 count - 1| / step) + 2, reaches 2^20.  The dense entry's limits
+ *   Y * Z < 2^31 and 2^26 bricks do not apply: nothing is indexed by the box.
+ */
+int dvmvs_sparse_raycast_index(const long long* pool_key, const long long* status, long long max_bricks, long long* index,
+                               long long index_slots, dvmvs_stream_t stream);
+int dvmvs_sparse_raycast_flags(const float* pool_tsdf, const float* pool_weight, const long long* pool_key, const int* neighbour,
+                               const long long* status, long long max_bricks, long long* index, long long index_slots, unsigned char* flags,
+                               dvmvs_stream_t stream);
+int dvmvs_sparse_raycast_fwd(const float* pool_tsdf, const float* pool_weight, const float* pool_color, const long long* status,
+                             long long max_bricks, const long long* index, long long index_slots, const int* neighbour,
+                             const unsigned char* flags, int first_x, int first_y, int first_z, int count_x, int count_y, int count_z,
+                             float origin_x, float origin_y, float origin_z, float voxel_size, int skip_empty, const float* cam_intr,
+                             const float* cam_pose, int n_views, int im_h, int im_w, float near, float far, float step, float* depth,
+                             float* normal, unsigned char* rgb, dvmvs_stream_t stream);
 
 #ifdef __cplusplus
 }
